@@ -15,6 +15,13 @@ frame f vs frame f-1 match.
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 through torch.distributed.run
 (one process per GPU, RCCL).  Rank 0 prints one JSON line.
+
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps and half a
+second more of them until the clocks have settled (--settle-s), K timed steps, the result line (metric, value, ms_per_step, the configuration and the end-to-end byte
+model, which is arithmetic on `value`).  ``--full`` adds every leg that takes runs of its own:
+the untimed soak, the per-kernel probe steps and the roofline leg, the CPU baseline, config 2's
+batch sweep and config 5's SearchByProjection-alone leg.  ``--dump-outputs DIR`` writes what the
+last timed step left in the output buffers as DIR/<name>.npy (float32 / float64).
 """
 from __future__ import annotations
 
@@ -248,13 +255,15 @@ def run_c5(args) -> None:
     # A14 alone ("time A17+A14 together and A14 alone"): the same
     # frame and map with isInFrustum's outputs already in HBM (computed once, untimed) —
     # SearchByProjection(F, vpLocalMapPoints, th) by itself
+    # (--full only)
     sf_np = np.asarray(scale, np.float32)
-    inv, px, py, pxr, pl, vc = mt.is_in_frustum(lm["xyz"], lm["normal"], lm["min_dist"],
-                                                lm["max_dist"], lm["tcw"], cam,
-                                                (0.0, float(W), 0.0, float(H)), log_scale, 0.5)
-    inv[(lm["skip"] > 0) | (lm["bad"] > 0)] = 0
-    A = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
-         for k, v in dict(inv=inv, px=px, py=py, pxr=pxr, pl=pl, vc=vc).items()}
+    if args.full:
+        inv, px, py, pxr, pl, vc = mt.is_in_frustum(lm["xyz"], lm["normal"], lm["min_dist"],
+                                                    lm["max_dist"], lm["tcw"], cam,
+                                                    (0.0, float(W), 0.0, float(H)), log_scale, 0.5)
+        inv[(lm["skip"] > 0) | (lm["bad"] > 0)] = 0
+        A = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+             for k, v in dict(inv=inv, px=px, py=py, pxr=pxr, pl=pl, vc=vc).items()}
 
     def step_a14():
         with torch.cuda.stream(cs):
@@ -287,10 +296,20 @@ def run_c5(args) -> None:
             el = float(t.item())
         return el
 
-    dt_a14 = timed(step_a14)
-    fmp_a14 = slots.clone()
+    if args.full:
+        dt_a14 = timed(step_a14)
+        fmp_a14 = slots.clone()
     dt = timed(step)
-    same_a14 = bool(torch.equal(fmp_a14, slots))  # both legs reach the same assignment
+    if args.full:
+        same_a14 = bool(torch.equal(fmp_a14, slots))  # both legs reach the same assignment
+    if args.dump_outputs and rank == 0:
+        # what the call hands back: the frame's MapPoint slots and their Observations(), the
+        # in-view byte per map point, (nmatches, nToMatch)
+        dump_arrays(args.dump_outputs, {
+            "frame_mp": slots[0].cpu().numpy().astype(np.float64),
+            "frame_mp_obs": slots[1].cpu().numpy().astype(np.float64),
+            "in_view": d_inv.cpu().numpy().astype(np.float32),
+            "counts": np.asarray(out["r"], np.float64)})
     if rank == 0:
         K = args.steps
         value = world * K / dt
@@ -301,7 +320,7 @@ def run_c5(args) -> None:
         nbytes = M * (12 + 12 + 8 + 32 + 4 + 1 + 1 + 4 + 1) + len(keys) * 60
         achieved = nbytes / (ms / 1e3) / 1e9
         cpu = None
-        if world == 1 and args.cpu_budget > 0:
+        if world == 1 and args.full and args.cpu_budget > 0:
             import oracle  # test infrastructure: the cpu_baseline leg is allowed to load it
             from orbslam_mapsave_amd.abi import Frame
             fr = Frame(keys, desc, W, H, scale)
@@ -327,13 +346,16 @@ def run_c5(args) -> None:
                              f"+ SearchByProjection, 1 thread, oracle/orb_oracle.cpp -O3, "
                              f"{el:.1f} s"}
         nm, nto = out["r"]
-        a14 = {"calls_per_s": round(world * K / dt_a14, 2),
-               "ms_per_call": round(dt_a14 / K * 1e3, 4), "nmatches": out["a14"],
-               "same_assignment_as_fused": same_a14,
-               "note": "orbfe_search_by_projection_local_device: isInFrustum outputs resident in "
-                       "HBM (computed once, untimed); grid + one kernel for the candidates "
-                       "(fixed per-point slots) and the greedy initialisation + blind greedy "
-                       "rounds + accept, one synchronisation (CSR path on overflow)"}
+        a14 = None
+        if args.full:
+            a14 = {"calls_per_s": round(world * K / dt_a14, 2),
+                   "ms_per_call": round(dt_a14 / K * 1e3, 4), "nmatches": out["a14"],
+                   "same_assignment_as_fused": same_a14,
+                   "note": "orbfe_search_by_projection_local_device: isInFrustum outputs "
+                           "resident in HBM (computed once, untimed); grid + one kernel for the "
+                           "candidates (fixed per-point slots) and the greedy initialisation + "
+                           "blind greedy rounds + accept, one synchronisation (CSR path on "
+                           "overflow)"}
         line = {
             "metric": C5_METRIC, "value": round(value, 2), "unit": "frames/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
@@ -351,9 +373,10 @@ def run_c5(args) -> None:
                          "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": None,
                          "bytes_per_launch": nbytes, "avg_launch_ms": round(ms, 4)},
-            "cpu_baseline": cpu,
-            "a14_alone": a14,
+            "full": args.full,
         }
+        if args.full:
+            line.update({"cpu_baseline": cpu, "a14_alone": a14})
         if cpu:
             line["gpu_over_cpu"] = round(value / cpu["value"], 1)
         print(json.dumps(line), flush=True)
@@ -389,11 +412,28 @@ def parse_args():
     # 100 timed steps: the two sub-batch streams' fill and drain at the ends of the timed region
     # (one stream's last kernels alone on the chip) weigh 1/K of it — c3 1.385 ms per step at
     # K = 20, 1.374 at K = 100 (profiles/r05/steps_k/)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the soak, the per-kernel "
+                         "probe steps and the roofline leg, the CPU baseline (--soak-s, "
+                         "--probe-steps, --profile and --cpu-budget size them), config 2's batch "
+                         "sweep and config 5's SearchByProjection-alone leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left in the output "
+                         "buffers as DIR/<name>.npy (float32 / float64; a fixed seeded sample of "
+                         "the frames, rows past a frame's count zeroed)")
     ap.add_argument("--soak-s", type=float, default=8.0,
-                    help="untimed wall-clock seconds of steps after the warmup (c2/c3/c4), so "
-                         "that an external GPU-utilisation sampler sees the load; 0 = off")
+                    help="--full: untimed wall-clock seconds of steps after the warmup "
+                         "(c2/c3/c4), so that an external GPU-utilisation sampler sees the load; "
+                         "0 = off")
+    # a plain run's warm-up: without it the timed steps begin milliseconds after the first
+    # launch and run 3-4 % slower at K = 20 (1.39-1.41 ms per c3 step against 1.35 after 0.5 s
+    # or after the 8 s soak; 2 s measures as 0.5 s), 1 % slower at K = 100
+    ap.add_argument("--settle-s", type=float, default=0.5,
+                    help="plain run (c2/c3/c4): the warm-up goes on for this many seconds of "
+                         "untimed steps, so that the timed steps start at settled clocks "
+                         "(--full soaks for --soak-s instead); 0 = off")
     ap.add_argument("--batch", type=int, default=512,
                     help="frames per rank per step (c3; 512: +4 %% frames/s over 256, level at 1024)")
     ap.add_argument("--config", default="c3", choices=["c2", "c3", "c4", "c5"])
@@ -407,8 +447,8 @@ def parse_args():
                          "A's all-gather runs while B is extracted); 0 = 2.  The probe and "
                          "roofline legs always run the whole batch on one stream")
     ap.add_argument("--probe-steps", type=int, default=2,
-                    help="steps after the warmup with events on every kernel, for the per-stage "
-                         "table and the choice of the dominant kernel")
+                    help="--full: steps after the warmup with events on every kernel, for the "
+                         "per-stage table and the choice of the dominant kernel")
     ap.add_argument("--chunks", type=int, default=1,
                     help="extraction calls per stream per step (each a sub-batch / chunks)")
     ap.add_argument("--pipeline", type=int, default=0,
@@ -421,17 +461,55 @@ def parse_args():
                          "for stream 0's chunk k*chunks/streams - 1), so the streams run "
                          "different stages at the same time")
     ap.add_argument("--profile", type=int, default=1,
-                    help="0: no per-kernel HIP events in the timed region (no roofline)")
+                    help="--full: 0 = no probe steps and no roofline leg")
     ap.add_argument("--cpu-budget", type=float, default=15.0,
-                    help="seconds of CPU-baseline work on rank 0 (0 disables)")
+                    help="--full: seconds of CPU-baseline work on rank 0 (0 disables)")
     return ap.parse_args()
 
 
-def run_extract(args, dev, rank, world, local, W, H, NF, NREF, B, mode, steps, warmup):
+def dump_arrays(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: one DIR/<name>.npy per array."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+DUMP_FRAMES = 64  # frames of a batch that --dump-outputs writes (seeded choice, ~15 MB at c3)
+
+
+def extract_outputs(d_kps, d_desc, d_n, d_out, cap: int) -> dict:
+    """What a caller of the extraction (+ match) step receives, as float arrays: every frame's
+    keypoint count, and for a fixed seeded sample of the frames the keypoints (x, y, size,
+    angle, response, octave, class_id), the descriptors' bytes and the match rows (best index,
+    best and second distance).  Rows past a frame's count are not part of the result (the
+    buffers are not cleared there) and are written as zeros."""
+    import torch
+    from orbslam_mapsave_amd.abi import KEYPOINT_DTYPE
+
+    B = d_n.shape[0]
+    sel = np.sort(np.random.default_rng(0).choice(B, min(B, DUMP_FRAMES), replace=False))
+    idx = torch.from_numpy(sel).to(d_n.device)
+    n = d_n.cpu().numpy()
+    live = np.arange(cap)[None, :] < n[sel][:, None]
+    k = d_kps[idx].cpu().numpy().view(KEYPOINT_DTYPE).reshape(len(sel), cap)
+    out = {"counts": n.astype(np.float32), "frame_index": sel.astype(np.float32),
+           "keypoints": np.where(live[:, :, None],
+                                 np.stack([k[f].astype(np.float32) for f in KEYPOINT_DTYPE.names],
+                                          -1), np.float32(0)),
+           "descriptors": np.where(live[:, :, None], d_desc[idx].cpu().numpy(),
+                                   0).astype(np.float32)}
+    if d_out is not None:
+        out["matches"] = np.where(live[:, :, None], d_out[idx].cpu().numpy(), 0).astype(np.float32)
+    return out
+
+
+def run_extract(args, dev, rank, world, local, W, H, NF, NREF, B, mode, steps, warmup,
+                dump_dir=None):
     """One extraction benchmark: every step, every rank extracts B frames (device-resident) and,
     by `mode`, matches nothing ("none", config 2), each frame against a 2000-kp reference
     ("ref", config 3), or each frame against its global predecessor after the descriptor
-    all-gather ("pred", config 4).  Returns the measurement (rank 0) or None."""
+    all-gather ("pred", config 4).  Returns the measurement (rank 0) or None.  The soak, the
+    probe steps and the roofline leg run with --full only."""
     import torch
     import torch.distributed as dist
     from orbslam_mapsave_amd.native import ORBextractor, ORBmatcher
@@ -606,9 +684,10 @@ def run_extract(args, dev, rank, world, local, W, H, NF, NREF, B, mode, steps, w
     # the measurement and settles the clocks.  Steady-state step time from 10 steps after the
     # warmup (the warmup's first calls include plan, workspace and graph setup); the soak then
     # runs in chunks of ~0.5 s and stops when every rank has passed --soak-s (collective counts
-    # stay paired).
+    # stay paired).  A plain run keeps only the clock settling: --settle-s (0.5) of the same.
     soak = {"seconds": 0.0, "steps": 0}
-    if args.soak_s > 0:
+    soak_s = args.soak_s if args.full else args.settle_s
+    if soak_s > 0:
         ta = time.perf_counter()
         for _ in range(10):
             step()
@@ -625,13 +704,13 @@ def run_extract(args, dev, rank, world, local, W, H, NF, NREF, B, mode, steps, w
                 step()
             barrier()
             soak["steps"] += chunk
-            if agreed(time.perf_counter() - ts >= args.soak_s):
+            if agreed(time.perf_counter() - ts >= soak_s):
                 break
         soak["seconds"] = round(time.perf_counter() - ts, 2)
         soak["steady_ms_per_step"] = round(tw * 1e3, 4)
     # Probe steps (untimed, single-stream): events on every kernel give the per-stage table and
     # pick the dominant kernel.
-    probe_steps = max(args.probe_steps, 1) if args.profile else 0
+    probe_steps = max(args.probe_steps, 1) if args.full and args.profile else 0
     for e in exs:
         e.profile(bool(probe_steps))
         e.profile_read()
@@ -652,6 +731,9 @@ def run_extract(args, dev, rank, world, local, W, H, NF, NREF, B, mode, steps, w
         step()
     barrier()
     dt = time.perf_counter() - t0
+    if dump_dir and rank == 0:  # before the roofline leg runs its single-stream steps
+        dump_arrays(dump_dir, extract_outputs(d_kps, d_desc, d_n,
+                                              d_out if mode != "none" else None, cap))
     # Roofline leg (untimed for `value`): the same number of steps single-stream with HIP events
     # on the dominant kernel's launches alone, so each event pair times that kernel with the chip
     # to itself (with S streams a launch shares the chip with the other sub-batch's kernels).
@@ -928,13 +1010,18 @@ def main() -> None:
         W, H, NF, NREF = 640, 480, 1000, 0
         metric = C2_METRIC
         workload = ("configs[1]: 640x480 extract only (8-level pyramid, FAST-9, oct-tree, "
-                    "rBRIEF, 1000 kp), batch sweep B in {1, 64, 256}, >= 1000 frames after 50 "
-                    "warm-up frames per B; value at B = 256")
-        sweep = {}
-        for Bc in (1, 64, 256):
+                    "rBRIEF, 1000 kp); value at B = 256, --steps timed steps" +
+                    ("; batch sweep B in {1, 64, 256}, at B = 1 and 64 >= 1000 frames after 50 "
+                     "warm-up frames" if args.full else ""))
+        # the headline run (B = 256, --steps timed steps) comes last, as its place in the sweep
+        sweep = {} if args.full else None
+        for Bc in ((1, 64, 256) if args.full else (256,)):
+            head = Bc == 256
             r = run_extract(args, dev, rank, world, local, W, H, NF, NREF, Bc, "none",
-                            max(args.steps, -(-1000 // Bc)), max(args.warmup, -(-50 // Bc)))
-            if rank == 0:
+                            args.steps if head else max(args.steps, -(-1000 // Bc)),
+                            args.warmup if head else max(args.warmup, -(-50 // Bc)),
+                            args.dump_outputs if head else None)
+            if rank == 0 and args.full:
                 sweep[str(Bc)] = {"frames_per_s": round(r["value"], 1),
                                   "ms_per_call": round(r["dt"] / r["K"] * 1e3, 4),
                                   "frames": Bc * r["K"] * world,
@@ -950,7 +1037,7 @@ def main() -> None:
         workload = ("configs[2]: 640x480 extract (8-level pyramid, FAST-9, oct-tree, rBRIEF, "
                     "1000 kp) + brute-force Hamming match vs a 2000-kp reference frame")
         r = run_extract(args, dev, rank, world, local, W, H, NF, NREF, B, "ref", args.steps,
-                        args.warmup)
+                        args.warmup, args.dump_outputs)
         parallelism = f"frame-sharded x{world}, no data-path collective"
     else:
         W, H, NF, NREF = 1920, 1080, ORB_YAML_NFEATURES, ORB_YAML_NFEATURES
@@ -959,12 +1046,12 @@ def main() -> None:
         workload = (f"configs[3]: 1920x1080 @2000 kp, global batch {B * world} sharded "
                     "round-robin, RCCL all-gather of descriptor slabs, frame f vs f-1 match")
         r = run_extract(args, dev, rank, world, local, W, H, NF, NREF, B, "pred", args.steps,
-                        args.warmup)
+                        args.warmup, args.dump_outputs)
         parallelism = f"frame-sharded x{world} + RCCL all-gather"
 
     if rank == 0:
         cpu = None
-        if world == 1 and args.cpu_budget > 0:
+        if world == 1 and args.full and args.cpu_budget > 0:
             if args.config == "c4":
                 cpu = cpu_baseline(r["frames_np"][:min(args.distinct, 8)], None, args.cpu_budget,
                                    NF, "(1920x1080, extract 2000 kp + BF match vs frame f-1)",
@@ -993,18 +1080,24 @@ def main() -> None:
                        "stage_pipeline": bool(args.pipeline) and S > 1 and args.config == "c3",
                        "global_batch": B * world, "nfeatures": NF, "reference_kp": r["ref_kp"],
                        "mean_kp_per_frame": round(r["nkp"], 1), "parallelism": parallelism},
-            "roofline": r["roofline"],
             "end_to_end": r["end_to_end"],
-            "cpu_baseline": cpu,
-            "stage_ms_per_step": {k: round(v, 4) for k, v in r["per_step"].items()},
-            "stage_roofline": r.get("stage_roofline"),
-            "stage_note": (f"summed kernel durations per step over {r['probe_steps']} untimed "
-                           "single-stream probe steps (events on every launch, the whole batch "
-                           "in one call); the timed steps are uninstrumented" +
-                           (f" and overlap {S} sub-batch streams, so ms_per_step is below the "
-                            "sum" if S > 1 else "")),
-            "soak": r["soak"],
+            "full": args.full,
         }
+        if not args.full:
+            line["settle"] = r["soak"]
+        if args.full:
+            line.update({
+                "roofline": r["roofline"],
+                "cpu_baseline": cpu,
+                "stage_ms_per_step": {k: round(v, 4) for k, v in r["per_step"].items()},
+                "stage_roofline": r.get("stage_roofline"),
+                "stage_note": (f"summed kernel durations per step over {r['probe_steps']} "
+                               "untimed single-stream probe steps (events on every launch, the "
+                               "whole batch in one call); the timed steps are uninstrumented" +
+                               (f" and overlap {S} sub-batch streams, so ms_per_step is below "
+                                "the sum" if S > 1 else "")),
+                "soak": r["soak"],
+            })
         if sweep is not None:
             line["batch_sweep"] = sweep
         if cpu:

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Summarise gpurun_out/ablib_<tag>/ (tools/ab_lib.sh): frames/s and stage times per build."""
+"""Summarise $BENCH_OUT/ablib_<tag>/ (tools/ab_lib.sh; default bench_out/): frames/s and stage
+times per build."""
 import glob
 import json
 import os
 import sys
 
-d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "ablib_" + sys.argv[1])
+d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                 os.environ.get("BENCH_OUT", "bench_out"), "ablib_" + sys.argv[1])
 out = {}
 for f in sorted(glob.glob(os.path.join(d, "*.json"))):
     line = json.loads(open(f).read().strip().splitlines()[-1])

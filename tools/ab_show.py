@@ -1,5 +1,5 @@
 import glob, json, os, sys
-for f in sorted(glob.glob('gpurun_out/ab/b_*.json')):
+for f in sorted(glob.glob(os.path.join(os.environ.get('BENCH_OUT', 'bench_out'), 'ab', 'b_*.json'))):
     try:
         d = json.loads(open(f).read().strip().splitlines()[-1])
     except Exception as e:

@@ -1,6 +1,6 @@
-"""Print the FAST strip A/B lines of gpurun_out/<tag>/ (tools/ab_fast_strip.sh)."""
+"""Print the bench lines of $BENCH_OUT/<tag>/ (tools/ab_quick.sh; default bench_out/)."""
 import glob, json, os, sys
-d = os.path.join("gpurun_out", sys.argv[1] if len(sys.argv) > 1 else "fstrip")
+d = os.path.join(os.environ.get("BENCH_OUT", "bench_out"), sys.argv[1] if len(sys.argv) > 1 else "fstrip")
 for f in sorted(glob.glob(os.path.join(d, "c*_s*.json"))):
     j = json.load(open(f))
     s = j["stage_ms_per_step"]

@@ -7,15 +7,15 @@
 #   rows       the §8(f) rows (tools/bench_rows.py)
 #   prof_c3 / prof_c4   tools/profile_round.sh TAG[_c4] (bench + rocprofv3 trace + PMC passes)
 # Steps run in order, each under its own time limit, and the first failure ends the call.
-# Extra bench arguments in $BENCH_ARGS.  Output under gpurun_out/TAG/.
+# Extra bench arguments in $BENCH_ARGS.  Output under ${BENCH_OUT:-bench_out}/TAG/.
 # (Replaces round 3/4's one-off r03_*.sh / r04_*.sh drivers, kept under profiles/r0N/scripts/.)
 set -o pipefail
 T=${1:?tag}
 shift
-O=gpurun_out/$T
+O=${BENCH_OUT:-bench_out}/$T
 mkdir -p $O
 export TMPDIR=/tmp
-B="python bench.py --cpu-budget 0 --soak-s 2 $BENCH_ARGS"
+B="python bench.py --full --cpu-budget 0 --soak-s 2 $BENCH_ARGS"
 for s in "$@"; do
   case $s in
     suite) timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $O/gpu_suite.log 2>&1 ;;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gpurun_out/order/ (tools/ab_order.sh) -> profiles/r04/experiments/describe_order.json: the
+"""$BENCH_OUT/order/ (tools/ab_order.sh) -> profiles/r04/experiments/describe_order.json: the
 describe kernel's HBM traffic and time with the oct-tree's band processing order on / off
 (ORBFE_DESC_ORDER), per config.  Traffic = 2 x FETCH_SIZE + WRITE_SIZE (the window-pattern
 calibration of profiles/r04/experiments/describe_stride.json), per 256 frames, from the
@@ -11,7 +11,7 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "gpurun_out", sys.argv[1] if len(sys.argv) > 1 else "order")
+SRC = os.path.join(ROOT, os.environ.get("BENCH_OUT", "bench_out"), sys.argv[1] if len(sys.argv) > 1 else "order")
 DST = os.path.join(ROOT, "profiles", "r04", "experiments", "describe_order.json")
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turns gpurun_out/prof_<name>/ (tools/profile_round.sh <name> [bench args]) into the committed
+"""Turns $BENCH_OUT/prof_<name>/ (tools/profile_round.sh <name> [bench args]) into the committed
 summaries under profiles/<name>/ and profiles/traffic_<config>.json (read by bench.py for
 roofline.traffic; keys "<stage>" for the scalar reading, "<stage>@x86" for --arith x86).
 
@@ -17,7 +17,7 @@ import sys
 
 R = sys.argv[1] if len(sys.argv) > 1 else "r03"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "gpurun_out", "prof_" + R.replace("/", "_"))
+SRC = os.path.join(ROOT, os.environ.get("BENCH_OUT", "bench_out"), "prof_" + R.replace("/", "_"))
 DST = os.path.join(ROOT, "profiles", R)
 os.makedirs(DST, exist_ok=True)
 
