@@ -480,6 +480,68 @@ int orbfe_search_by_projection_keyframe(orbfe_matcher* m, int check_ori,
                                         const float* kf_mp_max_dist, const int32_t* kf_mp_ids,
                                         float th, int orb_dist, int32_t* nmatches);
 
+/* ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>&, th) (ORBmatcher.cc:828-978, called by
+ * LocalMapping::SearchInNeighbors, LocalMapping.cc:489, 514) and Fuse(KeyFrame* pKF, cv::Mat Scw,
+ * const vector<MapPoint*>&, th, vpReplacePoint) (ORBmatcher.cc:980-1103, called by
+ * LoopClosing::SearchAndFuse, LoopClosing.cc:597): the search half.  Everything either overload
+ * computes up to bestIdx / bestDist reads only data that Replace / AddObservation / AddMapPoint
+ * never change, so the search runs for all points at once and the caller applies the
+ * GetMapPoint(bestIdx) branch afterwards, walking the points in order and re-evaluating the skip
+ * test (isBad(), IsInKeyFrame / spAlreadyFound) against live state — identical to the
+ * sequential loop (include/orbfe_orbslam.hpp ORBmatcher::Fuse does that walk).
+ *   kf     : the keyframe's mvKeysUn, mDescriptors, mvuRight, image bounds, grid constants and
+ *            mvScaleFactors; tcw its row-major 3x4 [R|t] world->camera pose.  For the Sim3
+ *            overload the caller passes the normalised pose (R = sRcw / scw, t = tcw / scw,
+ *            ORBmatcher.cc:989-992).
+ *   inv_level_sigma2 : pKF->mvInvLevelSigma2, kf->nlevels floats (read in SE3 mode only).
+ *   points : n_mp world positions (x 3), normals GetNormal() (x 3), mfMinDistance /
+ *            mfMaxDistance (the 0.8 / 1.2 factors of Get*DistanceInvariance are applied
+ *            inside) and descriptors (x 32).
+ *   skip   : NULL or n_mp bytes; a point with skip[i] != 0 is not searched (the loop's
+ *            `continue` at 849-853 / 1008-1009).
+ *   mode   : ORBFE_FUSE_SE3 applies the chi-square tests of 917-941 (7.8 with mvuRight >= 0,
+ *            5.99 otherwise); ORBFE_FUSE_SIM3 has none.
+ * best_idx[i] = the keypoint with the smallest descriptor distance among the candidates of
+ * KeyFrame::GetFeaturesInArea(u, v, th * mvScaleFactors[nPredictedLevel]) that pass the level
+ * (and chi-square) tests, first in the reference's order on ties, if that distance is <= TH_LOW;
+ * otherwise -1.  best_dist[i] (may be NULL) = that distance, 256 when no candidate survived.
+ * *n_found = the number of points with best_idx >= 0.  A predicted scale level outside the
+ * pyramid (where the fork indexes mvScaleFactors out of range) returns ORBFE_ERR_UNSUPPORTED;
+ * such a point gets no match and every other point's result is valid.  Synchronous. */
+#define ORBFE_FUSE_SE3  0
+#define ORBFE_FUSE_SIM3 1
+int orbfe_fuse_search(orbfe_matcher* m, const orbfe_frame_view* kf, const float* tcw,
+                      const orbfe_camera* cam, float log_scale_factor,
+                      const float* inv_level_sigma2, int n_mp, const float* mp_xyz,
+                      const float* mp_normal, const float* mp_min_dist,
+                      const float* mp_max_dist, const uint8_t* mp_desc, const uint8_t* skip,
+                      float th, int mode, int32_t* best_idx, int32_t* best_dist,
+                      int32_t* n_found);
+/* Device-resident batched form, the shape of both call sites (every neighbour / corrected
+ * keyframe against one shared point set): n_kf keyframes in pitched slabs — keyframe k's
+ * keypoints at d_keys + k*keys_pitch (orbfe_keypoint units), descriptors at d_desc +
+ * k*desc_pitch (bytes, a multiple of 16), mvuRight at d_u_right + k*kp_cap (d_u_right NULL:
+ * monocular), d_n[k] keypoints (clipped to kp_cap; pitches below kp_cap keypoints / kp_cap * 32
+ * bytes return ORBFE_ERR_ARG).  tcw is a HOST array of n_kf x 12 floats
+ * (read before the call returns); the camera, image bounds, scale tables (host, nlevels <= 16)
+ * and the n_mp points are shared by all keyframes.  d_skip: NULL or n_kf x n_mp bytes, one per
+ * (keyframe, point).  Outputs d_best_idx / d_best_dist (may be NULL): n_kf x n_mp, keyframe k's
+ * row at k*n_mp.  *d_status = 0, or ORBFE_ERR_UNSUPPORTED (a predicted level outside the
+ * pyramid, as above).  All keyframes' grids are built by one launch and all pairs searched by
+ * one launch per 40 keyframes; asynchronous on the matcher's stream. */
+int orbfe_fuse_search_batch_device(orbfe_matcher* m, int n_kf, const orbfe_keypoint* d_keys,
+                                   size_t keys_pitch, const uint8_t* d_desc, size_t desc_pitch,
+                                   const float* d_u_right, int kp_cap, const int32_t* d_n,
+                                   const float* tcw, const orbfe_camera* cam, float min_x,
+                                   float max_x, float min_y, float max_y,
+                                   const float* scale_factors, const float* inv_level_sigma2,
+                                   int nlevels, float log_scale_factor, int n_mp,
+                                   const float* d_xyz, const float* d_normal,
+                                   const float* d_min_dist, const float* d_max_dist,
+                                   const uint8_t* d_mp_desc, const uint8_t* d_skip, float th,
+                                   int mode, int32_t* d_best_idx, int32_t* d_best_dist,
+                                   int32_t* d_status);
+
 /* MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:483-548) for n_mp map points at once
  * (LocalMapping calls it for every new / fused point, LocalMapping.cc:268, 489).  The
  * descriptors of map point i's observations in non-bad keyframes, in mObservations order, are

@@ -6,6 +6,7 @@
 // on the C++ side only; nothing throws across the C ABI.
 #pragma once
 
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -149,6 +150,25 @@ struct FrameData {
     }
 };
 
+// The MapPoints handed to ORBmatcher::Fuse as flat arrays (owns nothing): GetWorldPos() and
+// GetNormal() (n x 3), mfMinDistance / mfMaxDistance, GetDescriptor() (n x 32).  skip: NULL or
+// n bytes, the skip test as it stands before the call (saves the search of those points; the
+// walk asks the live test again either way).
+struct FusePoints {
+    int n = 0;
+    const float* xyz = nullptr;
+    const float* normal = nullptr;
+    const float* min_dist = nullptr;
+    const float* max_dist = nullptr;
+    const uint8_t* desc = nullptr;
+    const uint8_t* skip = nullptr;
+};
+
+// Rows 0-2 of the 4x4 Sim3 matrix Scw = [s R | t] (row-major 3x4), LoopClosing's corrected pose.
+struct Sim3 {
+    float m[12];
+};
+
 // ORB_SLAM2::ORBmatcher hot subset (ORBmatcher.h:38-110) on a gfx950 GPU.
 class ORBmatcher {
 public:
@@ -243,9 +263,76 @@ public:
         return n;
     }
 
+    // Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, th) (ORBmatcher.cc:828-978), as
+    // LocalMapping::SearchInNeighbors calls it.  The device searches every point at once
+    // (orbfe_fuse_search); the tail of the loop (955-974) is the caller's, through callables, in
+    // the order of the list:
+    //   skipped(i)          !pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF), asked when the walk
+    //                       reaches i — a Replace earlier in the walk can change it
+    //   slot_occupied(idx)  pKF->GetMapPoint(idx) != NULL
+    //   on_occupied(i, idx) lines 958-966: the two Replace directions, unless pMPinKF is bad
+    //   on_empty(i, idx)    lines 970-971: AddObservation + AddMapPoint
+    // Returns nFused.  A predicted level outside the pyramid throws Error(ORBFE_ERR_UNSUPPORTED)
+    // before any callable runs.
+    template <class Skipped, class Occupied, class OnOccupied, class OnEmpty>
+    int Fuse(const FrameData& KF, const float* Tcw, const orbfe_camera& cam,
+             float logScaleFactor, const std::vector<float>& invLevelSigma2,
+             const FusePoints& pts, float th, Skipped skipped, Occupied slot_occupied,
+             OnOccupied on_occupied, OnEmpty on_empty) {
+        return fuse(KF, Tcw, cam, logScaleFactor, invLevelSigma2, pts, th, ORBFE_FUSE_SE3,
+                    skipped, slot_occupied, on_occupied, on_empty);
+    }
+
+    // Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, th, vpReplacePoint)
+    // (ORBmatcher.cc:980-1103), as LoopClosing::SearchAndFuse calls it.  Scw is decomposed here
+    // as lines 989-992 do: scw = (float)sqrt of the double dot product of row 0, Rcw = sRcw / scw
+    // and tcw = t / scw as products with the float (float)(1.0 / scw) (cv::Mat / double scales
+    // by the reciprocal).  skipped(i) is pMP->isBad() ||
+    // spAlreadyFound.count(pMP); on_occupied(i, idx) is lines 1090-1091 (vpReplacePoint[i] =
+    // pMPinKF unless it is bad), on_empty(i, idx) lines 1095-1096.  inv_level_sigma2 is not read.
+    template <class Skipped, class Occupied, class OnOccupied, class OnEmpty>
+    int Fuse(const FrameData& KF, const Sim3& Scw, const orbfe_camera& cam, float logScaleFactor,
+             const FusePoints& pts, float th, Skipped skipped, Occupied slot_occupied,
+             OnOccupied on_occupied, OnEmpty on_empty) {
+        const float* s = Scw.m;
+        const float scw = (float)std::sqrt((double)s[0] * s[0] + (double)s[1] * s[1] + (double)s[2] * s[2]);
+        const float inv = (float)(1.0 / (double)scw);
+        float T[12];
+        for (int i = 0; i < 12; ++i) T[i] = s[i] * inv;
+        const std::vector<float> unused(KF.scale_factors.size(), 0.f);
+        return fuse(KF, T, cam, logScaleFactor, unused, pts, th, ORBFE_FUSE_SIM3, skipped,
+                    slot_occupied, on_occupied, on_empty);
+    }
+
     orbfe_matcher* handle() { return m_; }
 
 private:
+    template <class Skipped, class Occupied, class OnOccupied, class OnEmpty>
+    int fuse(const FrameData& KF, const float* T, const orbfe_camera& cam, float logScaleFactor,
+             const std::vector<float>& invLevelSigma2, const FusePoints& pts, float th, int mode,
+             Skipped& skipped, Occupied& slot_occupied, OnOccupied& on_occupied,
+             OnEmpty& on_empty) {
+        if (invLevelSigma2.size() < KF.scale_factors.size()) throw Error("ORBmatcher::Fuse", ORBFE_ERR_ARG);
+        const orbfe_frame_view v = KF.view();
+        fuse_idx_.assign(pts.n, -1);
+        int found = 0;
+        check("orbfe_fuse_search",
+              orbfe_fuse_search(m_, &v, T, &cam, logScaleFactor, invLevelSigma2.data(), pts.n,
+                                pts.xyz, pts.normal, pts.min_dist, pts.max_dist, pts.desc,
+                                pts.skip, th, mode, fuse_idx_.data(), nullptr, &found));
+        int nFused = 0;
+        for (int i = 0; i < pts.n; ++i) {
+            if (skipped(i)) continue;
+            const int idx = fuse_idx_[i];
+            if (idx < 0) continue;
+            if (slot_occupied(idx))
+                on_occupied(i, idx);
+            else
+                on_empty(i, idx);
+            ++nFused;
+        }
+        return nFused;
+    }
     static void prepare(FrameData& F) {
         F.map_points.resize(F.keys_un.size(), -1);
         F.map_point_obs.resize(F.keys_un.size(), 0);
@@ -254,6 +341,7 @@ private:
     float mfNNratio;
     bool mbCheckOrientation;
     std::vector<float> kf_angle_, f_angle_;  // SearchByBoW: the keypoints' angles as arrays
+    std::vector<int> fuse_idx_;              // Fuse: best_idx of the device search
 };
 
 }  // namespace orbfe

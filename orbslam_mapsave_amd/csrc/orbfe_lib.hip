@@ -6,5 +6,6 @@
 #include "orbfe_match.hip"
 #include "orbfe_greedy.hip"
 #include "orbfe_match_api.hip"
+#include "orbfe_fuse.hip"
 #include "orbfe_bow.hip"
 #include "orbfe_archive.hip"

@@ -86,6 +86,7 @@ struct orbfe_matcher {
     DevBuf m_f0, m_f1, m_f2, m_f3, m_f4, m_u0, m_u1, m_i0, m_i1, m_d;  // per-map-point inputs
     DevBuf o_u, o_f0, o_f1, o_f2, o_f3, o_i;        // frustum outputs
     DevBuf scal, done_ctr;
+    DevBuf fu_cs, fu_ci;                            // Fuse: the batch's keyframe grids (orbfe_fuse.hip)
     DevBuf g_t0, g_t1, g_t2, g_dec, g_chg, g_last, g_bins, g_hist;  // greedy resolver
     Profiler prof;
     int last_rounds = 0;  // rounds the most recent greedy resolution took (diagnostics)
@@ -144,7 +145,8 @@ struct orbfe_matcher {
                           &fb_cs, &fb_ci, &fb_co, &q, &r, &nq, &nr, &out, &cnt, &off, &cand, &s1,
                           &s2, &s3, &s4, &s5, &m_f0, &m_f1, &m_f2, &m_f3, &m_f4, &m_u0, &m_u1,
                           &m_i0, &m_i1, &m_d, &o_u, &o_f0, &o_f1, &o_f2, &o_f3, &o_i, &scal,
-                          &g_t0, &g_t1, &g_t2, &g_dec, &g_chg, &g_last, &g_bins, &g_hist, &done_ctr})
+                          &g_t0, &g_t1, &g_t2, &g_dec, &g_chg, &g_last, &g_bins, &g_hist, &done_ctr,
+                          &fu_cs, &fu_ci})
             b->release();
         for (auto& kv : bf_e) {
             kv.second.buf.release();

@@ -5,7 +5,8 @@ reference interface for the hot path:
   same ctor arguments, ``__call__(image, mask)`` for ``operator()`` and the six getters;
 * :class:`ORBmatcher` mirrors the hot subset of ``ORB_SLAM2::ORBmatcher``
   (include/ORBmatcher.h:38-110): ``DescriptorDistance``, ``SearchForInitialization`` and the two
-  tracking ``SearchByProjection`` overloads, plus the brute-force match of config 3.
+  tracking ``SearchByProjection`` overloads, the search of ``Fuse`` (``FuseSearch``,
+  ``fuse_search_batch_device``), plus the brute-force match of config 3.
 
 There is no CPU fallback: importing works anywhere, but constructing an extractor or matcher
 needs the built library and a gfx950 device, and raises otherwise.
@@ -40,7 +41,8 @@ EXPORTED = [
     "orbfe_matcher_profile", "orbfe_matcher_profile_read", "orbfe_matcher_profile_read_stages", "orbfe_hamming",
     "orbfe_bf_match", "orbfe_bf_match_batch_device", "orbfe_search_for_initialization",
     "orbfe_search_by_projection_local", "orbfe_search_by_projection_last",
-    "orbfe_search_by_projection_keyframe", "orbfe_distinctive_descriptors",
+    "orbfe_search_by_projection_keyframe", "orbfe_fuse_search",
+    "orbfe_fuse_search_batch_device", "orbfe_distinctive_descriptors",
     "orbfe_distinctive_descriptors_device", "orbfe_search_local_points_device",
     "orbfe_search_by_projection_local_device",
     "orbfe_matcher_last_rounds", "orbfe_matcher_capacity_retries", "orbfe_features_in_area", "orbfe_is_in_frustum", "orbfe_vocabulary_load_text",
@@ -687,6 +689,65 @@ class ORBmatcher:
             C.c_float(log_scale), ptr(fmp), len(a[1]), *(ptr(x) for x in a[1:]), ptr(ids),
             C.c_float(th), int(ORBdist), C.byref(nm)))
         return fmp, nm.value
+
+    FUSE_SE3, FUSE_SIM3 = 0, 1  # ORBFE_FUSE_*
+
+    def FuseSearch(self, kf: Frame, tcw, cam: Camera, log_scale: float, inv_level_sigma2,
+                   mp_xyz, mp_normal, mp_min_dist, mp_max_dist, mp_desc, th: float = 3.0,
+                   mode: int = 0, skip=None):
+        """The search half of ORBmatcher::Fuse (ORBmatcher.cc:828-978; mode FUSE_SIM3: the
+        loop-closing overload, 980-1103, with the normalised [R|t]) for one keyframe
+        (orbfe_fuse_search).  Returns (best_idx, best_dist, n_found): per point the keypoint to
+        fuse into (-1: none) and the winning descriptor distance (256: no candidate).  A predicted
+        level outside the pyramid raises OrbfeError(ORBFE_ERR_UNSUPPORTED) carrying the valid
+        results of every other point as ``.results``."""
+        a = [np.ascontiguousarray(tcw, np.float32).reshape(12),
+             np.ascontiguousarray(inv_level_sigma2, np.float32),
+             np.ascontiguousarray(mp_xyz, np.float32).reshape(-1, 3),
+             np.ascontiguousarray(mp_normal, np.float32).reshape(-1, 3),
+             np.ascontiguousarray(mp_min_dist, np.float32),
+             np.ascontiguousarray(mp_max_dist, np.float32),
+             np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)]
+        n = len(a[2])
+        assert len(a[1]) >= len(kf.scale_factors)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        bi = np.full(n, -1, np.int32)
+        bd = np.full(n, 256, np.int32)
+        nf = C.c_int32(0)
+        kv = kf.view()
+        st = lib().orbfe_fuse_search(
+            self._h, C.byref(kv), ptr(a[0]), C.byref(cam), C.c_float(log_scale), ptr(a[1]), n,
+            *(ptr(x) for x in a[2:]), ptr(sk), C.c_float(th), int(mode), ptr(bi), ptr(bd),
+            C.byref(nf))
+        if st != ORBFE_OK:
+            e = OrbfeError("orbfe_fuse_search", st)
+            e.results = (bi, bd, nf.value)
+            raise e
+        return bi, bd, nf.value
+
+    def fuse_search_batch_device(self, n_kf: int, d_keys: int, keys_pitch: int, d_desc: int,
+                                 desc_pitch: int, d_u_right: int | None, kp_cap: int, d_n: int,
+                                 tcw, cam: Camera, bounds, scale_factors, inv_level_sigma2,
+                                 log_scale: float, n_mp: int, d_xyz: int, d_normal: int,
+                                 d_min: int, d_max: int, d_mdesc: int, d_skip: int | None,
+                                 th: float, mode: int, d_best_idx: int,
+                                 d_best_dist: int | None, d_status: int) -> None:
+        """Fuse's search for n_kf keyframes against one shared point set, device-resident
+        (orbfe_fuse_search_batch_device): raw device pointers, keys_pitch in keypoints,
+        desc_pitch in bytes; tcw (n_kf, 3, 4) on the host; bounds = (min_x, max_x, min_y,
+        max_y).  Asynchronous on the matcher's stream."""
+        t = np.ascontiguousarray(tcw, np.float32).reshape(-1)
+        assert len(t) == 12 * n_kf
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        isg = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        assert len(isg) >= len(sf)
+        vp = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        _check("orbfe_fuse_search_batch_device", lib().orbfe_fuse_search_batch_device(
+            self._h, n_kf, vp(d_keys), C.c_size_t(keys_pitch), vp(d_desc),
+            C.c_size_t(desc_pitch), vp(d_u_right), kp_cap, vp(d_n), ptr(t), C.byref(cam),
+            *(C.c_float(b) for b in bounds), ptr(sf), ptr(isg), len(sf), C.c_float(log_scale),
+            n_mp, vp(d_xyz), vp(d_normal), vp(d_min), vp(d_max), vp(d_mdesc), vp(d_skip),
+            C.c_float(th), int(mode), vp(d_best_idx), vp(d_best_dist), vp(d_status)))
 
     def ComputeDistinctiveDescriptors(self, obs_off: np.ndarray, obs_desc: np.ndarray):
         """MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:483-548) over a CSR of the

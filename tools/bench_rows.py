@@ -221,6 +221,57 @@ def row_reloc():
     m.close()
 
 
+def row_fuse():
+    """ORBmatcher::Fuse's search (ORBmatcher.cc:828-978): the host form for one keyframe (about
+    1,300 points) and the device batch LocalMapping::SearchInNeighbors makes of it (20 neighbour
+    keyframes against the same points).  No CPU leg: the oracle has no Fuse port."""
+    import fuse_cases as FC
+    c = FC.fuse_case(0)
+    kf, n_mp = c["kf"], len(c["xyz"])
+    m = native.ORBmatcher(0.6, True, device=0)
+    args = (kf, c["tcw"], c["cam"], c["log_scale"], c["inv_sigma2"], c["xyz"], c["normal"],
+            c["min_dist"], c["max_dist"], c["desc"], 3.0, FC.SE3)
+    nf = m.FuseSearch(*args, skip=c["skip"])[2]
+    t = timed(lambda: m.FuseSearch(*args, skip=c["skip"]), 100)
+    per_pt = 12 + 12 + 8 + 32 + 1 + 8
+    line = {"row": f"Fuse search, one keyframe (host ABI, {n_mp} points, {kf.n} kp, SE3 th 3)",
+            "unit": "calls/s", "value": round(1 / t, 2), "ms_per_call": round(t * 1e3, 4),
+            "units_per_call": 1, "bytes_per_call": n_mp * per_pt + kf.n * 64, "n_found": nf,
+            "cpu_value": None, "note": "host ABI (uploads included): scatter, grid, search, gather; "
+            "one wait on a done word; no CPU leg (the oracle has no Fuse port)"}
+    print(json.dumps(line), flush=True)
+    K, cap = 20, kf.n
+    rng = np.random.Generator(np.random.PCG64(3))
+    poses = np.stack([c["tcw"]] + [FC.S.pose(rng, 0.002, 0.01) for _ in range(K - 1)])
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(DEV)  # noqa: E731
+    d_keys, d_desc, d_ur = up(np.tile(kf.keys, K)), up(np.tile(kf.desc, (K, 1))), up(np.tile(kf.u_right, K))
+    d_n = up(np.full(K, kf.n, np.int32))
+    d_pts = [up(c[k]) for k in ("xyz", "normal", "min_dist", "max_dist", "desc")]
+    d_skip = up(np.tile(c["skip"], K))
+    d_bi = torch.empty(K * n_mp, dtype=torch.int32, device=DEV)
+    d_bd = torch.empty(K * n_mp, dtype=torch.int32, device=DEV)
+    d_st = torch.empty(1, dtype=torch.int32, device=DEV)
+    m.set_stream(torch.cuda.current_stream(DEV).cuda_stream)
+
+    def go():
+        m.fuse_search_batch_device(K, d_keys.data_ptr(), cap, d_desc.data_ptr(), cap * 32,
+                                   d_ur.data_ptr(), cap, d_n.data_ptr(), poses, c["cam"],
+                                   (0.0, 640.0, 0.0, 480.0), kf.scale_factors, c["inv_sigma2"],
+                                   c["log_scale"], n_mp, *(x.data_ptr() for x in d_pts),
+                                   d_skip.data_ptr(), 3.0, FC.SE3, d_bi.data_ptr(), d_bd.data_ptr(),
+                                   d_st.data_ptr())
+    t = timed(go, 100)
+    assert int(d_st[0]) == 0 and int((d_bi.view(K, n_mp)[0] >= 0).sum()) == nf
+    line = {"row": f"Fuse search, device batch ({K} keyframes x {n_mp} points, {kf.n} kp each, SE3 th 3)",
+            "unit": "keyframes/s", "value": round(K / t, 2), "ms_per_call": round(t * 1e3, 4),
+            "units_per_call": K, "bytes_per_call": K * (n_mp * (per_pt + 8) + kf.n * 64),
+            "matches": int((d_bi >= 0).sum()), "cpu_value": None,
+            "note": "device form, everything resident: one memset, one grid launch (a workgroup per "
+            "keyframe), one search launch (a wave per pair); no CPU leg"}
+    print(json.dumps(line), flush=True)
+    m.close()
+
+
 def row_track():
     """The per-frame tracking-loop matchers through the host ABI (uploads included):
     TrackWithMotionModel's SearchByProjection(CurrentFrame, LastFrame, th, mono)
@@ -419,7 +470,7 @@ def row_bow(tmpdir):
 if __name__ == "__main__":
     import tempfile
     with tempfile.TemporaryDirectory() as td:
-        rows = {"single": row_single, "color": row_color, "stereo": row_stereo, "reloc": row_reloc, "track": row_track,
+        rows = {"single": row_single, "color": row_color, "stereo": row_stereo, "reloc": row_reloc, "fuse": row_fuse, "track": row_track,
                 "distinctive": row_distinctive, "bow": lambda: row_bow(td)}
         for name in (sys.argv[1:] or list(rows)):
             rows[name]()
