@@ -326,3 +326,114 @@ def test_gpu_walk_equals_sequential_loop(mt, seed, th, mode):
     n_dec = FC.walk(dec, bi, mode)
     assert n_seq == n_dec > 30
     assert seq.result() == dec.result() and seq.calls == dec.calls
+
+
+# ---- the batch form's seams: 40 keyframes per launch, d_best_dist NULL, the in-place grid fill ----
+
+def run_batch(mt, c, kfs, poses, skips, th, mode, with_dist=True, stereo=True):
+    """orbfe_fuse_search_batch_device over the keyframes `kfs` (slabs with non-tight pitches) ->
+    (best_idx, best_dist or None, status), one row per keyframe."""
+    import torch
+    dev = torch.device("cuda", 0)
+    n_kf, n_mp = len(kfs), len(c["xyz"])
+    kp_cap = max(f.n for f in kfs) + 3
+    keys_pitch, desc_pitch = kp_cap + 2, (kp_cap + 1) * 32 + 16
+    keys = np.zeros((n_kf, keys_pitch), S.KEYPOINT_DTYPE)
+    desc = np.full((n_kf, desc_pitch), 0xAB, np.uint8)
+    ur = np.full((n_kf, kp_cap), 7.0, F32)
+    for k, f in enumerate(kfs):
+        keys[k, :f.n] = f.keys
+        desc[k, :f.n * 32] = f.desc.reshape(-1)
+        ur[k, :f.n] = f.u_right
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)  # noqa: E731
+    d_keys, d_desc, d_ur = up(keys), up(desc), up(ur)
+    d_n = up(np.array([f.n for f in kfs], np.int32))
+    d_xyz, d_nrm = up(c["xyz"]), up(c["normal"])
+    d_min, d_max, d_md = up(c["min_dist"]), up(c["max_dist"]), up(c["desc"])
+    d_skip = up(skips)
+    d_bi = torch.full((n_kf * n_mp,), -7, dtype=torch.int32, device=dev)
+    d_bd = torch.full((n_kf * n_mp,), -7, dtype=torch.int32, device=dev)
+    d_st = torch.full((1,), -7, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    mt.fuse_search_batch_device(
+        n_kf, d_keys.data_ptr(), keys_pitch, d_desc.data_ptr(), desc_pitch,
+        d_ur.data_ptr() if stereo else None, kp_cap, d_n.data_ptr(), np.stack(poses), c["cam"],
+        (0.0, float(S.W), 0.0, float(S.H)), FC.SCALE, c["inv_sigma2"], c["log_scale"], n_mp,
+        d_xyz.data_ptr(), d_nrm.data_ptr(), d_min.data_ptr(), d_max.data_ptr(), d_md.data_ptr(),
+        d_skip.data_ptr(), th, mode, d_bi.data_ptr(), d_bd.data_ptr() if with_dist else None,
+        d_st.data_ptr())
+    torch.cuda.synchronize()
+    bd = d_bd.cpu().numpy().reshape(n_kf, n_mp)
+    assert with_dist or (bd == -7).all()
+    return d_bi.cpu().numpy().reshape(n_kf, n_mp), bd if with_dist else None, int(d_st.cpu()[0])
+
+
+@functools.lru_cache(maxsize=None)
+def seam_case():
+    """200 points of the scenario, the ones that match one of its keyframe's first 150 keypoints
+    first, and that keyframe cut to 300 keypoints: every prefix of 150-300 of them is a cheap
+    keyframe with matches."""
+    c = case(0)
+    (ebi, _, _, _), _ = expected(0, 3.0, SE3)
+    near = np.flatnonzero((ebi >= 0) & (ebi < 150))
+    rest = np.setdiff1d(np.arange(len(ebi)), near)
+    idx = np.sort(np.concatenate([near, rest])[:200])
+    assert len(near) >= 20
+    return FC.subset(c, idx)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_kf,mode,th", [(40, SE3, 3.0), (41, SIM3, 4.0), (81, SE3, 3.0)])
+def test_gpu_fuse_search_batch_launch_seams(mt, n_kf, mode, th):
+    """The search kernel takes 40 keyframes' poses per launch as arguments and indexes them by
+    blockIdx.y, everything else by kf0 + blockIdx.y: keyframes 0, 39, 40, 41 and 80 -- distinct
+    poses, keypoint counts and skip rows, each with matches -- equal the host form's result for
+    that keyframe alone, keyframes 0 and 40 the restatement's too.  d_best_dist = NULL leaves
+    best_idx unchanged."""
+    c = seam_case()
+    n_mp = len(c["xyz"])
+    full = c["kf"]
+    rng = np.random.Generator(np.random.PCG64(40 + n_kf))
+    counts = [150 + (37 * k) % 151 for k in range(n_kf)]
+    kfs = [Frame(full.keys[:n], full.desc[:n], S.W, S.H, FC.SCALE, full.u_right[:n]) for n in counts]
+    poses = [c["tcw"]] + [S.pose(rng, 0.001 + 0.0002 * (k % 5), 0.004) for k in range(1, n_kf)]
+    skips = (rng.uniform(size=(n_kf, n_mp)) < 0.15).astype(np.uint8)
+    bi, bd, st = run_batch(mt, c, kfs, poses, skips, th, mode)
+    assert st == 0
+    seam = [k for k in (0, 39, 40, 41, 80) if k < n_kf]
+    for a in seam:
+        for b in seam:
+            assert a == b or not np.array_equal(poses[a], poses[b])
+    for k in seam:
+        hbi, hbd, hnf = gpu_search(mt, dict(c, kf=kfs[k], tcw=poses[k], skip=skips[k]), th, mode)
+        assert hnf > 0, k
+        assert np.array_equal(bi[k], hbi) and np.array_equal(bd[k], hbd), k
+    for k in (0, 40):
+        if k < n_kf:
+            e = FC.restated(dict(c, kf=kfs[k], tcw=poses[k], skip=skips[k]), th, mode)
+            assert e[2] > 0 and np.array_equal(bi[k], e[0]) and np.array_equal(bd[k], e[1]), k
+    bi2, _, st2 = run_batch(mt, c, kfs, poses, skips, th, mode, with_dist=False)
+    assert st2 == 0 and np.array_equal(bi2, bi)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("th,mode", [(3.0, SE3), (4.0, SIM3)])
+def test_gpu_fuse_search_batch_big_keyframe_second(mt, th, mode):
+    """A batch whose keyframe 1 has more than 4,096 keypoints: its grid is filled in place in
+    the batch's item slab (at keyframe 1's offset), between two small keyframes."""
+    c = FC.subset(big_case(), slice(0, 200))
+    big = c["kf"]
+    small = case(0)["kf"]
+    kfs = [Frame(small.keys[:n], small.desc[:n], S.W, S.H, FC.SCALE, small.u_right[:n])
+           for n in (300, 211)]
+    kfs.insert(1, big)
+    assert kfs[1].n > 4096
+    rng = np.random.Generator(np.random.PCG64(11))
+    poses = [S.pose(rng, 0.001, 0.004), c["tcw"], S.pose(rng, 0.002, 0.004)]
+    skips = (rng.uniform(size=(3, len(c["xyz"]))) < 0.1).astype(np.uint8)
+    bi, bd, st = run_batch(mt, c, kfs, poses, skips, th, mode)
+    assert st == 0
+    for k in range(3):
+        hbi, hbd, hnf = gpu_search(mt, dict(c, kf=kfs[k], tcw=poses[k], skip=skips[k]), th, mode)
+        assert hnf > (30 if k == 1 else 0), k
+        assert np.array_equal(bi[k], hbi) and np.array_equal(bd[k], hbd), k
