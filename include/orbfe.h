@@ -644,6 +644,70 @@ int orbfe_search_by_bow_batch_device(orbfe_matcher* m, float nnratio, int check_
                                      const int32_t* d_f_node_off, const int32_t* d_f_feat,
                                      int32_t* d_matches, int32_t* d_nmatches, int32_t* d_status);
 
+/* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo)
+ * (ORBmatcher.cc:660-826, CheckDistEpipolarLine 140-157) with ORBmatcher(nnratio, check_ori):
+ * LocalMapping::CreateNewMapPoints constructs ORBmatcher(0.6, false) and calls it once per
+ * covisible neighbour (LocalMapping.cc:207-268).  nnratio is not read by this matcher.
+ *   kf1, kf2      : mvKeysUn (x, y, octave, angle), mDescriptors and mvuRight (NULL: monocular)
+ *                   of the two keyframes; kf2's scale_factors / nlevels are pKF2->mvScaleFactors
+ *                   (the image bounds and grid constants are not read).
+ *   has_mp1/2     : per feature, GetMapPoint(i) != NULL (705, 728).
+ *   nn*, node_ids*, node_off*, feat* : mFeatVec of each keyframe as CSR (as orbfe_bow_transform
+ *                   writes it).  Each must list a feature index under at most one node, as DBoW2
+ *                   builds it; one that repeats an index returns ORBFE_ERR_ARG.
+ *   f12           : the caller's F12 (LocalMapping::ComputeF12), 3 x 3 row-major.
+ *   epipole       : ex, ey of 667-673 (include/orbfe_orbslam.hpp evaluates those lines).
+ *   level_sigma2  : pKF2->mvLevelSigma2, kf2->nlevels floats.
+ *   only_stereo   : bOnlyStereo.
+ *   block_matched2: vbMatched2 (680) is read at 728 but never written in the reference, so the
+ *                   literal source blocks nothing: 0 reproduces it (a keyframe-2 feature may be
+ *                   matched by several keyframe-1 features).  1 builds the evident intent,
+ *                   vbMatched2[bestIdx2] = true after 764, never released, not even when the
+ *                   orientation filter later drops the match.
+ * The winner of a keyframe-1 feature (no MapPoint; stereo under only_stereo) is, among the
+ * keyframe-2 features of the same node that are unblocked, hold no MapPoint, are stereo under
+ * only_stereo, lie at distance <= TH_LOW, are outside the epipole radius when both features are
+ * monocular (746-752, float, strict <) and pass dsqr < 3.84 * mvLevelSigma2[octave] (a double
+ * comparison; den == 0 fails), the one of smallest distance, last in node order on
+ * ties.  The orientation filter (794-813) applies with check_ori.  matches12[i] (kf1->n entries)
+ * = the keyframe-2 feature of keyframe-1 feature i or -1 (vMatches12; the pair list is its
+ * compaction in ascending i), *nmatches as returned.  A common node holding more than 256
+ * keyframe-2 features returns ORBFE_ERR_UNSUPPORTED, a keyframe-2 octave outside [0, nlevels)
+ * ORBFE_ERR_ARG; that node / candidate is skipped and every other result is valid.  Angles
+ * outside [0, 360) whose difference lands beyond bin 30 (where the reference writes outside
+ * rotHist) return ORBFE_ERR_UNSUPPORTED and that match is dropped.  Synchronous. */
+int orbfe_search_for_triangulation(orbfe_matcher* m, int check_ori, int block_matched2,
+                                   int only_stereo, const orbfe_frame_view* kf1,
+                                   const uint8_t* has_mp1, int nn1, const int32_t* node_ids1,
+                                   const int32_t* node_off1, const int32_t* feat1,
+                                   const orbfe_frame_view* kf2, const uint8_t* has_mp2, int nn2,
+                                   const int32_t* node_ids2, const int32_t* node_off2,
+                                   const int32_t* feat2, const float* f12, const float* epipole,
+                                   const float* level_sigma2, int32_t* matches12,
+                                   int32_t* nmatches);
+/* Batched device form for CreateNewMapPoints' neighbour loop (LocalMapping.cc:215-268): n_pairs
+ * (keyframe 1, keyframe 2) problems in one search launch (n_pairs <= 65535).  Keyframes are slots
+ * of capacity cap in exactly the layout orbfe_bow_transform_batch_device reads and writes: slot
+ * s holds descriptors at d_desc + s*cap*32, its FeatureVector's node ids and feature indices at
+ * s*cap, node offsets at s*(cap + 1), node count d_nn[s]; and in addition keypoints at d_keys +
+ * s*cap, mvuRight at d_u_right + s*cap (d_u_right NULL: monocular), map-point flags at d_has_mp
+ * + s*cap and the feature count d_n[s].  Pair p matches slot d_pair_1[p] (pKF1) against slot
+ * d_pair_2[p] (pKF2) with F12 = d_f12 + 9 p (row-major) and epipole d_epipole + 2 p.
+ * scale_factors / level_sigma2 are HOST arrays of nlevels <= 16 floats shared by all keyframes
+ * (read before the call returns).  d_matches12[p*cap + i] = the keyframe-2 feature of keyframe-1
+ * feature i or -1 (all cap entries written), d_nmatches[p] = the returned count.  *d_status = 0,
+ * or ORBFE_ERR_UNSUPPORTED (a common node over 256 keyframe-2 features) / ORBFE_ERR_ARG (an
+ * offset or index outside its slot or count, a keyframe-2 octave outside [0, nlevels); that node
+ * / feature is skipped).  Asynchronous on the matcher's stream. */
+int orbfe_search_for_triangulation_batch_device(
+    orbfe_matcher* m, int check_ori, int block_matched2, int only_stereo, int cap,
+    const orbfe_keypoint* d_keys, const uint8_t* d_desc, const float* d_u_right,
+    const uint8_t* d_has_mp, const int32_t* d_n, const int32_t* d_nn, const int32_t* d_node_ids,
+    const int32_t* d_node_off, const int32_t* d_feat, int n_pairs, const int32_t* d_pair_1,
+    const int32_t* d_pair_2, const float* d_f12, const float* d_epipole,
+    const float* scale_factors, const float* level_sigma2, int nlevels, int32_t* d_matches12,
+    int32_t* d_nmatches, int32_t* d_status);
+
 /* ---- map-archive records of the extractor outputs (device side) ---------------------------
  * The bodies the reference's Boost map archive stores for the extractor's outputs, written
  * from / read into HBM (MapPoint.h:196-247; KeyFrame::serialize KeyFrame.cc:133-134 / 354-355

@@ -164,6 +164,20 @@ struct FusePoints {
     const uint8_t* skip = nullptr;
 };
 
+// The KeyFrame members ORBmatcher::SearchForTriangulation reads (owns nothing): the frame data,
+// mFeatVec, GetMapPoint(i) != NULL per feature, GetRotation() (3 x 3 row-major), GetTranslation(),
+// GetCameraCenter(), the intrinsics and mvLevelSigma2 (frame->scale_factors.size() floats).
+struct KeyFrameData {
+    const FrameData* frame = nullptr;
+    FeatureVectorView feat_vec{nullptr, nullptr, nullptr, 0};
+    const uint8_t* has_map_point = nullptr;
+    const float* Rcw = nullptr;
+    const float* tcw = nullptr;
+    const float* Ow = nullptr;
+    float fx = 0, fy = 0, cx = 0, cy = 0;
+    const float* level_sigma2 = nullptr;
+};
+
 // Rows 0-2 of the 4x4 Sim3 matrix Scw = [s R | t] (row-major 3x4), LoopClosing's corrected pose.
 struct Sim3 {
     float m[12];
@@ -304,6 +318,43 @@ public:
                     slot_occupied, on_occupied, on_empty);
     }
 
+    // SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vMatchedPairs,
+    // bOnlyStereo) (ORBmatcher.cc:660-826), as LocalMapping::CreateNewMapPoints calls it with
+    // F12 = ComputeF12(pKF1, pKF2), 3 x 3 row-major.  The epipole is evaluated here as lines
+    // 667-673 write it: C2 = R2w * Cw + t2w is one cv::gemm (products and the added t2w
+    // accumulated in double, rounded to float once per element), invz, ex and ey are float
+    // expressions.  vMatchedPairs receives vMatches12 compacted in ascending keyframe-1 index;
+    // returns nmatches.  blockMatched2 = false is the reference as written (vbMatched2 is read
+    // but never set, so a keyframe-2 feature can appear in several pairs); true blocks a
+    // matched keyframe-2 feature for the rest of its node, the evident intent.
+    int SearchForTriangulation(const KeyFrameData& KF1, const KeyFrameData& KF2, const float* F12,
+                               std::vector<std::pair<size_t, size_t>>& vMatchedPairs,
+                               bool bOnlyStereo, bool blockMatched2 = false) {
+        if (!KF1.frame || !KF2.frame || !KF1.Ow || !KF2.Rcw || !KF2.tcw)
+            throw Error("ORBmatcher::SearchForTriangulation", ORBFE_ERR_ARG);
+        float C2[3];
+        for (int r = 0; r < 3; ++r)
+            C2[r] = (float)((double)KF2.Rcw[3 * r] * KF1.Ow[0] + (double)KF2.Rcw[3 * r + 1] * KF1.Ow[1] +
+                            (double)KF2.Rcw[3 * r + 2] * KF1.Ow[2] + (double)KF2.tcw[r]);
+        const float invz = 1.0f / C2[2];
+        const float epipole[2] = {KF2.fx * C2[0] * invz + KF2.cx, KF2.fy * C2[1] * invz + KF2.cy};
+        const orbfe_frame_view v1 = KF1.frame->view(), v2 = KF2.frame->view();
+        tri_m12_.assign(v1.n, -1);
+        int n = 0;
+        check("orbfe_search_for_triangulation",
+              orbfe_search_for_triangulation(
+                  m_, mbCheckOrientation, blockMatched2, bOnlyStereo, &v1, KF1.has_map_point,
+                  KF1.feat_vec.nn, KF1.feat_vec.node_ids, KF1.feat_vec.node_off, KF1.feat_vec.feat,
+                  &v2, KF2.has_map_point, KF2.feat_vec.nn, KF2.feat_vec.node_ids,
+                  KF2.feat_vec.node_off, KF2.feat_vec.feat, F12, epipole, KF2.level_sigma2,
+                  tri_m12_.data(), &n));
+        vMatchedPairs.clear();
+        vMatchedPairs.reserve(n);
+        for (size_t i = 0; i < tri_m12_.size(); ++i)
+            if (tri_m12_[i] >= 0) vMatchedPairs.push_back(std::make_pair(i, (size_t)tri_m12_[i]));
+        return n;
+    }
+
     orbfe_matcher* handle() { return m_; }
 
 private:
@@ -342,6 +393,7 @@ private:
     bool mbCheckOrientation;
     std::vector<float> kf_angle_, f_angle_;  // SearchByBoW: the keypoints' angles as arrays
     std::vector<int> fuse_idx_;              // Fuse: best_idx of the device search
+    std::vector<int> tri_m12_;               // SearchForTriangulation: vMatches12
 };
 
 }  // namespace orbfe

@@ -267,15 +267,15 @@ __global__ __launch_bounds__(256) void bow_init_kernel(BowMatchArgs a) {
     }
 }
 
-// The orientation filter (259-281) of pair p over its matched frame features, by one workgroup.
-__device__ void bow_ori_filter(const BowMatchArgs& a, int p) {
+// The orientation filter of one pair over its n match slots, by one workgroup: ComputeThreeMaxima
+// over the pair's histogram, the matches outside the three bins cleared and taken off *nm
+// (SearchByBoW 259-281, SearchForTriangulation 794-813).
+__device__ void ori_filter(int* matches, const int* bins, const int* hist, int* nm, int n) {
     __shared__ int top[3];
-    if (threadIdx.x == 0) three_maxima(a.hist + p * 32, top[0], top[1], top[2]);
+    if (threadIdx.x == 0) three_maxima(hist, top[0], top[1], top[2]);
     __syncthreads();
-    int* matches = a.matches + (size_t)p * a.f_cap;
-    const int* bins = a.bins + (size_t)p * a.f_cap;
     int removed = 0;
-    for (int j = threadIdx.x; j < a.f_cap; j += blockDim.x) {
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
         if (matches[j] < 0) continue;
         const int bin = bins[j];
         if (bin != top[0] && bin != top[1] && bin != top[2]) {
@@ -283,7 +283,11 @@ __device__ void bow_ori_filter(const BowMatchArgs& a, int p) {
             ++removed;
         }
     }
-    if (removed) atomicSub(&a.nm[p], removed);
+    if (removed) atomicSub(nm, removed);
+}
+__device__ void bow_ori_filter(const BowMatchArgs& a, int p) {
+    ori_filter(a.matches + (size_t)p * a.f_cap, a.bins + (size_t)p * a.f_cap, a.hist + p * 32,
+               &a.nm[p], a.f_cap);
 }
 
 // A frame feature belongs to exactly one vocabulary node, so the blocking

@@ -8,4 +8,5 @@
 #include "orbfe_match_api.hip"
 #include "orbfe_fuse.hip"
 #include "orbfe_bow.hip"
+#include "orbfe_triangulate.hip"
 #include "orbfe_archive.hip"

@@ -6,7 +6,8 @@ reference interface for the hot path:
 * :class:`ORBmatcher` mirrors the hot subset of ``ORB_SLAM2::ORBmatcher``
   (include/ORBmatcher.h:38-110): ``DescriptorDistance``, ``SearchForInitialization`` and the two
   tracking ``SearchByProjection`` overloads, the search of ``Fuse`` (``FuseSearch``,
-  ``fuse_search_batch_device``), plus the brute-force match of config 3.
+  ``fuse_search_batch_device``), ``SearchForTriangulation`` (and
+  ``search_for_triangulation_batch_device``), plus the brute-force match of config 3.
 
 There is no CPU fallback: importing works anywhere, but constructing an extractor or matcher
 needs the built library and a gfx950 device, and raises otherwise.
@@ -48,7 +49,9 @@ EXPORTED = [
     "orbfe_matcher_last_rounds", "orbfe_matcher_capacity_retries", "orbfe_features_in_area", "orbfe_is_in_frustum", "orbfe_vocabulary_load_text",
     "orbfe_vocabulary_create", "orbfe_vocabulary_destroy", "orbfe_vocabulary_info",
     "orbfe_vocabulary_set_stream", "orbfe_bow_transform", "orbfe_bow_transform_batch_device",
-    "orbfe_search_by_bow", "orbfe_search_by_bow_batch_device", "orbfe_archive_mat_bytes",
+    "orbfe_search_by_bow", "orbfe_search_by_bow_batch_device",
+    "orbfe_search_for_triangulation", "orbfe_search_for_triangulation_batch_device",
+    "orbfe_archive_mat_bytes",
     "orbfe_archive_write_keypoints_device", "orbfe_archive_read_keypoints_device",
     "orbfe_archive_write_descriptors_device", "orbfe_archive_read_descriptors_device",
 ]
@@ -876,6 +879,69 @@ class ORBmatcher:
             v(d_kf_nn), v(d_kf_node_ids), v(d_kf_node_off), v(d_kf_feat), f_cap, v(d_f_desc),
             v(d_f_angle), v(d_f_nn), v(d_f_node_ids), v(d_f_node_off), v(d_f_feat),
             v(d_matches), v(d_nmatches), v(d_status)))
+
+    def SearchForTriangulation(self, KF1: Frame, has_mp1, fv1, KF2: Frame, has_mp2, fv2, F12,
+                               epipole, level_sigma2, bOnlyStereo: bool = False,
+                               block_matched2: bool = False):
+        """SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo)
+        (ORBmatcher.cc:660-826) through orbfe_search_for_triangulation.  has_mp*:
+        GetMapPoint(i) != NULL per feature; fv*: (node_ids, node_off, feat) FeatureVectors; F12
+        3 x 3; epipole (ex, ey) of lines 667-673; level_sigma2 = pKF2->mvLevelSigma2.
+        block_matched2=False is the reference as written (vbMatched2 is never set, DESIGN.md
+        H13), True its evident intent.  Returns (vMatchedPairs (n, 2) int32, nmatches);
+        ``self.vMatches12`` keeps the per-feature array.  A node over 256 keyframe-2 features or
+        an octave outside the pyramid raises OrbfeError carrying the valid results of everything
+        else as ``.results``."""
+        mp1 = np.ascontiguousarray(has_mp1, np.uint8)
+        mp2 = np.ascontiguousarray(has_mp2, np.uint8)
+        n1, o1, f1 = (np.ascontiguousarray(x, np.int32) for x in fv1)
+        n2, o2, f2 = (np.ascontiguousarray(x, np.int32) for x in fv2)
+        F = np.ascontiguousarray(F12, np.float32).reshape(9)
+        ep = np.ascontiguousarray(epipole, np.float32).reshape(2)
+        sg = np.ascontiguousarray(level_sigma2, np.float32)
+        assert len(mp1) == KF1.n and len(mp2) == KF2.n and len(sg) >= len(KF2.scale_factors)
+        m12 = np.full(KF1.n, -1, np.int32)
+        nm = C.c_int32(0)
+        v1, v2 = KF1.view(), KF2.view()
+        st = lib().orbfe_search_for_triangulation(
+            self._h, int(self.mbCheckOrientation), int(bool(block_matched2)),
+            int(bool(bOnlyStereo)), C.byref(v1), ptr(mp1), len(n1), ptr(n1), ptr(o1), ptr(f1),
+            C.byref(v2), ptr(mp2), len(n2), ptr(n2), ptr(o2), ptr(f2), ptr(F), ptr(ep), ptr(sg),
+            ptr(m12), C.byref(nm))
+        self.vMatches12 = m12
+        i1 = np.flatnonzero(m12 >= 0)
+        pairs = np.stack([i1, m12[i1]], axis=1).astype(np.int32).reshape(-1, 2)
+        if st != ORBFE_OK:
+            e = OrbfeError("orbfe_search_for_triangulation", st)
+            e.results = (pairs, nm.value)
+            raise e
+        return pairs, nm.value
+
+    def search_for_triangulation_batch_device(self, cap: int, d_keys: int, d_desc: int,
+                                              d_u_right: int | None, d_has_mp: int, d_n: int,
+                                              d_nn: int, d_node_ids: int, d_node_off: int,
+                                              d_feat: int, n_pairs: int, d_pair_1: int,
+                                              d_pair_2: int, d_f12: int, d_epipole: int,
+                                              scale_factors, level_sigma2, d_matches12: int,
+                                              d_nmatches: int, d_status: int,
+                                              bOnlyStereo: bool = False,
+                                              block_matched2: bool = False) -> None:
+        """SearchForTriangulation over n_pairs (keyframe-1 slot, keyframe-2 slot) pairs
+        (CreateNewMapPoints' neighbour loop, LocalMapping.cc:215-268): device pointers in the
+        layout of Vocabulary.transform_batch_device plus keypoint, mvuRight and map-point-flag
+        slabs (orbfe_search_for_triangulation_batch_device); scale_factors / level_sigma2 on the
+        host.  Asynchronous on the matcher's stream."""
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        sg = np.ascontiguousarray(level_sigma2, np.float32)
+        assert len(sg) >= len(sf)
+        vp = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        _check("orbfe_search_for_triangulation_batch_device",
+               lib().orbfe_search_for_triangulation_batch_device(
+                   self._h, int(self.mbCheckOrientation), int(bool(block_matched2)),
+                   int(bool(bOnlyStereo)), cap, vp(d_keys), vp(d_desc), vp(d_u_right),
+                   vp(d_has_mp), vp(d_n), vp(d_nn), vp(d_node_ids), vp(d_node_off), vp(d_feat),
+                   n_pairs, vp(d_pair_1), vp(d_pair_2), vp(d_f12), vp(d_epipole), ptr(sf),
+                   ptr(sg), len(sf), vp(d_matches12), vp(d_nmatches), vp(d_status)))
 
     def is_in_frustum(self, xyz, normal, min_dist, max_dist, tcw, cam: Camera, bounds,
                       log_scale: float, cos_limit: float = 0.5):

@@ -272,6 +272,123 @@ def row_fuse():
     m.close()
 
 
+def row_triangulation():
+    """ORBmatcher::SearchForTriangulation (ORBmatcher.cc:660-826): the host form for one pair and
+    the device batch LocalMapping::CreateNewMapPoints makes of it (one keyframe against 20
+    neighbours, about 1,000 keypoints each, FeatureVectors at levelsup 4 of the synthetic
+    vocabulary, written on the device by the batched transform), issued back to back; beside it
+    SearchByBoW's batch at the same slot shape (the closest kernel in structure).  No CPU leg: the
+    oracle has no port of this matcher."""
+    import ctypes as C
+    import scenarios as S
+    kf = S.extract_frame(0, 1000, ini=20)
+    shifts = [(1 + s % 5, -(s % 3)) for s in range(20)]
+    cache = {}
+    nbr = [cache.setdefault(sh, S.extract_frame(0, 1000, shift=sh, ini=20)) for sh in shifts]
+    parent, word, desc, weight = vocab_arrays(10, 6, 0, anchors=kf.desc[::97])
+    st = C.c_int(0)
+    h = native.lib().orbfe_vocabulary_create(10, 6, 0, 0, len(parent), native.ptr(parent),
+                                             native.ptr(word), native.ptr(desc), native.ptr(weight), 0,
+                                             C.byref(st))
+    assert h, st.value
+    gv = native.Vocabulary.__new__(native.Vocabulary)
+    gv._h = C.c_void_p(h)
+    stream = torch.cuda.current_stream(DEV).cuda_stream
+    gv.set_stream(stream)
+    frames = [kf] + nbr
+    B, cap, P = len(frames), 1100, len(nbr)
+    dd = np.zeros((B, cap, 32), np.uint8)
+    kk = np.zeros((B, cap), native.KEYPOINT_DTYPE)
+    ang = np.zeros((B, cap), np.float32)
+    for i, x in enumerate(frames):
+        dd[i, :x.n], kk[i, :x.n], ang[i, :x.n] = x.desc, x.keys, x.keys["angle"]
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(DEV)  # noqa: E731
+    D, Kp, A = up(dd), up(kk), up(ang)
+    N = up(np.array([x.n for x in frames], np.int32))
+    wid = torch.empty((B, cap), dtype=torch.int32, device=DEV)
+    val = torch.empty((B, cap), dtype=torch.float64, device=DEV)
+    nid = torch.empty((B, cap), dtype=torch.int32, device=DEV)
+    off = torch.empty((B, cap + 1), dtype=torch.int32, device=DEV)
+    feat = torch.empty((B, cap), dtype=torch.int32, device=DEV)
+    nw = torch.empty(B, dtype=torch.int32, device=DEV)
+    nn = torch.empty(B, dtype=torch.int32, device=DEV)
+    gv.transform_batch_device(B, D.data_ptr(), N.data_ptr(), cap, 4, wid.data_ptr(), val.data_ptr(),
+                              nw.data_ptr(), nid.data_ptr(), off.data_ptr(), feat.data_ptr(),
+                              nn.data_ptr())
+    torch.cuda.synchronize()
+    scale = kf.scale_factors
+    sigma2 = (scale * scale).astype(np.float32)
+    # neighbour s is the keyframe's image rolled by (dy, dx): y2 = y1 + dy, the epipolar lines of a
+    # sideways motion (a = 0, b = 1, c = -y1 - dy); the epipole far outside the image
+    f12 = np.stack([np.array([[0, 0, 0], [0, 0, -1], [0, 1, -dy]], np.float32) for dy, _ in shifts])
+    epi = np.tile(np.array([-5000, -5000], np.float32), (P, 1))
+    fvs = []
+    for i in (0, 1):
+        k = int(nn[i])
+        o = off[i, :k + 1].cpu().numpy()
+        fvs.append((nid[i, :k].cpu().numpy(), o, feat[i, :o[-1]].cpu().numpy()))
+    m = native.ORBmatcher(0.6, False, device=0)   # LocalMapping.cc:212
+    none = [np.zeros(x.n, np.uint8) for x in frames[:2]]
+    hargs = (frames[0], none[0], fvs[0], frames[1], none[1], fvs[1], f12[0], epi[0], sigma2)
+    n_host = m.SearchForTriangulation(*hargs)[1]
+    t = timed(lambda: m.SearchForTriangulation(*hargs), 100)
+    per_pair = (frames[0].n + frames[1].n) * (32 + 28 + 1 + 4)
+    line = {"row": f"SearchForTriangulation, one pair (host ABI, {frames[0].n} x {frames[1].n} kp, "
+            f"{len(fvs[0][0])} nodes)", "unit": "calls/s", "value": round(1 / t, 2),
+            "ms_per_call": round(t * 1e3, 4), "units_per_call": 1, "bytes_per_call": per_pair,
+            "nmatches": n_host, "cpu_value": None,
+            "note": "host ABI (uploads included): scatter, init, search, gather; one wait on a done "
+            "word; no CPU leg (the oracle has no port of this matcher)"}
+    print(json.dumps(line), flush=True)
+    m.set_stream(stream)
+    p1 = torch.zeros(P, dtype=torch.int32, device=DEV)
+    p2 = torch.arange(1, P + 1, dtype=torch.int32, device=DEV)
+    dF, dE = up(f12), up(epi)
+    mp = torch.zeros(B * cap, dtype=torch.uint8, device=DEV)
+    out = torch.empty((P, cap), dtype=torch.int32, device=DEV)
+    nmv = torch.empty(P, dtype=torch.int32, device=DEV)
+    stv = torch.empty(1, dtype=torch.int32, device=DEV)
+
+    def go():
+        m.search_for_triangulation_batch_device(
+            cap, Kp.data_ptr(), D.data_ptr(), None, mp.data_ptr(), N.data_ptr(), nn.data_ptr(),
+            nid.data_ptr(), off.data_ptr(), feat.data_ptr(), P, p1.data_ptr(), p2.data_ptr(),
+            dF.data_ptr(), dE.data_ptr(), scale, sigma2, out.data_ptr(), nmv.data_ptr(), stv.data_ptr())
+    t = timed(go, 100)
+    assert int(stv[0]) == 0 and int(nmv[0]) == n_host
+    line = {"row": f"SearchForTriangulation, device batch (1 keyframe x {P} neighbours, ~{kf.n} kp each, "
+            "levelsup 4)", "unit": "pairs/s", "value": round(P / t, 2), "ms_per_call": round(t * 1e3, 4),
+            "us_per_pair": round(t * 1e6 / P, 3), "units_per_call": P, "bytes_per_call": P * per_pair,
+            "matches": int(nmv.sum()), "cpu_value": None,
+            "note": "device form, FeatureVectors as the batched transform wrote them; 2 launches (init; "
+            "search, a wave per common node); issued back to back; no CPU leg"}
+    print(json.dumps(line), flush=True)
+    # SearchByBoW's batch at the same slot shape: the 20 neighbours as keyframes (every feature
+    # with a map point) against the keyframe as the frame
+    mb = native.ORBmatcher(0.75, True, device=0)
+    mb.set_stream(stream)
+    ok = torch.ones(B * cap, dtype=torch.uint8, device=DEV)
+
+    def gob():
+        mb.search_by_bow_batch_device(P, p2.data_ptr(), p1.data_ptr(), cap, D.data_ptr(), A.data_ptr(),
+                                      ok.data_ptr(), nn.data_ptr(), nid.data_ptr(), off.data_ptr(),
+                                      feat.data_ptr(), cap, D.data_ptr(), A.data_ptr(), nn.data_ptr(),
+                                      nid.data_ptr(), off.data_ptr(), feat.data_ptr(), out.data_ptr(),
+                                      nmv.data_ptr(), stv.data_ptr())
+    tb = timed(gob, 100)
+    assert int(stv[0]) == 0
+    line = {"row": f"SearchByBoW, device batch at the same slot shape ({P} pairs, ~{kf.n} features)",
+            "unit": "pairs/s", "value": round(P / tb, 2), "ms_per_call": round(tb * 1e3, 4),
+            "us_per_pair": round(tb * 1e6 / P, 3), "units_per_call": P,
+            "bytes_per_call": P * (frames[0].n + frames[1].n) * (32 + 8), "matches": int(nmv.sum()),
+            "cpu_value": None, "triangulation_over_bow": round(t / tb, 3),
+            "note": "the comparison row for SearchForTriangulation's batch: same slots, same grid shape"}
+    print(json.dumps(line), flush=True)
+    m.close()
+    mb.close()
+    gv.close()
+
+
 def row_track():
     """The per-frame tracking-loop matchers through the host ABI (uploads included):
     TrackWithMotionModel's SearchByProjection(CurrentFrame, LastFrame, th, mono)
@@ -470,7 +587,7 @@ def row_bow(tmpdir):
 if __name__ == "__main__":
     import tempfile
     with tempfile.TemporaryDirectory() as td:
-        rows = {"single": row_single, "color": row_color, "stereo": row_stereo, "reloc": row_reloc, "fuse": row_fuse, "track": row_track,
+        rows = {"single": row_single, "color": row_color, "stereo": row_stereo, "reloc": row_reloc, "fuse": row_fuse, "triangulation": row_triangulation, "track": row_track,
                 "distinctive": row_distinctive, "bow": lambda: row_bow(td)}
         for name in (sys.argv[1:] or list(rows)):
             rows[name]()
