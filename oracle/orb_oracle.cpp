@@ -1087,6 +1087,7 @@ int oracle_compute_stereo_matches(const orbfe_params* p, const uint8_t* imL, con
         if (best_dist >= kThHigh) continue;
         // sub-pixel match by correlation (663-735)
         const float ur0 = kr[best_ir].x;
+        if (level_l < 0 || level_l >= p->nlevels) return ORBFE_ERR_UNSUPPORTED;  // mvInvScaleFactors[octave]
         const float sf = t.inv[level_l];
         const float sul = std::round(kpl.x * sf), svl = std::round(kpl.y * sf);
         const float sur0 = std::round(ur0 * sf);

@@ -131,11 +131,12 @@ __global__ __launch_bounds__(kStereoBlock) void stereo_match_kernel(StereoArgs a
         sad_out[il] = -1;
     }
     const int R = a.nrows;
-    if (!(vl >= 0.f) || (int)vl >= R || level_l < 0 || level_l >= a.nlevels) {
+    // vRowIndices[vL]: float -> size_t truncates, so -1 < vL < 0 reads row 0 like the reference
+    if (!(vl > -1.f) || !(vl < (float)R)) {
         if (lane == 0) atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);
         return;
     }
-    const int row = (int)vl;  // vRowIndices[vL]: float -> size_t truncation
+    const int row = (int)vl;
     const int* off = a.row_off + (size_t)f * (R + 1);
     const int c0 = off[row], c1 = off[row + 1];
     if (c0 == c1) return;
@@ -162,6 +163,12 @@ __global__ __launch_bounds__(kStereoBlock) void stereo_match_kernel(StereoArgs a
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, o, 64));
     if ((best >> 16) >= (uint32_t)kStereoThHigh) return;
+    // the level's tables are first read here (672): an octave no candidate can pair with is
+    // never used as an index and leaves the keypoint unmatched
+    if (level_l < 0 || level_l >= a.nlevels) {
+        if (lane == 0) atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);
+        return;
+    }
     const int best_ir = (int)(best & 0xffff);
     // sub-pixel match by correlation (663-706)
     const float ur0 = kr[best_ir].x;

@@ -7,97 +7,15 @@ kernels (stereo_rows / stereo_match / stereo_filter) through the C ABI, bit-exac
 Parity of the whole row is "unpinned" in the DESIGN.md sense: the reference holds no stereo
 fixtures; the oracle is pinned by the restatement here.
 """
-import math
-
 import numpy as np
 import pytest
 
 import oracle
 from orbslam_mapsave_amd.synth import synthetic_stereo_pair
+from stereo_cases import restated  # the restatement, shared with test_stereo_edges.py
 
 F32 = np.float32
 BF, B = 50.0, 0.1  # mbf = fx * baseline (fx 500, 10 cm), mb = mbf / fx
-
-
-def popcount_rows(a, b):
-    return np.unpackbits(a ^ b, axis=-1).sum(-1)
-
-
-def restated(p, im_l, im_r, kl, dl, kr, dr, bf, b):
-    """Frame::ComputeStereoMatches restated line by line (float32 scalars, python ints)."""
-    scale = oracle.tables(p)["scale"]
-    inv = oracle.tables(p)["inv_scale"]
-    pl, pr = oracle.pyramid(p, im_l), oracle.pyramid(p, im_r)
-    nl, nr = len(kl), len(kr)
-    ur_out = np.full(nl, -1, F32)
-    dp_out = np.full(nl, -1, F32)
-    rows = [[] for _ in range(im_l.shape[0])]
-    for ir in range(nr):
-        y = F32(kr["y"][ir])
-        r = F32(2.0) * scale[kr["octave"][ir]]
-        for yi in range(math.floor(y - r), math.ceil(y + r) + 1):
-            rows[yi].append(ir)
-    min_d = F32(-3)
-    max_d = F32(bf) / F32(b)
-    acc = []
-    for il in range(nl):
-        lvl = int(kl["octave"][il])
-        vl, ul = F32(kl["y"][il]), F32(kl["x"][il])
-        cand = rows[int(vl)]
-        if not cand:
-            continue
-        min_u, max_u = ul - max_d, ul - min_d
-        if max_u < 0:
-            continue
-        best, best_ir = 100, 0
-        for ir in cand:
-            if kr["octave"][ir] < lvl - 1 or kr["octave"][ir] > lvl + 1:
-                continue
-            u = F32(kr["x"][ir])
-            if min_u <= u <= max_u:
-                d = int(popcount_rows(dl[il], dr[ir]))
-                if d < best:
-                    best, best_ir = d, ir
-        if best >= 100:
-            continue
-        sf = inv[lvl]
-        rnd = lambda v: F32(math.floor(abs(float(v)) + 0.5) * (1 if v >= 0 else -1))  # round()
-        sul, svl, sur0 = rnd(F32(kl["x"][il]) * sf), rnd(F32(kl["y"][il]) * sf), rnd(F32(kr["x"][best_ir]) * sf)
-        PL, PR = pl[lvl].astype(np.int64), pr[lvl].astype(np.int64)
-        r0, c0 = int(svl) - 5, int(sul) - 5
-        if sur0 < 0 or sur0 + 11 >= PR.shape[1]:
-            continue
-        IL = PL[r0:r0 + 11, c0:c0 + 11]
-        IL = IL - IL[5, 5]
-        dists = []
-        for inc in range(-5, 6):
-            cc = int(sur0) + inc - 5
-            IR = PR[r0:r0 + 11, cc:cc + 11]
-            dists.append(int(np.abs(IL - (IR - IR[5, 5])).sum()))
-        bi = int(np.argmin(dists)) - 5  # first minimum
-        if bi in (-5, 5):
-            continue
-        d1, d2, d3 = (F32(dists[5 + bi + k]) for k in (-1, 0, 1))
-        delta = (d1 - d3) / (F32(2.0) * (d1 + d3 - F32(2.0) * d2))
-        if delta < -1 or delta > 1:
-            continue
-        bur = scale[lvl] * ((sur0 + F32(bi)) + delta)
-        disp = ul - bur
-        if disp >= 0 and disp < max_d:
-            if disp <= 0:
-                disp = F32(0.01)
-                bur = F32(float(ul) - 0.01)
-            dp_out[il] = F32(bf) / disp
-            ur_out[il] = bur
-            acc.append((dists[5 + bi], il))
-    if acc:
-        acc.sort()
-        median = F32(acc[len(acc) // 2][0])
-        th = (F32(1.5) * F32(1.4)) * median
-        for s, il in acc:
-            if not F32(s) < th:
-                ur_out[il] = dp_out[il] = -1
-    return ur_out, dp_out
 
 
 def case(seed, w=640, h=480, nf=1000, ini=20):
