@@ -8,9 +8,8 @@
 // host applies the Replace / AddObservation branch afterwards, walking the points in order
 // (include/orbfe_orbslam.hpp ORBmatcher::Fuse).  No fixed point, no greedy rounds.
 //
-//   fuse_grid_kernel     KeyFrame::mGrid (the Frame grid, Frame.cc:341-356) of every keyframe of
-//                        the batch in one launch, one workgroup per keyframe; the items list is
-//                        built in LDS up to kFuseGridLds keypoints and in place above
+//   grid_kernel          (orbfe_grid.hip) KeyFrame::mGrid, the Frame grid, of every keyframe of
+//                        the batch in one launch, one workgroup per keyframe
 //   fuse_search_kernel   one wave per (keyframe, point): projection, KeyFrame::IsInImage,
 //                        distance / viewing-angle tests, MapPoint::PredictScale,
 //                        KeyFrame::GetFeaturesInArea (features_in_area_wave), the level and
@@ -22,92 +21,7 @@
 
 namespace orbfe {
 
-constexpr int kFuseGridLds = 4096;  // keypoints whose items list is built in LDS (16 KB)
 constexpr int kFuseKfPerLaunch = 40;  // poses carried by one launch's kernel arguments
-
-__device__ __forceinline__ int fuse_cell(const orbfe_keypoint* k, int i, float minx, float miny,
-                                         float gwi, float ghi) {
-    const int gx = (int)roundf((k[i].x - minx) * gwi);
-    const int gy = (int)roundf((k[i].y - miny) * ghi);
-    if (gx < 0 || gx >= kGridCols || gy < 0 || gy >= kGridRows) return -1;  // PosInGrid (500-510)
-    return gx * kGridRows + gy;  // mGrid[ix][iy]
-}
-
-// Fills items (LDS or the keyframe's citems) from the cell cursors in cnt and orders every cell
-// by keypoint index (insertion order); cnt[c] ends as the end of cell c.
-__device__ __forceinline__ void fuse_grid_fill(const orbfe_keypoint* k, int n, float minx,
-                                               float miny, float gwi, float ghi, int* cnt,
-                                               int* items) {
-    for (int i = threadIdx.x; i < n; i += kGridBlock) {
-        const int c = fuse_cell(k, i, minx, miny, gwi, ghi);
-        if (c >= 0) items[atomicAdd(&cnt[c], 1)] = i;
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < kGridCells; c += kGridBlock) {
-        const int e = cnt[c], s0 = c ? cnt[c - 1] : 0;
-        for (int q = s0 + 1; q < e; ++q) {
-            const int v = items[q];
-            int b = q - 1;
-            while (b >= s0 && items[b] > v) {
-                items[b + 1] = items[b];
-                --b;
-            }
-            items[b + 1] = v;
-        }
-    }
-    __syncthreads();
-}
-
-// Keyframe kf's grid as a CSR at cstart + kf * (kGridCells + 1) / citems + kf * kp_cap.
-__global__ __launch_bounds__(kGridBlock) void fuse_grid_kernel(const orbfe_keypoint* keys,
-                                                               long long keys_pitch,
-                                                               const int* n_kp, int kp_cap,
-                                                               int kp_max, float minx, float miny,
-                                                               float gwi, float ghi,
-                                                               int* cstart_all, int* citems_all) {
-    __shared__ int cnt[kGridCells];
-    __shared__ int s_items[kFuseGridLds];
-    __shared__ int tmp[kGridBlock / 64 + 1];
-    const int kf = blockIdx.x;
-    const orbfe_keypoint* k = keys + (long long)kf * keys_pitch;
-    const int n = min(max(n_kp[kf], 0), kp_max);
-    int* cstart = cstart_all + (size_t)kf * (kGridCells + 1);
-    int* citems = citems_all + (size_t)kf * kp_cap;
-    for (int c = threadIdx.x; c < kGridCells; c += kGridBlock) cnt[c] = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += kGridBlock) {
-        const int c = fuse_cell(k, i, minx, miny, gwi, ghi);
-        if (c >= 0) atomicAdd(&cnt[c], 1);
-    }
-    __syncthreads();
-    constexpr int PER = (kGridCells + kGridBlock - 1) / kGridBlock;
-    int local[PER], sum = 0;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int c = threadIdx.x * PER + j;
-        local[j] = c < kGridCells ? cnt[c] : 0;
-        sum += local[j];
-    }
-    int total;
-    int off = block_exclusive_scan<kGridBlock>(sum, tmp, total);
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int c = threadIdx.x * PER + j;
-        if (c < kGridCells) {
-            cstart[c] = off;
-            cnt[c] = off;  // cursor
-        }
-        off += local[j];
-    }
-    if (threadIdx.x == 0) cstart[kGridCells] = total;
-    __syncthreads();
-    if (n <= kFuseGridLds) {
-        fuse_grid_fill(k, n, minx, miny, gwi, ghi, cnt, s_items);
-        for (int i = threadIdx.x; i < total; i += kGridBlock) citems[i] = s_items[i];
-    } else {
-        fuse_grid_fill(k, n, minx, miny, gwi, ghi, cnt, citems);
-    }
-}
 
 struct FuseArgs {
     const orbfe_keypoint* keys;  // keyframe kf at keys + kf * keys_pitch (keypoints)
@@ -119,7 +33,7 @@ struct FuseArgs {
     int kp_max;                  // keypoints a keyframe can hold: n_kp is clipped to it
     const int* n_kp;
     float minx, maxx, miny, maxy, gwi, ghi;
-    const int* cstart;           // fuse_grid_kernel's outputs
+    const int* cstart;           // grid_kernel's outputs, one CSR per keyframe
     const int* citems;
     int n_mp;
     const float* xyz;
@@ -140,6 +54,16 @@ struct FuseArgs {
     float T[kFuseKfPerLaunch][12];  // Tcw of keyframes kf0 + blockIdx.y
     float ow[kFuseKfPerLaunch][3];  // camera centres (host, double accumulation)
 };
+
+__device__ __forceinline__ DevFrame fuse_frame(const FuseArgs& a, int kf) {
+    return DevFrame{a.keys + kf * a.keys_pitch,
+                    reinterpret_cast<const uint4*>(a.desc + kf * a.desc_pitch),
+                    a.ur ? a.ur + (size_t)kf * a.kp_cap : nullptr,
+                    min(max(a.n_kp[kf], 0), a.kp_max),
+                    a.minx, a.maxx, a.miny, a.maxy, a.gwi, a.ghi,
+                    a.cstart + (size_t)kf * (kGridCells + 1),
+                    a.citems + (size_t)kf * a.kp_cap};
+}
 
 // One wave per (keyframe, point).  kSim3: the loop-closing overload, no chi-square test.
 template <bool kSim3>
@@ -177,19 +101,7 @@ __global__ __launch_bounds__(256) void fuse_search_kernel(FuseArgs a) {
         if (lvl < 0 || lvl >= a.nlevels) {
             if ((threadIdx.x & 63) == 0) atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);  // mvScaleFactors[lvl]
         } else {
-            DevFrame F;
-            F.k = a.keys + (long long)kf * a.keys_pitch;
-            F.desc = reinterpret_cast<const uint4*>(a.desc + (long long)kf * a.desc_pitch);
-            F.ur = a.ur ? a.ur + (size_t)kf * a.kp_cap : nullptr;
-            F.n = min(max(a.n_kp[kf], 0), a.kp_max);
-            F.minx = a.minx;
-            F.maxx = a.maxx;
-            F.miny = a.miny;
-            F.maxy = a.maxy;
-            F.gwi = a.gwi;
-            F.ghi = a.ghi;
-            F.cstart = a.cstart + (size_t)kf * (kGridCells + 1);
-            F.citems = a.citems + (size_t)kf * a.kp_cap;
+            const DevFrame F = fuse_frame(a, kf);
             const float radius = a.th * a.scale[lvl];
             const uint4 q0 = a.mdesc[2 * i], q1 = a.mdesc[2 * i + 1];
             // KeyFrame::GetFeaturesInArea(u, v, radius) has no level filter (KeyFrame.cc:1311);
@@ -254,9 +166,9 @@ int fuse_launch(orbfe_matcher* m, FuseArgs& a, int n_kf, const float* tcw, int m
     if ((st = m->fu_ci.ensure((size_t)n_kf * a.kp_cap * sizeof(int)))) return st;
     a.cstart = m->fu_cs.as<int>();
     a.citems = m->fu_ci.as<int>();
-    hipLaunchKernelGGL(fuse_grid_kernel, dim3(n_kf), dim3(kGridBlock), 0, m->stream, a.keys,
-                       a.keys_pitch, a.n_kp, a.kp_cap, a.kp_max, a.minx, a.miny, a.gwi, a.ghi,
-                       m->fu_cs.as<int>(), m->fu_ci.as<int>());
+    hipLaunchKernelGGL(grid_kernel, dim3(n_kf), dim3(kGridBlock), 0, m->stream, a.keys,
+                       a.keys_pitch, a.n_kp, a.kp_max, a.minx, a.miny, a.gwi, a.ghi,
+                       m->fu_cs.as<int>(), m->fu_ci.as<int>(), a.kp_cap);
     for (int k0 = 0; k0 < n_kf; k0 += kFuseKfPerLaunch) {
         const int nk = std::min(kFuseKfPerLaunch, n_kf - k0);
         a.kf0 = k0;

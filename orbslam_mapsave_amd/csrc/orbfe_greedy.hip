@@ -638,6 +638,7 @@ __global__ __launch_bounds__(1024) void sbp_local_fused_kernel(SbpFusedArgs fa) 
     // Staging: every load of a batch is issued before its LDS stores (one global latency per
     // batch, not one per element).
     for (int c = tid; c <= kGridCells; c += 1024) cs[c] = 0;
+    int* cur = cs + 1;  // the cells' counters, then cursors (grid_scan)
     static_assert(kSbpFixKp == 2 * 1024, "two keypoints per thread");
     int mine[2] = {-1, -1};  // AssignFeaturesToGrid's cell of keypoints tid, tid + 1024
     {
@@ -660,13 +661,8 @@ __global__ __launch_bounds__(1024) void sbp_local_fused_kernel(SbpFusedArgs fa) 
             if (k < F.n) {
                 kxy[k] = make_float2(kx[b], ky[b]);
                 koct[k] = (int8_t)min(max(ko[b], -128), 127);
-                // PosInGrid (Frame.cc:500-510), as grid_lds_kernel
-                const int gx = (int)roundf((kx[b] - F.minx) * F.gwi);
-                const int gy = (int)roundf((ky[b] - F.miny) * F.ghi);
-                if (gx >= 0 && gx < kGridCols && gy >= 0 && gy < kGridRows) {
-                    mine[b] = gx * kGridRows + gy;
-                    atomicAdd(&cs[mine[b]], 1);
-                }
+                mine[b] = grid_cell(kx[b], ky[b], F.minx, F.miny, F.gwi, F.ghi);
+                if (mine[b] >= 0) atomicAdd(&cur[mine[b]], 1);
             }
         }
     }
@@ -679,59 +675,15 @@ __global__ __launch_bounds__(1024) void sbp_local_fused_kernel(SbpFusedArgs fa) 
 #pragma unroll
         for (int b = 0; b < 4; ++b) fdesc[min(q0 + tid + 1024 * b, 2 * F.n - 1)] = d[b];
     }
-    // The frame's grid built in this workgroup's LDS (grid_lds_kernel's counting sort): cs[c]
-    // the start of cell c, ci its keypoints in index (insertion) order.
+    // The frame's grid built in this workgroup's LDS (grid_kernel's counting sort): cs[c] the
+    // start of cell c, ci its keypoints in index (insertion) order.
     __syncthreads();
-    {
-        constexpr int PER = (kGridCells + 1023) / 1024;
-        int local[PER], sum = 0;
+    grid_scan<1024>(cur, scan_tmp);
 #pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int c = tid * PER + j;
-            local[j] = c < kGridCells ? cs[c] : 0;
-            sum += local[j];
-        }
-        int total;
-        int off = block_exclusive_scan<1024>(sum, scan_tmp, total);
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int c = tid * PER + j;
-            if (c < kGridCells) cs[c] = off;  // cursor
-            off += local[j];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-            if (mine[b] >= 0) ci[atomicAdd(&cs[mine[b]], 1)] = tid + 1024 * b;
-        __syncthreads();
-        // cs[c] is now the end of cell c: sort each cell (index order), then shift to starts
-        int endp[PER];
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int c = tid * PER + j;
-            endp[j] = 0;
-            if (c < kGridCells) {
-                const int e = cs[c], s0 = c ? cs[c - 1] : 0;
-                for (int q = s0 + 1; q < e; ++q) {
-                    const int v = ci[q];
-                    int b = q - 1;
-                    while (b >= s0 && ci[b] > v) {
-                        ci[b + 1] = ci[b];
-                        --b;
-                    }
-                    ci[b + 1] = v;
-                }
-                endp[j] = c ? cs[c - 1] : 0;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int c = tid * PER + j;
-            if (c < kGridCells) cs[c] = endp[j];
-        }
-        if (tid == 0) cs[kGridCells] = total;
-    }
+    for (int b = 0; b < 2; ++b)
+        if (mine[b] >= 0) ci[atomicAdd(&cur[mine[b]], 1)] = tid + 1024 * b;
+    __syncthreads();
+    grid_sort<1024>(cs, ci);
     __syncthreads();
     int in = 0, ovf = 0, bad_level = 0;
     if (i < a.mp.m) {  // every lane of the point evaluates the (cheap, uniform) frustum test
@@ -769,13 +721,9 @@ __global__ __launch_bounds__(1024) void sbp_local_fused_kernel(SbpFusedArgs fa) 
                 // features_in_area's order (ix-major, iy, insertion); the level check is on
                 // (maxLevel = pl >= 0).  Lane sub takes window cells sub, sub + kSbpLpp, ..;
                 // a sub-group scan of the per-cell counts gives each candidate its rank.
-                const int cx0 = max(0, (int)floorf((x - F.minx - rs) * F.gwi));
-                const int cx1 = min(kGridCols - 1, (int)ceilf((x - F.minx + rs) * F.gwi));
-                const int cy0 = max(0, (int)floorf((y - F.miny - rs) * F.ghi));
-                const int cy1 = min(kGridRows - 1, (int)ceilf((y - F.miny + rs) * F.ghi));
-                if (cx0 < kGridCols && cx1 >= 0 && cy0 < kGridRows && cy1 >= 0) {
+                const CellWindow w = cell_window(F, x, y, rs);
+                if (!w.empty) {
                     const uint4 q0 = a.mp.desc[2 * i], q1 = a.mp.desc[2 * i + 1];
-                    const int ny = cy1 - cy0 + 1, ncell = (cx1 - cx0 + 1) * ny;
                     auto pass = [&](int idx) {
                         const int oct = koct[idx];
                         if (oct < pl - 1 || oct > pl) return false;
@@ -787,11 +735,11 @@ __global__ __launch_bounds__(1024) void sbp_local_fused_kernel(SbpFusedArgs fa) 
                         }
                         return true;
                     };
-                    for (int t0 = 0; t0 < ncell; t0 += kSbpLpp) {
+                    for (int t0 = 0; t0 < w.ncell; t0 += kSbpLpp) {
                         const int t = t0 + sub;
                         int e0 = 0, e1 = 0, cnt = 0;
-                        if (t < ncell) {
-                            const int c = (cx0 + t / ny) * kGridRows + cy0 + t % ny;
+                        if (t < w.ncell) {
+                            const int c = w.cell(t);
                             e0 = cs[c];
                             e1 = cs[c + 1];
                             for (int e = e0; e < e1; ++e) cnt += pass(ci[e]);

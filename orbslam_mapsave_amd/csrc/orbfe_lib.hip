@@ -3,6 +3,7 @@
 #include "orbfe_extract.hip"
 #include "orbfe_stereo.hip"
 #include "orbfe_api.hip"
+#include "orbfe_grid.hip"
 #include "orbfe_match.hip"
 #include "orbfe_greedy.hip"
 #include "orbfe_match_api.hip"

@@ -1,12 +1,11 @@
 // orbfe_match.hip — MI355X (gfx950) replacement for the hot subset of ORB-SLAM2's ORBmatcher
-// (skaegy/ORBSLAM_MapSave src/ORBmatcher.cc) and the Frame grid it queries (src/Frame.cc).
+// (skaegy/ORBSLAM_MapSave src/ORBmatcher.cc); the Frame grid it queries is orbfe_grid.hip.
 //
 //   hamming_kernel       DescriptorDistance (1650-1666), one row pair per lane
 //   bf_match_kernel      brute-force best/second (config 3) on the i8 matrix cores: Hamming
 //                        as popc(r) - 2 r.q + popc(q), references streamed through LDS
-//   grid_kernel          Frame::AssignFeaturesToGrid (Frame.cc:341-356) as a CSR
-//   *_cand_kernel        GetFeaturesInArea (Frame.cc:445-498) + distances for every query in
-//                        parallel (counts, scan, fill)
+//   *_cand_kernel        GetFeaturesInArea (features_in_area_wave) + distances for every query
+//                        in parallel (counts, scan, fill)
 //   sfi_round_kernel     SearchForInitialization's sequential greedy-with-steals semantics (H7)
 //                        as Jacobi rounds to the unique fixed point of the in-order loop (a
 //                        wave per query, lanes over candidates); sfi_final_kernel applies the
@@ -24,19 +23,7 @@
 
 namespace orbfe {
 
-constexpr int kGridCols = 64, kGridRows = 48;  // FRAME_GRID_COLS/ROWS (Frame.h:37-38)
-constexpr int kGridCells = kGridCols * kGridRows;
 constexpr int kHistLen = kHistoLength;  // ORBmatcher.cc:39 (kThHigh / kThLow: orbfe_device.hpp)
-
-struct DevFrame {
-    const orbfe_keypoint* k;
-    const uint4* desc;  // 2 x uint4 per keypoint
-    const float* ur;    // NULL: monocular
-    int n;
-    float minx, maxx, miny, maxy, gwi, ghi;
-    const int* cstart;  // kGridCells + 1
-    const int* citems;
-};
 
 __device__ __forceinline__ int hamming_rows(const uint4* a, const uint4* b) {
     return hamming256(a[0], a[1], b[0], b[1]);
@@ -549,277 +536,6 @@ __global__ __launch_bounds__(kBfBlock, ORBFE_BF_WAVES) void bf_match_fp4e_kernel
 // GPU suite runs the brute-force parity tests on both).
 using BfKernel = void (*)(const uint8_t*, long long, const int*, int, const uint8_t*, long long,
                           const int*, int*);
-
-// ---------------------------------------------------------------------------------------------
-// Grid as CSR.  cellof[i] = -1 for keypoints outside the 64 x 48 grid (PosInGrid, 500-510).
-constexpr int kGridBlock = 1024;
-__global__ __launch_bounds__(kGridBlock) void grid_kernel(const orbfe_keypoint* k, int n,
-                                                          float minx, float miny, float gwi,
-                                                          float ghi, int* cellof, int* cstart,
-                                                          int* citems) {
-    __shared__ int cnt[kGridCells];
-    __shared__ int tmp[kGridBlock / 64 + 1];
-    for (int c = threadIdx.x; c < kGridCells; c += kGridBlock) cnt[c] = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += kGridBlock) {
-        const int gx = (int)roundf((k[i].x - minx) * gwi);
-        const int gy = (int)roundf((k[i].y - miny) * ghi);
-        int c = -1;
-        if (gx >= 0 && gx < kGridCols && gy >= 0 && gy < kGridRows) {
-            c = gx * kGridRows + gy;  // mGrid[ix][iy]
-            atomicAdd(&cnt[c], 1);
-        }
-        cellof[i] = c;
-    }
-    __syncthreads();
-    constexpr int PER = (kGridCells + kGridBlock - 1) / kGridBlock;
-    int local[PER], sum = 0;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int c = threadIdx.x * PER + j;
-        local[j] = c < kGridCells ? cnt[c] : 0;
-        sum += local[j];
-    }
-    int total;
-    int off = block_exclusive_scan<kGridBlock>(sum, tmp, total);
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int c = threadIdx.x * PER + j;
-        if (c < kGridCells) {
-            cstart[c] = off;
-            cnt[c] = off;  // cursor
-        }
-        off += local[j];
-    }
-    if (threadIdx.x == 0) cstart[kGridCells] = total;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += kGridBlock) {
-        const int c = cellof[i];
-        if (c >= 0) citems[atomicAdd(&cnt[c], 1)] = i;
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < kGridCells; c += kGridBlock) {  // insertion order = index order
-        const int s = cstart[c], e = cstart[c + 1];
-        for (int a = s + 1; a < e; ++a) {
-            const int v = citems[a];
-            int b = a - 1;
-            while (b >= s && citems[b] > v) {
-                citems[b + 1] = citems[b];
-                --b;
-            }
-            citems[b + 1] = v;
-        }
-    }
-}
-
-constexpr int kGridPer = 8;                           // keypoints per thread held in registers
-constexpr int kGridLdsMax = kGridBlock * kGridPer;    // 8192: the items list fits LDS (32 KB)
-// grid_kernel for n <= kGridLdsMax: the cell of every keypoint stays in registers and the items
-// list is filled, ordered and only then copied out of LDS, so no step waits on a chain of
-// dependent global loads (grid_kernel's insertion sort walks global memory).
-__global__ __launch_bounds__(kGridBlock) void grid_lds_kernel(const orbfe_keypoint* k, int n,
-                                                              float minx, float miny, float gwi,
-                                                              float ghi, int* cstart,
-                                                              int* citems) {
-    __shared__ int cnt[kGridCells];
-    __shared__ int items[kGridLdsMax];
-    __shared__ int tmp[kGridBlock / 64 + 1];
-    for (int c = threadIdx.x; c < kGridCells; c += kGridBlock) cnt[c] = 0;
-    __syncthreads();
-    int mine[kGridPer];  // cells of keypoints threadIdx.x + j * kGridBlock
-#pragma unroll
-    for (int j = 0; j < kGridPer; ++j) {
-        const int i = threadIdx.x + j * kGridBlock;
-        mine[j] = -1;
-        if (i < n) {
-            const int gx = (int)roundf((k[i].x - minx) * gwi);
-            const int gy = (int)roundf((k[i].y - miny) * ghi);
-            if (gx >= 0 && gx < kGridCols && gy >= 0 && gy < kGridRows) {
-                mine[j] = gx * kGridRows + gy;  // mGrid[ix][iy]
-                atomicAdd(&cnt[mine[j]], 1);
-            }
-        }
-    }
-    __syncthreads();
-    constexpr int PER = (kGridCells + kGridBlock - 1) / kGridBlock;
-    int local[PER], sum = 0;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int c = threadIdx.x * PER + j;
-        local[j] = c < kGridCells ? cnt[c] : 0;
-        sum += local[j];
-    }
-    int total;
-    int off = block_exclusive_scan<kGridBlock>(sum, tmp, total);
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int c = threadIdx.x * PER + j;
-        if (c < kGridCells) {
-            cstart[c] = off;
-            cnt[c] = off;  // cursor
-        }
-        off += local[j];
-    }
-    if (threadIdx.x == 0) cstart[kGridCells] = total;
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < kGridPer; ++j)
-        if (mine[j] >= 0) items[atomicAdd(&cnt[mine[j]], 1)] = threadIdx.x + j * kGridBlock;
-    __syncthreads();
-    // insertion order = index order: sort each cell's items; cnt[c] is now the end of cell c
-    // and cnt[c - 1] its start
-    for (int c = threadIdx.x; c < kGridCells; c += kGridBlock) {
-        const int e = cnt[c], s0 = c ? cnt[c - 1] : 0;
-        for (int q = s0 + 1; q < e; ++q) {
-            const int v = items[q];
-            int b = q - 1;
-            while (b >= s0 && items[b] > v) {
-                items[b + 1] = items[b];
-                --b;
-            }
-            items[b + 1] = v;
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < total; i += kGridBlock) citems[i] = items[i];
-}
-
-// Frame::GetFeaturesInArea (Frame.cc:445-498): visits candidates in ix-major, iy, insertion
-// order and calls fn(idx) for each.
-template <class Fn>
-__device__ __forceinline__ void features_in_area(const DevFrame& F, float x, float y, float r,
-                                                 int min_level, int max_level, Fn fn) {
-    const int cx0 = max(0, (int)floorf((x - F.minx - r) * F.gwi));
-    if (cx0 >= kGridCols) return;
-    const int cx1 = min(kGridCols - 1, (int)ceilf((x - F.minx + r) * F.gwi));
-    if (cx1 < 0) return;
-    const int cy0 = max(0, (int)floorf((y - F.miny - r) * F.ghi));
-    if (cy0 >= kGridRows) return;
-    const int cy1 = min(kGridRows - 1, (int)ceilf((y - F.miny + r) * F.ghi));
-    if (cy1 < 0) return;
-    const bool check = min_level > 0 || max_level >= 0;
-    for (int ix = cx0; ix <= cx1; ++ix)
-        for (int iy = cy0; iy <= cy1; ++iy) {
-            const int c = ix * kGridRows + iy;
-            for (int e = F.cstart[c]; e < F.cstart[c + 1]; ++e) {
-                const int idx = F.citems[e];
-                const orbfe_keypoint kp = F.k[idx];
-                if (check) {
-                    if (kp.octave < min_level) continue;
-                    if (max_level >= 0 && kp.octave > max_level) continue;
-                }
-                if (fabsf(kp.x - x) < r && fabsf(kp.y - y) < r) fn(idx);
-            }
-        }
-}
-
-// Wave-cooperative GetFeaturesInArea for one query per wave (every lane passes the same query):
-// lane t takes cell t of the window in the reference's ix-major, iy order (64 cells per
-// step), counts its passing items, and an exclusive wave scan of the counts places every
-// candidate at its reference rank; emit(idx, rank) runs on the lane owning the candidate.
-// Returns the candidate count (wave-uniform).  keep(idx) is an extra per-candidate filter.
-template <class Keep, class Emit>
-__device__ __forceinline__ int features_in_area_wave(const DevFrame& F, float x, float y, float r,
-                                                     int min_level, int max_level, Keep keep,
-                                                     Emit emit) {
-    const int lane = threadIdx.x & 63;
-    const int cx0 = max(0, (int)floorf((x - F.minx - r) * F.gwi));
-    if (cx0 >= kGridCols) return 0;
-    const int cx1 = min(kGridCols - 1, (int)ceilf((x - F.minx + r) * F.gwi));
-    if (cx1 < 0) return 0;
-    const int cy0 = max(0, (int)floorf((y - F.miny - r) * F.ghi));
-    if (cy0 >= kGridRows) return 0;
-    const int cy1 = min(kGridRows - 1, (int)ceilf((y - F.miny + r) * F.ghi));
-    if (cy1 < 0) return 0;
-    const bool check = min_level > 0 || max_level >= 0;
-    const int ny = cy1 - cy0 + 1, ncell = (cx1 - cx0 + 1) * ny;
-    auto pass = [&](int idx) {
-        const orbfe_keypoint kp = F.k[idx];
-        if (check) {
-            if (kp.octave < min_level) return false;
-            if (max_level >= 0 && kp.octave > max_level) return false;
-        }
-        return fabsf(kp.x - x) < r && fabsf(kp.y - y) < r && keep(idx);
-    };
-    int total = 0;
-    for (int c0 = 0; c0 < ncell; c0 += 64) {
-        const int t = c0 + lane;
-        int e0 = 0, e1 = 0, n = 0;
-        if (t < ncell) {
-            const int c = (cx0 + t / ny) * kGridRows + cy0 + t % ny;
-            e0 = F.cstart[c];
-            e1 = F.cstart[c + 1];
-            for (int e = e0; e < e1; ++e) n += pass(F.citems[e]);
-        }
-        const int inc = wave_inclusive_sum(n);
-        int rank = total + inc - n;
-        if (n)
-            for (int e = e0; e < e1; ++e) {
-                const int idx = F.citems[e];
-                if (pass(idx)) emit(idx, rank++);
-            }
-        total += __shfl(inc, 63, 64);
-    }
-    return total;
-}
-
-// Exclusive scan of counts[0..n) into off[0..n], single workgroup.
-__global__ __launch_bounds__(1024) void scan_kernel(const int* counts, int n, int* off) {
-    __shared__ int tmp[1024 / 64 + 1];
-    int run = 0;
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int v = i < n ? counts[i] : 0;
-        int t;
-        const int ex = block_exclusive_scan<1024>(v, tmp, t);
-        if (i < n) off[i] = run + ex;
-        run += t;
-    }
-    if (threadIdx.x == 0) off[n] = run;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Frame::GetFeaturesInArea (Frame.cc:445-498) as a batch of queries — the parity probe of the
-// grid (orbfe_features_in_area): thread-per-query (features_in_area) and wave-per-query
-// (features_in_area_wave, which the matchers use: SearchForInitialization, SearchByProjection's
-// local-map / last-frame / keyframe forms) write each query's candidates in the reference's
-// order to items[off[q] ..).
-struct FiaArgs {
-    DevFrame f;
-    int nq;
-    const float* x;
-    const float* y;
-    const float* r;
-    const int* lo;
-    const int* hi;
-    int* cnt;
-    const int* off;
-    int* items;
-};
-template <bool FILL>
-__global__ __launch_bounds__(256) void fia_thread_kernel(FiaArgs a) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= a.nq) return;
-    const int o = FILL ? a.off[q] : 0;
-    int n = 0;
-    features_in_area(a.f, a.x[q], a.y[q], a.r[q], a.lo[q], a.hi[q], [&](int idx) {
-        if (FILL) a.items[o + n] = idx;
-        ++n;
-    });
-    if (!FILL) a.cnt[q] = n;
-}
-template <bool FILL>
-__global__ __launch_bounds__(256) void fia_wave_kernel(FiaArgs a) {
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= a.nq) return;
-    const int o = FILL ? a.off[q] : 0;
-    const int n = features_in_area_wave(
-        a.f, a.x[q], a.y[q], a.r[q], a.lo[q], a.hi[q], [](int) { return true; },
-        [&](int idx, int rank) {
-            if (FILL) a.items[o + rank] = idx;
-        });
-    if (!FILL && (threadIdx.x & 63) == 0) a.cnt[q] = n;
-}
 
 // ---------------------------------------------------------------------------------------------
 // SearchForInitialization (ORBmatcher.cc:408-523)

@@ -78,8 +78,8 @@ using namespace orbfe;
 struct orbfe_matcher {
     int device = 0;
     hipStream_t own = nullptr, stream = nullptr;
-    DevBuf fa_k, fa_d, fa_ur, fa_cs, fa_ci, fa_co;  // frame A (+ grid)
-    DevBuf fb_k, fb_d, fb_ur, fb_cs, fb_ci, fb_co;  // frame B (+ grid)
+    DevBuf fa_k, fa_d, fa_ur, fa_cs, fa_ci, fa_co;  // frame A (+ grid; co: feature lists)
+    DevBuf fb_k, fb_d, fb_ur, fb_cs, fb_ci, fb_co;  // frame B (+ grid; co: feature lists)
     DevBuf q, r, nq, nr, out;                       // brute force / hamming
     DevBuf cnt, off, cand;                          // candidate CSR
     DevBuf s1, s2, s3, s4, s5;                      // resolve scratch / outputs
@@ -342,15 +342,12 @@ struct orbfe_matcher {
         return ORBFE_OK;
     }
 
-    // Frame::AssignFeaturesToGrid: the LDS form up to kGridLdsMax keypoints.
-    void launch_grid(const orbfe_keypoint* k, int n, const orbfe_frame_view* v, int* cellof,
-                     int* cstart, int* citems) {
-        if (n <= kGridLdsMax)
-            hipLaunchKernelGGL(grid_lds_kernel, dim3(1), dim3(kGridBlock), 0, stream, k, n,
-                               v->min_x, v->min_y, v->grid_w_inv, v->grid_h_inv, cstart, citems);
-        else
-            hipLaunchKernelGGL(grid_kernel, dim3(1), dim3(kGridBlock), 0, stream, k, n, v->min_x,
-                               v->min_y, v->grid_w_inv, v->grid_h_inv, cellof, cstart, citems);
+    // Frame::AssignFeaturesToGrid of one frame of v->n keypoints at k (grid_kernel).
+    void launch_grid(const orbfe_keypoint* k, const orbfe_frame_view* v, int* cstart,
+                     int* citems) {
+        hipLaunchKernelGGL(grid_kernel, dim3(1), dim3(kGridBlock), 0, stream, k, 0LL,
+                           (const int*)nullptr, v->n, v->min_x, v->min_y, v->grid_w_inv,
+                           v->grid_h_inv, cstart, citems, 0);
     }
 
     // Uploads a frame view and builds its 64 x 48 grid (Frame::AssignFeaturesToGrid).
@@ -360,7 +357,6 @@ struct orbfe_matcher {
         DevBuf& u = second ? fb_ur : fa_ur;
         DevBuf& cs = second ? fb_cs : fa_cs;
         DevBuf& ci = second ? fb_ci : fa_ci;
-        DevBuf& co = second ? fb_co : fa_co;
         const int n = v->n;
         int st;
         if ((st = up(k, v->keys_un, (size_t)n * sizeof(orbfe_keypoint)))) return st;
@@ -368,45 +364,22 @@ struct orbfe_matcher {
         if (v->u_right && (st = up(u, v->u_right, (size_t)n * sizeof(float)))) return st;
         if ((st = cs.ensure((kGridCells + 1) * sizeof(int)))) return st;
         if ((st = ci.ensure(std::max(n, 1) * sizeof(int)))) return st;
-        if ((st = co.ensure(std::max(n, 1) * sizeof(int)))) return st;
         if ((st = flush())) return st;
-        launch_grid(k.as<orbfe_keypoint>(), n, v, co.as<int>(), cs.as<int>(), ci.as<int>());
-        F.k = k.as<orbfe_keypoint>();
-        F.desc = d.as<uint4>();
-        F.ur = v->u_right ? u.as<float>() : nullptr;
-        F.n = n;
-        F.minx = v->min_x;
-        F.maxx = v->max_x;
-        F.miny = v->min_y;
-        F.maxy = v->max_y;
-        F.gwi = v->grid_w_inv;
-        F.ghi = v->grid_h_inv;
-        F.cstart = cs.as<int>();
-        F.citems = ci.as<int>();
+        launch_grid(k.as<orbfe_keypoint>(), v, cs.as<int>(), ci.as<int>());
+        F = dev_frame(v, k.as<orbfe_keypoint>(), d.as<uint4>(),
+                      v->u_right ? u.as<float>() : nullptr, cs.as<int>(), ci.as<int>());
         return ORBFE_OK;
     }
 
     // Device-resident frame view (keys_un / desc / u_right are device pointers): builds the grid.
     // grid = false: F's grid arrays are not built (a kernel that builds the grid itself)
     int frame_device(const orbfe_frame_view* v, DevFrame& F, bool grid = true) {
-        const int n = v->n;
         int st;
         if ((st = fa_cs.ensure((kGridCells + 1) * sizeof(int)))) return st;
-        if ((st = fa_ci.ensure(std::max(n, 1) * sizeof(int)))) return st;
-        if ((st = fa_co.ensure(std::max(n, 1) * sizeof(int)))) return st;
-        if (grid) launch_grid(v->keys_un, n, v, fa_co.as<int>(), fa_cs.as<int>(), fa_ci.as<int>());
-        F.k = v->keys_un;
-        F.desc = reinterpret_cast<const uint4*>(v->desc);
-        F.ur = v->u_right;
-        F.n = n;
-        F.minx = v->min_x;
-        F.maxx = v->max_x;
-        F.miny = v->min_y;
-        F.maxy = v->max_y;
-        F.gwi = v->grid_w_inv;
-        F.ghi = v->grid_h_inv;
-        F.cstart = fa_cs.as<int>();
-        F.citems = fa_ci.as<int>();
+        if ((st = fa_ci.ensure(std::max(v->n, 1) * sizeof(int)))) return st;
+        if (grid) launch_grid(v->keys_un, v, fa_cs.as<int>(), fa_ci.as<int>());
+        F = dev_frame(v, v->keys_un, reinterpret_cast<const uint4*>(v->desc), v->u_right,
+                      fa_cs.as<int>(), fa_ci.as<int>());
         return ORBFE_OK;
     }
 

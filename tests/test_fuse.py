@@ -181,22 +181,32 @@ def test_gpu_fuse_search_empty_keyframe(mt):
     assert nf == 0 and (bi == -1).all() and (bd == 256).all()
 
 
+GRID_BLOCK = 1024             # grid_kernel's workgroup: thread t holds keypoints t + 1024 j
+GRID_LDS_MAX = 8 * GRID_BLOCK  # keypoints whose items list grid_kernel orders in LDS
+
+
 @functools.lru_cache(maxsize=None)
-def big_case():
-    """A keyframe of five frames' keypoints (about 5,000: past the 4,096 the grid kernel
-    orders in LDS), the first of them the scenario's own keyframe."""
+def big_case(copies):
+    """A keyframe of `copies` frames' keypoints, the first of them the scenario's own keyframe and
+    the others shifted copies.  Five (5,035 keypoints): the grid kernel's LDS form with five of
+    a thread's register slots in use; ten (10,070): past the 8,192 it orders in LDS, the
+    in-place form."""
     frames = [S.extract_frame(0, 1000, u_right=True)] + [
-        S.extract_frame(0, 1000, shift=(s, 2 * s), u_right=True) for s in range(1, 5)]
+        S.extract_frame(0, 1000, shift=(s, 2 * s), u_right=True) for s in range(1, copies)]
     kf = Frame(np.concatenate([f.keys for f in frames]), np.concatenate([f.desc for f in frames]),
                S.W, S.H, FC.SCALE, np.concatenate([f.u_right for f in frames]))
-    assert kf.n > 4096
+    if copies == 10:
+        assert kf.n > GRID_LDS_MAX
+    else:
+        assert 4 * GRID_BLOCK < kf.n <= GRID_LDS_MAX
     return FC.subset(FC.fuse_case(0, kf=kf), slice(0, 500))
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("copies", [5, 10])
 @pytest.mark.parametrize("th,mode", [(3.0, SE3), (4.0, SIM3)])
-def test_gpu_fuse_search_keyframe_past_lds_grid(mt, th, mode):
-    c = big_case()
+def test_gpu_fuse_search_keyframe_past_lds_grid(mt, th, mode, copies):
+    c = big_case(copies)
     exp = FC.restated(c, th, mode)
     assert exp[2] > 100
     check(gpu_search(mt, c, th, mode), exp)
@@ -417,17 +427,19 @@ def test_gpu_fuse_search_batch_launch_seams(mt, n_kf, mode, th):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("copies", [5, 10])
 @pytest.mark.parametrize("th,mode", [(3.0, SE3), (4.0, SIM3)])
-def test_gpu_fuse_search_batch_big_keyframe_second(mt, th, mode):
-    """A batch whose keyframe 1 has more than 4,096 keypoints: its grid is filled in place in
-    the batch's item slab (at keyframe 1's offset), between two small keyframes."""
-    c = FC.subset(big_case(), slice(0, 200))
+def test_gpu_fuse_search_batch_big_keyframe_second(mt, th, mode, copies):
+    """A batch whose keyframe 1 is a big one, between two small keyframes: its grid lands at
+    keyframe 1's offset of the batch's item slab, copied out of LDS (five copies) or, with more
+    than 8,192 keypoints (ten), filled in place there."""
+    c = FC.subset(big_case(copies), slice(0, 200))
     big = c["kf"]
     small = case(0)["kf"]
     kfs = [Frame(small.keys[:n], small.desc[:n], S.W, S.H, FC.SCALE, small.u_right[:n])
            for n in (300, 211)]
     kfs.insert(1, big)
-    assert kfs[1].n > 4096
+    assert (kfs[1].n > GRID_LDS_MAX) == (copies == 10)
     rng = np.random.Generator(np.random.PCG64(11))
     poses = [S.pose(rng, 0.001, 0.004), c["tcw"], S.pose(rng, 0.002, 0.004)]
     skips = (rng.uniform(size=(3, len(c["xyz"]))) < 0.1).astype(np.uint8)

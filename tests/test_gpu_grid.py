@@ -1,7 +1,8 @@
 """A16 — the Frame grid, directly: Frame::AssignFeaturesToGrid / PosInGrid (Frame.cc:341-356,
-500-510) and Frame::GetFeaturesInArea (Frame.cc:445-498) on the GPU (grid_lds_kernel for up to
-8,192 keypoints, grid_kernel above; features_in_area and features_in_area_wave) against the
-oracle's restatement (oracle/orb_oracle.cpp build_grid / features_in_area), candidate lists and
+500-510) and Frame::GetFeaturesInArea (Frame.cc:445-498) on the GPU (grid_kernel: the items
+list ordered in LDS for up to 8,192 keypoints, a thread holding the cells of keypoints
+t + 1024 j in registers, and in place above; features_in_area and features_in_area_wave) against
+the oracle's restatement (oracle/orb_oracle.cpp build_grid / features_in_area), candidate lists and
 their ORDER compared exactly.
 
 The cases pin what the matchers' first-wins ties depend on:
@@ -64,7 +65,7 @@ def mt():
     m.close()
 
 
-@pytest.mark.parametrize("n", [1, 100, 1000, 8192, 8193, 9000])
+@pytest.mark.parametrize("n", [0, 1, 100, 1000, 1024, 1025, 8192, 8193, 9000])
 @pytest.mark.parametrize("wave", [False, True])
 def test_features_in_area(mt, n, wave):
     f = grid_frame(n, n)
@@ -76,7 +77,10 @@ def test_features_in_area(mt, n, wave):
                                       int(hi[q]))
         assert np.array_equal(got[q], exp), (q, x[q], y[q], r[q], lo[q], hi[q])
         total += len(exp)
-    assert total > 0
+    if n == 0:  # the empty frame: no candidates, not a read of keypoint 0
+        assert all(len(g) == 0 for g in got)
+    else:
+        assert total > 0
 
 
 def test_roundf_half_away_insertion(mt):
