@@ -26,10 +26,18 @@ namespace orbfe {
         }                                                                                  \
     } while (0)
 
-// Device buffer that only grows.
+// Device buffer that only grows; it frees its memory when its owner goes.
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int ensure(size_t n) {
         if (n <= bytes) return ORBFE_OK;
         if (p) hipFree(p);

@@ -21,7 +21,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -1015,9 +1014,10 @@ static int search_by_bow1(orbfe_matcher* m, float nnratio, int check_ori, const 
     const size_t o_fd = (size_t)ktot * 32, o_ki = o_fd + (size_t)ftot * 32, o_ka = o_ki + 4 * (size_t)ktot,
                  o_fi = o_ka + 4 * (size_t)ktot, o_fa = o_fi + 4 * (size_t)ftot, o_out = o_fa + 4 * (size_t)ftot,
                  bytes = o_out + 4 * (size_t)ftot;
-    uint8_t* q = m->stage(bytes);
+    uint8_t* q = m->stg.stage(bytes);
     if (!q) return ORBFE_ERR_NOMEM;
-    if (!m->pin_dev) return ORBFE_OK;  // the staging buffer is not device-mapped: general path
+    const uint8_t* d = m->stg.dev(q);
+    if (!d) return ORBFE_OK;  // the staging buffer is not device-mapped: general path
     *done = true;
     // each common node's features in FeatureVector order (keyframe features with a good map
     // point only), as the node loop visits them (198-245)
@@ -1042,7 +1042,6 @@ static int search_by_bow1(orbfe_matcher* m, float nnratio, int check_ori, const 
             ++fy;
         }
     }
-    const uint8_t* d = m->pin_dev + (q - m->pin);
     a.kd = reinterpret_cast<const uint4*>(d);
     a.fd = reinterpret_cast<const uint4*>(d + o_fd);
     a.ki = reinterpret_cast<const int*>(d + o_ki);
@@ -1050,32 +1049,16 @@ static int search_by_bow1(orbfe_matcher* m, float nnratio, int check_ori, const 
     a.fi = reinterpret_cast<const int*>(d + o_fi);
     a.fa = reinterpret_cast<const float*>(d + o_fa);
     a.out = reinterpret_cast<int*>(const_cast<uint8_t*>(d + o_out));
-    volatile int* out = reinterpret_cast<volatile int*>(q + o_out);
+    int* out = reinterpret_cast<int*>(q + o_out);
     for (int s = 0; s < ftot; ++s) out[s] = kSlotPending;
     if ((st = m->flush())) return st;
     hipLaunchKernelGGL(bow_search1_kernel, dim3(a.nodes), dim3(256), 0, m->stream, a,
                        nnratio, check_ori);
     if (hipGetLastError() != hipSuccess) return ORBFE_ERR_HIP;
-    if (!m->pend.empty() || !m->dnq.empty() || m->cand_check) {
-        if ((st = m->sync())) return st;
-    } else {
-        // every slot is written once, after its node's last read of the staging buffer: the host
-        // waits on the slots themselves instead of a stream synchronisation; past kSlotWaitUs it
-        // synchronises the stream (which reports a failed kernel) and checks the slots again
-        const auto t0 = std::chrono::steady_clock::now();
-        for (int s = 0; s < ftot; ++s) {
-            while (out[s] == kSlotPending) {
-                if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(kSlotWaitUs)) {
-                    ORBFE_HIP(hipStreamSynchronize(m->stream));
-                    for (int u = s; u < ftot; ++u)
-                        if (out[u] == kSlotPending) return ORBFE_ERR_HIP;
-                    s = ftot;
-                    break;
-                }
-                __builtin_ia32_pause();
-            }
-        }
-    }
+    // every slot is written once, after its node's last read of the staging buffer: the host
+    // waits on the slots themselves instead of a stream synchronisation
+    if ((st = m->stg.idle() ? wait_words(out, ftot, kSlotPending, m->stream, kSlotWaitUs) : m->sync()))
+        return st;
     // the orientation filter (259-281) on the host, as in the reference: the rotation histogram
     // of every match, ComputeThreeMaxima (1604-1645), matches outside the three bins dropped
     int hist[kHistLen] = {};
@@ -1120,7 +1103,7 @@ int orbfe_search_by_bow(orbfe_matcher* m, float nnratio, int check_ori, int n_kf
         for (int i = 0; i < n_f; ++i) matches[i] = -1;  // vpMapPointMatches = NULL (164)
         *nmatches = 0;
         if (!kf_nn || !f_nn || !n_f) return ORBFE_OK;
-        if (!m->zero_copy_off && !bow1_off()) {
+        if (!m->stg.zero_copy_off && !bow1_off()) {
             bool done = false;
             if ((st = search_by_bow1(m, nnratio, check_ori, kf_desc, kf_angle, kf_mp_ok, kf_nn,
                                      kf_node_ids, kf_node_off, kf_feat, f_desc, f_angle, f_nn,
@@ -1146,7 +1129,7 @@ int orbfe_search_by_bow(orbfe_matcher* m, float nnratio, int check_ori, int n_kf
         if ((st = m->s1.ensure((size_t)f_cap * 4))) return st;  // bins per frame feature
         // bow_init_kernel's work as uploads (the scatter runs anyway): every match NULL (164),
         // an empty histogram, the finished-workgroup counter, nmatches and status 0
-        const bool zc = m->pin_dev != nullptr;
+        const bool zc = m->stg.pin_dev != nullptr;
         if (zc) {
             m->init_neg.assign((size_t)f_cap, -1);
             const int zeros[64] = {};
@@ -1162,10 +1145,10 @@ int orbfe_search_by_bow(orbfe_matcher* m, float nnratio, int check_ori, int n_kf
         int* res = nullptr;
         int* res_dev = nullptr;
         if (zc) {
-            uint8_t* q = m->stage((size_t)(n_f + 2) * 4);
+            uint8_t* q = m->stg.stage((size_t)(n_f + 2) * 4);
             if (!q) return ORBFE_ERR_NOMEM;
             res = reinterpret_cast<int*>(q);
-            res_dev = reinterpret_cast<int*>(m->pin_dev + (q - m->pin));
+            res_dev = reinterpret_cast<int*>(m->stg.dev(q));
         }
         BowMatchArgs a{};
         a.kf_cap = kf_cap;

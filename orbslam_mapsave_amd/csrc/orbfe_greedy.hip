@@ -716,7 +716,7 @@ __global__ __launch_bounds__(1024) void sbp_local_fused_kernel(SbpFusedArgs fa) 
                 if (a.th != 1.0) r *= a.th;
                 const float rs = r * fa.scalev[pl];
                 const float x = o.u, y = o.v;
-                int2* out = a.cand + (size_t)i * kSbpFix;
+                int2* out = a.c.cand + (size_t)i * kSbpFix;
                 // GetFeaturesInArea(x, y, rs, pl - 1, pl) (Frame.cc:445-498) on the LDS copy, in
                 // features_in_area's order (ix-major, iy, insertion); the level check is on
                 // (maxLevel = pl >= 0).  Lane sub takes window cells sub, sub + kSbpLpp, ..;
@@ -762,7 +762,7 @@ __global__ __launch_bounds__(1024) void sbp_local_fused_kernel(SbpFusedArgs fa) 
                 ovf = sub == 0 && n > kSbpFix;
             }
         }
-        if (sub == 0) a.cnt[i] = min(n, kSbpFix);
+        if (sub == 0) a.c.cnt[i] = min(n, kSbpFix);
     }
     const int w_in = wave_sum(in), w_ovf = wave_sum(ovf), w_bad = wave_sum(bad_level);
     if ((tid & 63) == 0) {

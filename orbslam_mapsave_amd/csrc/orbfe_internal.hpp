@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <chrono>
 #include <vector>
 
 #include "../../include/orbfe.h"
@@ -187,6 +188,26 @@ struct DescArgs {
     uint32_t pre_mask;          // levels whose blurred plane exists (bit l): windows read from it
     const uint4* frags;         // the matrix-core window blur: H / V fragments (blur_frags, 128..)
 };
+
+// The bounded wait on device-mapped pinned memory: until none of the n words at w (each written
+// once, with release semantics at system scope, by a kernel on `stream`) holds `pending`.  Polls
+// with acquire loads, so what the kernel wrote before a word is visible once the word is; past
+// limit_us it synchronises the stream (which reports a failed kernel) and checks once more.
+inline int wait_words(const int* w, int n, int pending, hipStream_t stream, int limit_us) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int s = 0; s < n; ++s) {
+        while (__atomic_load_n(w + s, __ATOMIC_ACQUIRE) == pending) {
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(limit_us)) {
+                if (hipStreamSynchronize(stream) != hipSuccess) return ORBFE_ERR_HIP;
+                for (; s < n; ++s)
+                    if (__atomic_load_n(w + s, __ATOMIC_ACQUIRE) == pending) return ORBFE_ERR_HIP;
+                return ORBFE_OK;
+            }
+            __builtin_ia32_pause();
+        }
+    }
+    return ORBFE_OK;
+}
 
 // Pixels [0, n) of a w-pixel row that OpenCV 3.3's x86 SSE2 vertical kernels produce (the rest
 // is the scalar tail): VResizeLinearVec_32s8u steps 16 while x <= w - 16, then 4 while

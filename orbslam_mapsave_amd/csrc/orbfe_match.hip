@@ -539,29 +539,37 @@ using BfKernel = void (*)(const uint8_t*, long long, const int*, int, const uint
 
 // ---------------------------------------------------------------------------------------------
 // SearchForInitialization (ORBmatcher.cc:408-523)
+// The candidate lists a *_cand_kernel writes, filled in by the host's candidate builder
+// (orbfe_match_api.hip): CSR lists (count -> scan -> fill) or kfix fixed slots per query.
+struct CandArgs {
+    long long cand_cap;  // fill writes only lists that end within the capacity
+    int* cnt;            // per query
+    const int* off;      // queries + 1
+    int2* cand;          // (index, dist [| octave << 16])
+    int kfix;            // fixed-slot form: candidate slots per query
+    int* ovf;            // fixed-slot form: queries with more candidates than kfix
+};
+
 struct SfiArgs {
     DevFrame f1, f2;
     const float* prev;  // 2 per F1 keypoint
     float window;
-    long long cand_cap;  // fill writes only lists that end within the capacity
-    int* cnt;           // per F1 keypoint
-    const int* off;     // n1 + 1
-    int2* cand;         // (i2, dist)
+    CandArgs c;         // one list per F1 keypoint of (i2, dist)
 };
 
 template <bool FILL>
 __global__ __launch_bounds__(256) void sfi_cand_kernel(SfiArgs a) {
     const int i1 = blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per F1 keypoint
     if (i1 >= a.f1.n) return;
-    if (FILL && a.off[i1 + 1] > a.cand_cap) return;
+    if (FILL && a.c.off[i1 + 1] > a.c.cand_cap) return;
     const orbfe_keypoint k1 = a.f1.k[i1];
     if (k1.octave > 0) {
-        if (!FILL && (threadIdx.x & 63) == 0) a.cnt[i1] = 0;
+        if (!FILL && (threadIdx.x & 63) == 0) a.c.cnt[i1] = 0;
         return;
     }
     const uint4* d1 = a.f1.desc + 2 * i1;
     const uint4 q0 = d1[0], q1 = d1[1];
-    int2* out = FILL ? a.cand + a.off[i1] : nullptr;
+    int2* out = FILL ? a.c.cand + a.c.off[i1] : nullptr;
     const int n = features_in_area_wave(
         a.f2, a.prev[2 * i1], a.prev[2 * i1 + 1], a.window, k1.octave, k1.octave,
         [](int) { return true; },
@@ -571,7 +579,7 @@ __global__ __launch_bounds__(256) void sfi_cand_kernel(SfiArgs a) {
                 out[rank] = make_int2(i2, hamming256(q0, q1, d2[0], d2[1]));
             }
         });
-    if (!FILL && (threadIdx.x & 63) == 0) a.cnt[i1] = n;
+    if (!FILL && (threadIdx.x & 63) == 0) a.c.cnt[i1] = n;
 }
 
 __device__ __forceinline__ int rot_bin(float a1, float a2) {  // ORBmatcher.cc:478-483
@@ -777,12 +785,7 @@ struct SbpLocalArgs {
     float th;
     int nlevels;         // levels of `scale`; a predicted level outside is UB in the reference
     int* status;         // NULL, or set to ORBFE_ERR_UNSUPPORTED for such a point
-    long long cand_cap;  // fill writes only lists that end within the capacity
-    int* cnt;
-    const int* off;
-    int2* cand;          // (idx, dist | octave << 16)
-    int kfix;            // kMode 2: candidate slots per point
-    int* ovf;            // kMode 2: points with more candidates than kfix
+    CandArgs c;          // (idx, dist | octave << 16); kMode 2 uses kfix / ovf
 };
 
 // kMode 0: count, 1: fill the CSR lists, 2: fixed slots in one pass (the first kfix candidates at
@@ -797,38 +800,38 @@ __global__ __launch_bounds__(256) void sbp_local_cand_kernel(SbpLocalArgs a) {
     if (i >= a.mp.m) return;
     const bool lead = (threadIdx.x & 63) == 0;  // the lane that writes the point's words
     if (!a.mp.in_view[i] || a.mp.bad[i]) {
-        if (!FILL && lead) a.cnt[i] = 0;
+        if (!FILL && lead) a.c.cnt[i] = 0;
         return;
     }
     const int pl = a.mp.lvl[i];
     if (pl < 0 || pl >= a.nlevels) {  // F.mvScaleFactors[nPredictedLevel] out of range
         if (a.status && lead) atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);
-        if (!FILL && lead) a.cnt[i] = 0;
+        if (!FILL && lead) a.c.cnt[i] = 0;
         return;
     }
     float r = a.mp.vcos[i] > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos (131-137)
     if (a.th != 1.0) r *= a.th;
     const float rs = r * a.scale[pl];
     const float pxr = a.mp.pxr[i];
-    if (FILL && a.off[i + 1] > a.cand_cap) return;
+    if (FILL && a.c.off[i + 1] > a.c.cand_cap) return;
     const uint4 q0 = a.mp.desc[2 * i], q1 = a.mp.desc[2 * i + 1];
     int n = 0;
-    int2* out = FILL ? a.cand + a.off[i] : kMode == 2 ? a.cand + (size_t)i * a.kfix : nullptr;
+    int2* out = FILL ? a.c.cand + a.c.off[i] : kMode == 2 ? a.c.cand + (size_t)i * a.c.kfix : nullptr;
     n = features_in_area_wave(
         a.f, a.mp.px[i], a.mp.py[i], rs, pl - 1, pl,
         [&](int idx) {  // stereo consistency (91-96)
             return !(a.f.ur && a.f.ur[idx] > 0 && fabsf(pxr - a.f.ur[idx]) > r * a.scale[pl]);
         },
         [&](int idx, int rank) {
-            if (FILL || (kMode == 2 && rank < a.kfix)) {
+            if (FILL || (kMode == 2 && rank < a.c.kfix)) {
                 const uint4* d = a.f.desc + 2 * idx;
                 out[rank] = make_int2(idx, hamming256(q0, q1, d[0], d[1]) | (a.f.k[idx].octave << 16));
             }
         });
-    if (kMode == 0 && lead) a.cnt[i] = n;
+    if (kMode == 0 && lead) a.c.cnt[i] = n;
     if (kMode == 2 && lead) {
-        a.cnt[i] = min(n, a.kfix);
-        if (n > a.kfix) atomicAdd(a.ovf, 1);
+        a.c.cnt[i] = min(n, a.c.kfix);
+        if (n > a.c.kfix) atomicAdd(a.c.ovf, 1);
     }
 }
 
@@ -848,12 +851,7 @@ struct SbpLastArgs {
     const float* scale;
     float th;
     int mode;              // 0: [o-1, o+1], 1: forward [o, -], 2: backward [0, o]
-    long long cand_cap;
-    int* cnt;
-    const int* off;
-    int2* cand;
-    int kfix;                 // kMode 2: candidate slots per point
-    int* ovf;                 // kMode 2: points with more candidates than kfix
+    CandArgs c;            // kMode 2 uses kfix / ovf
 };
 
 // kMode as sbp_kf_cand_kernel's: 0 count, 1 fill the CSR lists, 2 fixed slots in one pass
@@ -863,7 +861,7 @@ __global__ __launch_bounds__(256) void sbp_last_cand_kernel(SbpLastArgs a) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per last-frame point
     if (i >= a.n_last) return;
     // Inputs read up front, as in sbp_kf_cand_kernel.
-    const bool room = !FILL || a.off[i + 1] <= a.cand_cap;
+    const bool room = !FILL || a.c.off[i + 1] <= a.c.cand_cap;
     const bool live = a.valid[i] && !a.outlier[i];
     const float P[3] = {a.xyz[3 * i], a.xyz[3 * i + 1], a.xyz[3 * i + 2]};
     const int o = a.lk[i].octave;
@@ -882,23 +880,23 @@ __global__ __launch_bounds__(256) void sbp_last_cand_kernel(SbpLastArgs a) {
             const int lo = a.mode == 0 ? o - 1 : a.mode == 1 ? o : 0;
             const int hi = a.mode == 0 ? o + 1 : a.mode == 1 ? -1 : o;
             const uint4 q0 = a.desc[2 * i], q1 = a.desc[2 * i + 1];
-            int2* out = FILL ? a.cand + a.off[i] : kMode == 2 ? a.cand + (size_t)i * a.kfix : nullptr;
+            int2* out = FILL ? a.c.cand + a.c.off[i] : kMode == 2 ? a.c.cand + (size_t)i * a.c.kfix : nullptr;
             const float ur = u - a.bf * invz;
             n = features_in_area_wave(
                 a.cur, u, v, radius, lo, hi,
                 [&](int i2) { return !(a.cur.ur && a.cur.ur[i2] > 0 && fabsf(ur - a.cur.ur[i2]) > radius); },
                 [&](int i2, int rank) {
-                    if (FILL || (kMode == 2 && rank < a.kfix)) {
+                    if (FILL || (kMode == 2 && rank < a.c.kfix)) {
                         const uint4* d = a.cur.desc + 2 * i2;
                         out[rank] = make_int2(i2, hamming256(q0, q1, d[0], d[1]));
                     }
                 });
         }
     }
-    if (kMode == 0 && (threadIdx.x & 63) == 0) a.cnt[i] = n;
+    if (kMode == 0 && (threadIdx.x & 63) == 0) a.c.cnt[i] = n;
     if (kMode == 2 && (threadIdx.x & 63) == 0) {
-        a.cnt[i] = min(n, a.kfix);
-        if (n > a.kfix) atomicAdd(a.ovf, 1);
+        a.c.cnt[i] = min(n, a.c.kfix);
+        if (n > a.c.kfix) atomicAdd(a.c.ovf, 1);
     }
 }
 
@@ -925,12 +923,7 @@ struct SbpKfArgs {
     int nlevels;
     float log_scale, th;
     int* status;
-    long long cand_cap;
-    int* cnt;
-    const int* off;
-    int2* cand;
-    int kfix;                 // kMode 2: candidate slots per point
-    int* ovf;                 // kMode 2: points with more candidates than kfix
+    CandArgs c;               // kMode 2 uses kfix / ovf
 };
 
 // kMode 0: count the candidates, 1: fill the CSR lists (after the scan), 2: the fixed-slot form
@@ -943,7 +936,7 @@ __global__ __launch_bounds__(256) void sbp_kf_cand_kernel(SbpKfArgs a) {
     if (i >= a.n) return;
     // Every per-point input is read up front and feeds the unconditional arithmetic below, so
     // the loads issue together instead of one flag test (and one memory round trip) at a time.
-    const bool room = !FILL || a.off[i + 1] <= a.cand_cap;
+    const bool room = !FILL || a.c.off[i + 1] <= a.c.cand_cap;
     const bool live = a.valid[i] && !a.bad[i] && !a.found[i];
     const float P[3] = {a.xyz[3 * i], a.xyz[3 * i + 1], a.xyz[3 * i + 2]};
     const float maxd = a.maxd[i], mind = a.mind[i];
@@ -970,11 +963,11 @@ __global__ __launch_bounds__(256) void sbp_kf_cand_kernel(SbpKfArgs a) {
             } else {
                 const float radius = a.th * a.scale[lvl];
                 const uint4 q0 = a.desc[2 * i], q1 = a.desc[2 * i + 1];
-                int2* out = FILL ? a.cand + a.off[i] : kMode == 2 ? a.cand + (size_t)i * a.kfix : nullptr;
+                int2* out = FILL ? a.c.cand + a.c.off[i] : kMode == 2 ? a.c.cand + (size_t)i * a.c.kfix : nullptr;
                 n = features_in_area_wave(
                     a.cur, u, v, radius, lvl - 1, lvl + 1, [](int) { return true; },
                     [&](int i2, int rank) {
-                        if (FILL || (kMode == 2 && rank < a.kfix)) {
+                        if (FILL || (kMode == 2 && rank < a.c.kfix)) {
                             const uint4* d = a.cur.desc + 2 * i2;
                             out[rank] = make_int2(i2, hamming256(q0, q1, d[0], d[1]));
                         }
@@ -982,10 +975,10 @@ __global__ __launch_bounds__(256) void sbp_kf_cand_kernel(SbpKfArgs a) {
             }
         }
     }
-    if (kMode == 0 && (threadIdx.x & 63) == 0) a.cnt[i] = n;
+    if (kMode == 0 && (threadIdx.x & 63) == 0) a.c.cnt[i] = n;
     if (kMode == 2 && (threadIdx.x & 63) == 0) {
-        a.cnt[i] = min(n, a.kfix);
-        if (n > a.kfix) atomicAdd(a.ovf, 1);
+        a.c.cnt[i] = min(n, a.c.kfix);
+        if (n > a.c.kfix) atomicAdd(a.c.ovf, 1);
     }
 }
 

@@ -5,12 +5,11 @@
 #include <map>
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
-#include <functional>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "../../include/orbfe.h"
@@ -71,125 +70,51 @@ __global__ __launch_bounds__(256) void upload_scatter_kernel(UpScatter a) {
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n16; i += gridDim.x * 256) dst[i] = src[i];
     if (blockIdx.x == 0 && threadIdx.x < (nb & 15)) a.dst[s][16 * n16 + threadIdx.x] = a.src[s][16 * n16 + threadIdx.x];
 }
-}  // namespace orbfe
 
-using namespace orbfe;
-
-struct orbfe_matcher {
-    int device = 0;
-    hipStream_t own = nullptr, stream = nullptr;
-    DevBuf fa_k, fa_d, fa_ur, fa_cs, fa_ci, fa_co;  // frame A (+ grid; co: feature lists)
-    DevBuf fb_k, fb_d, fb_ur, fb_cs, fb_ci, fb_co;  // frame B (+ grid; co: feature lists)
-    DevBuf q, r, nq, nr, out;                       // brute force / hamming
-    DevBuf cnt, off, cand;                          // candidate CSR
-    DevBuf s1, s2, s3, s4, s5;                      // resolve scratch / outputs
-    DevBuf m_f0, m_f1, m_f2, m_f3, m_f4, m_u0, m_u1, m_i0, m_i1, m_d;  // per-map-point inputs
-    DevBuf o_u, o_f0, o_f1, o_f2, o_f3, o_i;        // frustum outputs
-    DevBuf scal, done_ctr;
-    DevBuf fu_cs, fu_ci;                            // Fuse: the batch's keyframe grids (orbfe_fuse.hip)
-    DevBuf g_t0, g_t1, g_t2, g_dec, g_chg, g_last, g_bins, g_hist;  // greedy resolver
-    Profiler prof;
-    int last_rounds = 0;  // rounds the most recent greedy resolution took (diagnostics)
-    int capacity_retries = 0;  // calls rerun because the candidates outgrew the buffer
-    bool rounds_on_device = false;  // single-workgroup form: the count sits in g_chg[0]
+// Host transfers of a matcher call go through a pinned staging buffer: the copy into it is a
+// CPU memcpy and the DMA is asynchronous (pageable hipMemcpyAsync stages and blocks per call).
+// A call starts with begin() and ends with sync(), which completes the deferred downloads; the
+// staging memory is reused from call to call.
+struct Staging {
     // ORBFE_ZERO_COPY=0: uploads and downloads as DMA copies (the staging buffer unmapped)
     bool zero_copy_off = std::getenv("ORBFE_ZERO_COPY") && std::strcmp(std::getenv("ORBFE_ZERO_COPY"), "0") == 0;
-    BfKernel bf_kernel = bf_match_fp4_kernel;  // ORBFE_BF_I8=1 at creation: bf_match_kernel
-    // a reference set shared by the whole batch is expanded to FP4 fragments once per call
-    // (bf_expand_kernel) instead of by every workgroup: c3 bf_match 0.159 -> 0.148 ms per 512
-    // frames (profiles/r04/experiments/bf_pre/); ORBFE_BF_PRE=0: every workgroup expands it
-    bool bf_pre = !(std::getenv("ORBFE_BF_PRE") && std::strcmp(std::getenv("ORBFE_BF_PRE"), "0") == 0);
-    // the shared reference set as FP4 fragments (bf_expand_kernel), one buffer per stream the
-    // batch form was called on (calls on different streams may overlap), at most kBfStreams of
-    // them.  Each buffer carries an event recorded behind the last launch that reads it; a call
-    // on another stream takes the least recently used buffer once that event has completed — a
-    // wait on that one buffer's readers, not on the device (a caller creating a stream per call,
-    // or a destroyed stream whose handle is reused, cannot grow the set or find a buffer another
-    // stream still reads; the event stays valid after its stream is destroyed).
-    static constexpr int kBfStreams = 4;
-    struct BfSlot {
-        DevBuf buf;
-        hipEvent_t done = nullptr;  // recorded after the last launch reading buf
-        unsigned long long used = 0;
-    };
-    std::map<hipStream_t, BfSlot> bf_e;
-    unsigned long long bf_e_clock = 0;
-    BfSlot* bf_buffer(hipStream_t s, int* st) {
-        *st = ORBFE_OK;
-        auto it = bf_e.find(s);
-        if (it == bf_e.end() && (int)bf_e.size() >= kBfStreams) {
-            auto lru = bf_e.begin();
-            for (auto i = bf_e.begin(); i != bf_e.end(); ++i)
-                if (i->second.used < lru->second.used) lru = i;
-            if (lru->second.done && hipEventSynchronize(lru->second.done) != hipSuccess) {
-                *st = ORBFE_ERR_HIP;
-                return nullptr;
-            }
-            BfSlot moved = lru->second;  // reuse the allocation and the event for the new stream
-            bf_e.erase(lru);
-            it = bf_e.emplace(s, moved).first;
-        }
-        BfSlot& e = bf_e[s];
-        e.used = ++bf_e_clock;
-        if (!e.done && hipEventCreateWithFlags(&e.done, hipEventDisableTiming) != hipSuccess) {
-            e.done = nullptr;
-            *st = ORBFE_ERR_HIP;
-            return nullptr;
-        }
-        if ((*st = e.buf.ensure((size_t)kBfMaxTiles * 8 * kBfRefs * sizeof(i32x4)))) return nullptr;
-        return &e;
-    }
-
-    ~orbfe_matcher() {
-        for (DevBuf* b : {&fa_k, &fa_d, &fa_ur, &fa_cs, &fa_ci, &fa_co, &fb_k, &fb_d, &fb_ur,
-                          &fb_cs, &fb_ci, &fb_co, &q, &r, &nq, &nr, &out, &cnt, &off, &cand, &s1,
-                          &s2, &s3, &s4, &s5, &m_f0, &m_f1, &m_f2, &m_f3, &m_f4, &m_u0, &m_u1,
-                          &m_i0, &m_i1, &m_d, &o_u, &o_f0, &o_f1, &o_f2, &o_f3, &o_i, &scal,
-                          &g_t0, &g_t1, &g_t2, &g_dec, &g_chg, &g_last, &g_bins, &g_hist, &done_ctr,
-                          &fu_cs, &fu_ci})
-            b->release();
-        for (auto& kv : bf_e) {
-            kv.second.buf.release();
-            if (kv.second.done) hipEventDestroy(kv.second.done);
-        }
-        prof.release();
-        if (own) hipStreamDestroy(own);
-        if (stat_host) hipHostFree(stat_host);
-        if (dn_flag_host) hipHostFree(dn_flag_host);
-        dn_ctr.release();
-    }
-
-    // Host transfers go through a pinned staging buffer: the copy into it is a CPU memcpy and
-    // the DMA is asynchronous (pageable hipMemcpyAsync stages and blocks per call).  Every
-    // host-form entry point starts with begin() and ends with sync(), which completes the
-    // deferred downloads; the staging memory is reused from call to call.
-    // SearchLocalPoints' fast-path tallies: 6 ints of device-mapped pinned memory written by the
-    // accept kernel's last workgroup (null: read back by a D2H copy)
-    int* stat_host = nullptr;
-    int* stat_dev = nullptr;
+    hipStream_t stream = nullptr;  // the call's stream
+    bool may_wait = false;         // the call may wait on the done word (no profiler events)
     uint8_t* pin = nullptr;
     uint8_t* pin_dev = nullptr;  // the staging buffer's device-mapped address (null: DMA path)
     size_t pin_cap = 0, pin_used = 0;
-    struct DnSeg { const uint8_t* src; uint8_t* dst; size_t bytes; };
-    std::vector<DnSeg> dnq;  // downloads not yet gathered (zero-copy path)
-    std::vector<int32_t> init_neg;  // host-side -1 fill staged as an upload (SearchByBoW)
     std::vector<uint8_t*> pin_retired;  // outgrown buffers, freed once the stream is idle
-    struct Pending { void* dst; const uint8_t* src; size_t bytes; };
-    std::vector<Pending> pend;
-
     struct UpSeg { uint8_t* dst; size_t off; size_t bytes; };
     std::vector<UpSeg> upq;  // staged uploads not yet copied
     DevBuf d_stage;
+    struct DnSeg { const uint8_t* src; uint8_t* dst; size_t bytes; };
+    std::vector<DnSeg> dnq;  // downloads not yet gathered (zero-copy path)
+    struct Pending { void* dst; const uint8_t* src; size_t bytes; };
+    std::vector<Pending> pend;  // downloads sync() hands to the caller
+    // The done word of the download gather (device-mapped pinned memory) and its counter.
+    int* dn_flag_host = nullptr;
+    int* dn_flag_dev = nullptr;
+    int dn_seq = 0;
+    DevBuf dn_ctr;
 
-    void begin() {
+    ~Staging() {
+        for (uint8_t* q : pin_retired) hipHostFree(q);
+        if (pin) hipHostFree(pin);
+        if (dn_flag_host) hipHostFree(dn_flag_host);
+    }
+    void begin(hipStream_t s, bool wait_ok) {
         for (uint8_t* q : pin_retired) hipHostFree(q);
         pin_retired.clear();
+        stream = s;
+        may_wait = wait_ok;
         pin_used = 0;
         pend.clear();
         upq.clear();
         dnq.clear();
-        cand_check = false;
     }
+    bool idle() const { return pend.empty() && dnq.empty(); }  // no download is waiting for sync()
+    // The device-mapped address of staged bytes (null: the staging buffer is not mapped).
+    uint8_t* dev(const uint8_t* q) const { return pin_dev ? pin_dev + (q - pin) : nullptr; }
     // Copies the staged uploads to their device buffers (call before any kernel reads them).
     // With a device-mapped staging buffer the scatter kernel reads the pinned bytes itself
     // (zero-copy: no DMA in front of it); otherwise one H2D copy into d_stage first.
@@ -250,9 +175,10 @@ struct orbfe_matcher {
         upq.push_back(UpSeg{b.as<uint8_t>(), (size_t)(q - pin), bytes});
         return ORBFE_OK;
     }
-    int down(void* dst, const DevBuf& b, size_t bytes) { return down_ptr(dst, b.p, bytes); }
-    int down_ptr(void* dst, const void* src, size_t bytes) {
-        if (!bytes) return ORBFE_OK;
+    // A download that stays in the staging buffer: *at holds the bytes once sync() has waited
+    // (before it hands anything to the caller), until the next begin().
+    template <class T>
+    int down_staged(const void* src, size_t bytes, const T** at) {
         uint8_t* q = stage(bytes);
         if (!q) return ORBFE_ERR_NOMEM;
         if (pin_dev) {  // gathered at sync() by one kernel
@@ -260,18 +186,21 @@ struct orbfe_matcher {
         } else {
             ORBFE_HIP(hipMemcpyAsync(q, src, bytes, hipMemcpyDeviceToHost, stream));
         }
-        pend.push_back(Pending{dst, q, bytes});
+        *at = reinterpret_cast<const T*>(q);
         return ORBFE_OK;
     }
-    // The done word of the download gather (device-mapped pinned memory) and its counter.
-    int* dn_flag_host = nullptr;
-    int* dn_flag_dev = nullptr;
-    int dn_seq = 0;
-    DevBuf dn_ctr;
+    int down(void* dst, const DevBuf& b, size_t bytes) { return down_ptr(dst, b.p, bytes); }
+    int down_ptr(void* dst, const void* src, size_t bytes) {
+        if (!bytes) return ORBFE_OK;
+        const uint8_t* q;
+        const int st = down_staged(src, bytes, &q);
+        if (st == ORBFE_OK) pend.push_back(Pending{dst, q, bytes});
+        return st;
+    }
     // *waited = true: the last launch carries the done word and the host waited on it
-    int gather(bool* waited = nullptr) {
-        if (waited) *waited = false;
-        if (waited && !dnq.empty() && !prof.on && !dn_flag_host) {
+    int gather(bool* waited) {
+        *waited = false;
+        if (!dnq.empty() && may_wait && !dn_flag_host) {
             void* q = nullptr;
             void* dq = nullptr;
             if (dn_ctr.ensure(64) == ORBFE_OK && hipMemsetAsync(dn_ctr.p, 0, 64, stream) == hipSuccess &&
@@ -285,7 +214,8 @@ struct orbfe_matcher {
                 }
             }
         }
-        const bool flagged = waited && !dnq.empty() && !prof.on && dn_flag_host;
+        const bool flagged = !dnq.empty() && may_wait && dn_flag_host;
+        const int before = flagged ? *dn_flag_host : 0;  // an earlier launch's seq
         for (size_t b = 0; b < dnq.size(); b += kMaxUpSeg) {
             UpScatter a;
             a.n = (int)std::min<size_t>(kMaxUpSeg, dnq.size() - b);
@@ -304,42 +234,136 @@ struct orbfe_matcher {
         dnq.clear();
         ORBFE_HIP(hipGetLastError());
         if (flagged) {
-            // the stream's earlier kernels finished before the gather ran; bounded wait, then the
-            // stream synchronisation (which also reports a failed kernel)
-            const volatile int* fl = dn_flag_host;
-            const auto t0 = std::chrono::steady_clock::now();
-            while (*fl != dn_seq) {
-                if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(2000)) {
-                    ORBFE_HIP(hipStreamSynchronize(stream));
-                    if (*fl != dn_seq) return ORBFE_ERR_HIP;
-                    break;
-                }
-                __builtin_ia32_pause();
+            // the stream's earlier kernels finished before the gather ran
+            const int st = wait_words(dn_flag_host, 1, before, stream, 2000);
+            if (st) {  // a gather that did not finish may have left its count behind
+                hipMemsetAsync(dn_ctr.p, 0, 64, stream);
+                return st;
             }
             *waited = true;
         }
         return ORBFE_OK;
     }
-    int sync() {
+    // Completes the call's transfers.  check() runs once the downloads are in the staging buffer
+    // and before any reaches the caller: a status from it drops them.
+    template <class Check>
+    int sync(Check&& check) {
         int st;
         if ((st = flush())) return st;
         bool waited = false;
         if ((st = gather(&waited))) return st;
         if (!waited) ORBFE_HIP(hipStreamSynchronize(stream));
-        if (cand_check) {  // csr_async: the candidates must have fit before results count
-            int total = 0;
-            for (const Pending& d : pend)
-                if (d.dst == &cand_total) std::memcpy(&total, d.src, sizeof(int));
-            cand_check = false;
-            if ((size_t)total > cand_cap_used) {
-                pend.clear();
-                cand_need = (size_t)total;
-                return ORBFE_ERR_CAPACITY;
-            }
+        if ((st = check())) {
+            pend.clear();
+            return st;
         }
         for (const Pending& d : pend) std::memcpy(d.dst, d.src, d.bytes);
         pend.clear();
         return ORBFE_OK;
+    }
+};
+
+// What the rerun of a call does differently (guarded() below is the one place that reruns).
+struct Rerun {
+    bool again = false;     // set by the attempt that asks for the rerun
+    bool no_fixed = false;  // a point had more candidates than the fixed slots: the CSR path
+    size_t cand_cap = 0;    // a bounded fill did not fit: its reported total
+};
+}  // namespace orbfe
+
+using namespace orbfe;
+
+struct orbfe_matcher {
+    int device = 0;
+    hipStream_t own = nullptr, stream = nullptr;
+    // scratch; every buffer frees itself with the matcher
+    DevBuf fa_k, fa_d, fa_ur, fa_cs, fa_ci, fa_co;  // frame A (+ grid; co: feature lists)
+    DevBuf fb_k, fb_d, fb_ur, fb_cs, fb_ci, fb_co;  // frame B (+ grid; co: feature lists)
+    DevBuf q, r, nq, nr, out;                       // brute force / hamming
+    DevBuf s1, s2, s3, s4, s5;                      // resolve scratch / outputs
+    DevBuf m_f0, m_f1, m_f2, m_f3, m_f4, m_u0, m_u1, m_i0, m_i1, m_d;  // per-map-point inputs
+    DevBuf o_u, o_f0, o_f1, o_f2, o_f3, o_i;        // frustum outputs
+    DevBuf scal, done_ctr;
+    DevBuf fu_cs, fu_ci;                            // Fuse: the batch's keyframe grids (orbfe_fuse.hip)
+    DevBuf g_t0, g_t1, g_t2, g_dec, g_chg, g_last, g_bins, g_hist;  // greedy resolver
+    Profiler prof;
+    int last_rounds = 0;  // rounds the most recent greedy resolution took (diagnostics)
+    int capacity_retries = 0;  // calls rerun because the candidates outgrew the buffer
+    bool rounds_on_device = false;  // single-workgroup form: the count sits in g_chg[0]
+    Rerun rerun;
+    BfKernel bf_kernel = bf_match_fp4_kernel;  // ORBFE_BF_I8=1 at creation: bf_match_kernel
+    // a reference set shared by the whole batch is expanded to FP4 fragments once per call
+    // (bf_expand_kernel) instead of by every workgroup: c3 bf_match 0.159 -> 0.148 ms per 512
+    // frames (profiles/r04/experiments/bf_pre/); ORBFE_BF_PRE=0: every workgroup expands it
+    bool bf_pre = !(std::getenv("ORBFE_BF_PRE") && std::strcmp(std::getenv("ORBFE_BF_PRE"), "0") == 0);
+    // the shared reference set as FP4 fragments (bf_expand_kernel), one buffer per stream the
+    // batch form was called on (calls on different streams may overlap), at most kBfStreams of
+    // them.  Each buffer carries an event recorded behind the last launch that reads it; a call
+    // on another stream takes the least recently used buffer once that event has completed — a
+    // wait on that one buffer's readers, not on the device (a caller creating a stream per call,
+    // or a destroyed stream whose handle is reused, cannot grow the set or find a buffer another
+    // stream still reads; the event stays valid after its stream is destroyed).
+    static constexpr int kBfStreams = 4;
+    struct BfSlot {
+        DevBuf buf;
+        hipEvent_t done = nullptr;  // recorded after the last launch reading buf
+        unsigned long long used = 0;
+    };
+    std::map<hipStream_t, BfSlot> bf_e;
+    unsigned long long bf_e_clock = 0;
+    BfSlot* bf_buffer(hipStream_t s, int* st) {
+        *st = ORBFE_OK;
+        auto it = bf_e.find(s);
+        if (it == bf_e.end() && (int)bf_e.size() >= kBfStreams) {
+            auto lru = bf_e.begin();
+            for (auto i = bf_e.begin(); i != bf_e.end(); ++i)
+                if (i->second.used < lru->second.used) lru = i;
+            if (lru->second.done && hipEventSynchronize(lru->second.done) != hipSuccess) {
+                *st = ORBFE_ERR_HIP;
+                return nullptr;
+            }
+            BfSlot moved = std::move(lru->second);  // reuse the allocation and the event for the new stream
+            bf_e.erase(lru);
+            it = bf_e.emplace(s, std::move(moved)).first;
+        }
+        BfSlot& e = bf_e[s];
+        e.used = ++bf_e_clock;
+        if (!e.done && hipEventCreateWithFlags(&e.done, hipEventDisableTiming) != hipSuccess) {
+            e.done = nullptr;
+            *st = ORBFE_ERR_HIP;
+            return nullptr;
+        }
+        if ((*st = e.buf.ensure((size_t)kBfMaxTiles * 8 * kBfRefs * sizeof(i32x4)))) return nullptr;
+        return &e;
+    }
+
+    ~orbfe_matcher() {
+        for (auto& kv : bf_e)
+            if (kv.second.done) hipEventDestroy(kv.second.done);
+        prof.release();
+        if (own) hipStreamDestroy(own);
+        if (stat_host) hipHostFree(stat_host);
+    }
+
+    // SearchLocalPoints' fast-path tallies: 6 ints of device-mapped pinned memory written by the
+    // accept kernel's last workgroup (null: read back by a D2H copy)
+    int* stat_host = nullptr;
+    int* stat_dev = nullptr;
+    std::vector<int32_t> init_neg;  // host-side -1 fill staged as an upload (SearchByBoW)
+
+    // The call's host transfers (Staging).  sync() lets the candidate builder check its words
+    // before a result reaches the caller.
+    Staging stg;
+    void begin() {
+        stg.begin(stream, !prof.on);
+        cl.total = cl.ovf = nullptr;
+    }
+    int flush() { return stg.flush(); }
+    int up(DevBuf& b, const void* src, size_t bytes) { return stg.up(b, src, bytes); }
+    int down(void* dst, const DevBuf& b, size_t bytes) { return stg.down(dst, b, bytes); }
+    int down_ptr(void* dst, const void* src, size_t bytes) { return stg.down_ptr(dst, src, bytes); }
+    int sync() {
+        return stg.sync([this]() { return cand_check(); });
     }
 
     // Frame::AssignFeaturesToGrid of one frame of v->n keypoints at k (grid_kernel).
@@ -383,63 +407,76 @@ struct orbfe_matcher {
         return ORBFE_OK;
     }
 
-    // count -> scan -> fill for a candidate kernel family; returns the candidate total.
-    // per_block: queries per 256-thread block (256: thread per query, 4: wave per query).
-    // Without a host round trip: the fill is bounded by a grow-only capacity and the true total
-    // is checked by sync() (ORBFE_ERR_CAPACITY: the caller grows to cand_need and runs again).
-    int cand_total = 0;          // written by the deferred download of off[nq]
-    size_t cand_cap_used = 0;
-    bool cand_check = false;
-    size_t cand_need = 0;
-    template <class Args, class CountK, class FillK>
-    int csr_async(Args& a, int nq, CountK ck, FillK fk, int per_block) {
+    // The candidate builder: the lists of a *_cand_kernel family (their CandArgs) in one of two
+    // forms, neither with a host round trip.  The word that says whether the lists are whole
+    // (the CSR total, the fixed slots' overflow count) comes back with the call's next sync(),
+    // which checks it before any result reaches the caller: ORBFE_ERR_CAPACITY then, with
+    // `rerun` saying what the next attempt changes.
+    struct CandLists {
+        DevBuf cnt, off, cand;
+        size_t cap = 0;              // entries the fill in flight could write
+        int kfix = 0;                // > 0: fixed slots per query
+        const int* total = nullptr;  // bounded fill: off[nq], staged (null: nothing to check)
+        const int* ovf = nullptr;    // fixed slots: queries with more candidates than kfix
+    } cl;
+    // count -> scan -> fill, bounded by a grow-only capacity of at least per_query entries per
+    // query (lists ending past it are not filled and the resolvers read them as empty).
+    // per_block: queries per 256-thread block (4: a wave per query).
+    template <class Args>
+    int cand_bounded(Args& a, int nq, int per_query, void (*count)(Args), void (*fill)(Args),
+                     int per_block = 4) {
         int st;
-        if ((st = cnt.ensure(std::max(nq, 1) * sizeof(int)))) return st;
-        if ((st = off.ensure((nq + 1) * sizeof(int)))) return st;
-        const size_t cap = std::max(std::max(cand.bytes / sizeof(int2), (size_t)nq * 64), cand_need);
-        if ((st = cand.ensure(std::max<size_t>(cap, 1) * sizeof(int2)))) return st;
-        a.cnt = cnt.as<int>();
-        a.off = off.as<int>();
-        a.cand = cand.as<int2>();
-        a.cand_cap = (long long)cap;
+        if ((st = cl.cnt.ensure(std::max(nq, 1) * sizeof(int)))) return st;
+        if ((st = cl.off.ensure((nq + 1) * sizeof(int)))) return st;
+        const size_t cap = std::max({cl.cand.bytes / sizeof(int2), (size_t)per_query * std::max(nq, 1),
+                                     rerun.cand_cap});
+        if ((st = cl.cand.ensure(cap * sizeof(int2)))) return st;
+        a.c = CandArgs{(long long)cap, cl.cnt.as<int>(), cl.off.as<int>(), cl.cand.as<int2>(), 0, nullptr};
         if ((st = flush())) return st;
         const int blocks = std::max(1, (nq + per_block - 1) / per_block);
-        hipLaunchKernelGGL(ck, dim3(blocks), dim3(256), 0, stream, a);
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, stream, cnt.as<int>(), nq, off.as<int>());
-        hipLaunchKernelGGL(fk, dim3(blocks), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(count, dim3(blocks), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, stream, cl.cnt.as<int>(), nq, cl.off.as<int>());
+        hipLaunchKernelGGL(fill, dim3(blocks), dim3(256), 0, stream, a);
         ORBFE_HIP(hipGetLastError());
-        if ((st = down_ptr(&cand_total, off.as<int>() + nq, sizeof(int)))) return st;
-        cand_cap_used = cap;
-        cand_check = true;
-        return ORBFE_OK;
+        cl.cap = cap;
+        cl.kfix = 0;
+        return stg.down_staged(cl.off.as<int>() + nq, sizeof(int), &cl.total);
     }
-
-    template <class Args, class CountK, class FillK>
-    int csr(Args& a, int nq, CountK ck, FillK fk, int& total, int per_block = 256) {
+    // One launch: the first kfix candidates of query i at i * kfix (a wave per query); *ovf_word
+    // (zero before the launch) counts the queries that have more.
+    template <class Args>
+    int cand_fixed(Args& a, int nq, int kfix, int* ovf_word, void (*fixed)(Args)) {
         int st;
-        if ((st = cnt.ensure(std::max(nq, 1) * sizeof(int)))) return st;
-        if ((st = off.ensure((nq + 1) * sizeof(int)))) return st;
-        a.cnt = cnt.as<int>();
-        a.off = off.as<int>();
+        if ((st = cl.cnt.ensure((size_t)nq * sizeof(int)))) return st;
+        if ((st = cl.cand.ensure((size_t)nq * kfix * sizeof(int2)))) return st;
+        a.c = CandArgs{LLONG_MAX, cl.cnt.as<int>(), nullptr, cl.cand.as<int2>(), kfix, ovf_word};
         if ((st = flush())) return st;
-        const int blocks = std::max(1, (nq + per_block - 1) / per_block);
-        hipLaunchKernelGGL(ck, dim3(blocks), dim3(256), 0, stream, a);
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, stream, cnt.as<int>(), nq, off.as<int>());
-        ORBFE_HIP(hipMemcpyAsync(&total, off.as<int>() + nq, sizeof(int), hipMemcpyDeviceToHost, stream));
-        ORBFE_HIP(hipStreamSynchronize(stream));
-        if ((st = cand.ensure(std::max(total, 1) * sizeof(int2)))) return st;
-        a.cand = cand.as<int2>();
-        hipLaunchKernelGGL(fk, dim3(blocks), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(fixed, dim3((nq + 3) / 4), dim3(256), 0, stream, a);
         ORBFE_HIP(hipGetLastError());
-        return ORBFE_OK;
+        cl.kfix = kfix;
+        return stg.down_staged(ovf_word, sizeof(int), &cl.ovf);
+    }
+    int cand_check() {
+        const int* total = cl.total;
+        const int* ovf = cl.ovf;
+        cl.total = cl.ovf = nullptr;
+        if (ovf && *ovf > 0) {
+            rerun.no_fixed = true;
+        } else if (total && (size_t)*total > cl.cap) {
+            rerun.cand_cap = (size_t)*total;
+        } else {
+            return ORBFE_OK;
+        }
+        rerun.again = true;
+        return ORBFE_ERR_CAPACITY;
     }
 
-    // Exact parallel resolution of the greedy assignment (orbfe_greedy.hip).  `g` carries the
-    // problem (m points, nkp slots, CSR candidates, decision mode, slot arrays fmp/fobs that
-    // hold the state before the call and receive the result); the scratch is owned here.
-    // `total` / `cap` (optional): a candidate total that is only known on the device; it is
-    // checked at the first synchronization, before any slot is written (ORBFE_ERR_CAPACITY).
-    int greedy(GreedyArgs& g, int first_batch = 8, const int* total = nullptr, size_t cap = 0) {
+    // Exact parallel resolution of the greedy assignment (orbfe_greedy.hip) over the candidate
+    // builder's lists.  `g` carries the problem (m points, nkp slots, decision mode, slot arrays
+    // fmp/fobs that hold the state before the call and receive the result); the scratch is owned
+    // here.  in_place: the slot arrays are the caller's own, so the candidates are checked (at
+    // the first synchronisation of the rounds) before any slot is written.
+    int greedy(GreedyArgs& g, bool in_place = false) {
         int st;
         const int M = g.m, N = g.nkp;
         if ((st = g_t0.ensure(std::max(N, 1) * sizeof(int)))) return st;
@@ -452,6 +489,11 @@ struct orbfe_matcher {
         if ((st = g_hist.ensure(32 * sizeof(int)))) return st;
         if ((st = scal.ensure(16))) return st;
         if ((st = flush())) return st;
+        g.off = cl.off.as<int>();
+        g.cand = cl.cand.as<int2>();
+        g.kfix = cl.kfix;
+        g.fcnt = cl.kfix ? cl.cnt.as<int>() : nullptr;
+        g.cand_cap = cl.kfix ? LLONG_MAX : (long long)cl.cap;  // lists past it were not filled
         g.T[0] = g_t0.as<int>();
         g.T[1] = g_t1.as<int>();
         g.T[2] = g_t2.as<int>();
@@ -461,10 +503,7 @@ struct orbfe_matcher {
         g.bins = g_bins.as<int>();
         g.hist = g_hist.as<int>();
         g.nm = scal.as<int>();
-        // the fill's capacity: csr() sized it to the exact total; csr_async() and a device
-        // total (`total`) bound it, and lists past it were not filled
-        g.cand_cap = total ? (long long)cap : cand_check ? (long long)cand_cap_used : LLONG_MAX;
-        if (M <= kGreedySmallMax && N <= kGreedySmallSlots && !total) {  // one workgroup
+        if (M <= kGreedySmallMax && N <= kGreedySmallSlots && !in_place) {  // one workgroup
             hipLaunchKernelGGL(greedy_small_kernel, dim3(1), dim3(kGreedySmallBlock),
                                (size_t)4 * std::max(N, 1) * sizeof(int), stream, g);
             ORBFE_HIP(hipGetLastError());
@@ -478,18 +517,17 @@ struct orbfe_matcher {
         // (greedy_init_kernel also clears the change flags: blocks cover max(M, N, 32) >= M + 2)
         hipLaunchKernelGGL(greedy_init_kernel, dim3(blocks), dim3(kGreedyBlock), 0, stream, g);
         // rounds in batches; a round after a change-free round exits at once
-        int r = 0, batch = first_batch;
+        int r = 0, batch = 8;
         std::vector<int> chg_h;
         while (true) {
             const int r0 = r;
             for (int b = 0; b < batch && r <= M; ++b, ++r)
                 hipLaunchKernelGGL(greedy_round_kernel<false>, dim3(blocks), dim3(kGreedyBlock), 0, stream, g, r);
-            // the batch's change flags through the staging gather and its done word (sync()
-            // also checks an asynchronous candidate fill's capacity first)
+            // the batch's change flags through the staging gather and its done word (the first
+            // sync() also checks the candidates)
             chg_h.assign(r - r0, 0);
             if ((st = down_ptr(chg_h.data(), g.chg + r0, (size_t)(r - r0) * sizeof(int)))) return st;
             if ((st = sync())) return st;
-            if (total && (size_t)*total > cap) return ORBFE_ERR_CAPACITY;
             const auto z = std::find(chg_h.begin(), chg_h.end(), 0);
             if (z != chg_h.end()) {
                 last_rounds = r0 + (int)(z - chg_h.begin()) + 1;  // the change-free round included
@@ -523,25 +561,94 @@ void rigid(const float* T, const float* p, float* out) {
     for (int r = 0; r < 3; ++r)
         out[r] = ((T[4 * r] * p[0] + T[4 * r + 1] * p[1]) + T[4 * r + 2] * p[2]) + T[4 * r + 3];
 }
+// The pose, pinhole intrinsics and image bounds of a projection kernel's arguments.
+template <class A>
+void put_view(A& a, const float* tcw, const orbfe_camera* cam, float min_x, float max_x,
+              float min_y, float max_y) {
+    std::memcpy(a.T, tcw, sizeof(a.T));
+    a.fx = cam->fx;
+    a.fy = cam->fy;
+    a.cx = cam->cx;
+    a.cy = cam->cy;
+    a.minx = min_x;
+    a.maxx = max_x;
+    a.miny = min_y;
+    a.maxy = max_y;
+}
+// The pose and intrinsics part of FrustumArgs; the point arrays and outputs are the caller's.
+FrustumArgs frustum_view(const float* tcw, const orbfe_camera* cam, float min_x, float max_x,
+                         float min_y, float max_y, float log_scale_factor,
+                         float viewing_cos_limit) {
+    FrustumArgs a{};
+    put_view(a, tcw, cam, min_x, max_x, min_y, max_y);
+    camera_center(tcw, a.ow);
+    a.bf = cam->bf;
+    a.log_scale = log_scale_factor;
+    a.cos_limit = viewing_cos_limit;
+    return a;
+}
+// Every entry point runs through here, and this loop is the one place that runs a call again:
+// an attempt that finds its candidates cut short (cand_check(), or the fused path's tallies)
+// records in m->rerun what the next attempt does differently and sets `again`.
 template <class F>
 int guarded(orbfe_matcher* m, F&& f) {
     if (!m) return ORBFE_ERR_ARG;
     try {
         DeviceGuard dg(m->device);
-        m->begin();
-        const size_t need0 = m->cand_need;
-        int st = f();
-        if (st == ORBFE_ERR_CAPACITY && m->cand_need > need0) {  // candidates outgrew the bound
-            ++m->capacity_retries;
+        m->rerun = Rerun{};
+        for (int run = 0;; ++run) {
             m->begin();
-            st = f();
+            m->rerun.again = false;
+            const int st = f();
+            if (!m->rerun.again) return st;
+            if (run == 2) return ORBFE_ERR_HIP;  // cannot happen: each change is made once
+            ++m->capacity_retries;
         }
-        return st;
     } catch (const std::bad_alloc&) {
         return ORBFE_ERR_NOMEM;
     } catch (...) {
         return ORBFE_ERR_HIP;
     }
+}
+// The three host forms of SearchByProjection (local map, last frame, keyframe) after their own
+// uploads: the slots, the scale factors and the frame go up with them in one scatter, `fill`
+// sets the form's candidate arguments and what differs in GreedyArgs (mode, nnratio or
+// max_dist, nobs, check_ori, q_angle, ids), the candidates take the fixed slots unless a point
+// overflowed them in an earlier attempt, and the greedy resolution's slots and {nmatches,
+// status} come down.  frame_mp_obs null: a form without observation counts (any held slot
+// blocks).  Returns the status word.
+template <class Args, class Fill>
+int sbp_search(orbfe_matcher* m, const orbfe_frame_view* cur, int nq, int kfix,
+               void (*count)(Args), void (*fillk)(Args), void (*fixed)(Args), int32_t* frame_mp,
+               int32_t* frame_mp_obs, int32_t* nmatches, Fill&& fill) {
+    int st;
+    const int N = cur->n;
+    const int32_t zero[4] = {0, 0, 0, 0};  // nmatches, status, overflow
+    if ((st = m->up(m->scal, zero, sizeof(zero)))) return st;
+    if ((st = m->up(m->s1, frame_mp, (size_t)N * 4))) return st;
+    if (frame_mp_obs && (st = m->up(m->s2, frame_mp_obs, (size_t)N * 4))) return st;
+    if ((st = m->up(m->m_f4, cur->scale_factors, (size_t)cur->nlevels * 4))) return st;
+    DevFrame F;
+    if ((st = m->frame(cur, false, F))) return st;
+    Args a{};
+    GreedyArgs g{};
+    fill(a, g, F);
+    if (N > 0 && nq > 0 && !m->rerun.no_fixed) st = m->cand_fixed(a, nq, kfix, m->scal.as<int>() + 2, fixed);
+    else st = m->cand_bounded(a, nq, 64, count, fillk);
+    if (st) return st;
+    g.m = nq;
+    g.nkp = N;
+    g.fmp0 = g.fmp = m->s1.as<int>();
+    g.fobs0 = g.fobs = frame_mp_obs ? m->s2.as<int>() : nullptr;
+    g.k = F.k;
+    if ((st = m->greedy(g))) return st;
+    if ((st = m->down(frame_mp, m->s1, (size_t)N * 4))) return st;
+    if (frame_mp_obs && (st = m->down(frame_mp_obs, m->s2, (size_t)N * 4))) return st;
+    int res[2] = {0, 0};  // {nmatches, status}
+    if ((st = m->down(res, m->scal, sizeof(res)))) return st;
+    if ((st = m->sync())) return st;
+    *nmatches = res[0];
+    return res[1];
 }
 // SearchLocalPoints' fast path (frames of <= kSbpFixKp keypoints): the grid, ONE kernel for
 // isInFrustum (kPre: its outputs already resident) + candidates (fixed per-point slots) + the
@@ -549,8 +656,8 @@ int guarded(orbfe_matcher* m, F&& f) {
 // one is a no-op), the acceptances whose last workgroup writes the slots and the tallies, and ONE
 // synchronisation reading host[0..5] = {nmatches, nToMatch, status, overflow, last round's
 // changes, rounds}.  A point with more than kSbpFix candidates or a map that needs more rounds
-// (rare: host[3] or host[4] set) has the slots saved by the fused kernel restored, and the caller
-// reruns the call through the CSR path.
+// (rare: host[3] or host[4] set) has the slots saved by the fused kernel restored and asks for
+// the rerun without the fixed slots (ORBFE_ERR_CAPACITY): the callers' CSR path.
 template <bool kPre>
 int sbp_local_fast(orbfe_matcher* m, const orbfe_frame_view* frame, const FrustumArgs& fr,
                    const SbpMps& mp, float nnratio, float th, const int32_t* d_nobs,
@@ -560,8 +667,8 @@ int sbp_local_fast(orbfe_matcher* m, const orbfe_frame_view* frame, const Frustu
     const int M = mp.m, N = frame->n;
     constexpr int kBlindRounds = 6;
     const int fblocks = (std::max(std::max(M, N), kBlindRounds + 1) + kSbpPts - 1) / kSbpPts;
-    if ((st = m->cand.ensure((size_t)M * kSbpFix * sizeof(int2)))) return st;
-    if ((st = m->cnt.ensure((size_t)M * sizeof(int)))) return st;
+    if ((st = m->cl.cand.ensure((size_t)M * kSbpFix * sizeof(int2)))) return st;
+    if ((st = m->cl.cnt.ensure((size_t)M * sizeof(int)))) return st;
     if ((st = m->s1.ensure(std::max(N, 1) * sizeof(int)))) return st;
     if ((st = m->s2.ensure(std::max(N, 1) * sizeof(int)))) return st;
     if ((st = m->s3.ensure((size_t)3 * fblocks * sizeof(int)))) return st;
@@ -581,8 +688,8 @@ int sbp_local_fast(orbfe_matcher* m, const orbfe_frame_view* frame, const Frustu
     a.mp = mp;
     a.th = th;
     a.nlevels = frame->nlevels;
-    a.cnt = m->cnt.as<int>();
-    a.cand = m->cand.as<int2>();
+    a.c.cnt = m->cl.cnt.as<int>();
+    a.c.cand = m->cl.cand.as<int2>();
     for (int l = 0; l < frame->nlevels; ++l) fu.scalev[l] = frame->scale_factors[l];
     fu.blk = m->s3.as<int>();
     fu.rounds = kBlindRounds;
@@ -592,8 +699,8 @@ int sbp_local_fast(orbfe_matcher* m, const orbfe_frame_view* frame, const Frustu
     g.mode = kGreedyLocal;
     g.nnratio = nnratio;
     g.kfix = kSbpFix;
-    g.fcnt = m->cnt.as<int>();
-    g.cand = m->cand.as<int2>();
+    g.fcnt = m->cl.cnt.as<int>();
+    g.cand = m->cl.cand.as<int2>();
     g.cand_cap = LLONG_MAX;
     g.nobs = d_nobs;
     g.fmp0 = g.fmp = d_frame_mp;
@@ -613,7 +720,7 @@ int sbp_local_fast(orbfe_matcher* m, const orbfe_frame_view* frame, const Frustu
     g.nblk = fblocks;
     g.stats = m->scal.as<int>();
     g.conv_round = kBlindRounds - 1;
-    if (!m->stat_host && !m->zero_copy_off) {
+    if (!m->stat_host && !m->stg.zero_copy_off) {
         void* q = nullptr;
         void* dq = nullptr;
         if (hipHostMalloc(&q, 64, hipHostMallocDefault) == hipSuccess) {
@@ -644,15 +751,8 @@ int sbp_local_fast(orbfe_matcher* m, const orbfe_frame_view* frame, const Frustu
         ORBFE_HIP(hipMemcpyAsync(host, m->scal.p, 6 * sizeof(int), hipMemcpyDeviceToHost, m->stream));
     if (m->stat_host && !m->prof.on) {
         // the accept kernel's last workgroup releases the slots and then writes stat_host[4]
-        // (-1 until then): wait on it; past 2 ms synchronise the stream (reports a failed kernel)
-        const auto t0 = std::chrono::steady_clock::now();
-        while (__atomic_load_n(&m->stat_host[4], __ATOMIC_ACQUIRE) == -1) {
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(2000)) {
-                ORBFE_HIP(hipStreamSynchronize(m->stream));
-                break;
-            }
-            __builtin_ia32_pause();
-        }
+        // (-1 until then): wait on it
+        if ((st = wait_words(m->stat_host + 4, 1, -1, m->stream, 2000))) return st;
     } else {
         ORBFE_HIP(hipStreamSynchronize(m->stream));
     }
@@ -662,11 +762,49 @@ int sbp_local_fast(orbfe_matcher* m, const orbfe_frame_view* frame, const Frustu
         m->last_rounds = host[5];
         return ORBFE_OK;
     }
-    // restore the frame's slots; the caller takes the CSR path
+    // restore the frame's slots; the rerun takes the CSR path
     ORBFE_HIP(hipMemcpyAsync(d_frame_mp, m->s1.p, (size_t)N * 4, hipMemcpyDeviceToDevice, m->stream));
     ORBFE_HIP(hipMemcpyAsync(d_frame_mp_obs, m->s2.p, (size_t)N * 4, hipMemcpyDeviceToDevice, m->stream));
-    ++m->capacity_retries;
-    return ORBFE_OK;
+    m->rerun.no_fixed = m->rerun.again = true;
+    return ORBFE_ERR_CAPACITY;
+}
+// The CSR path of the two device forms of SearchByProjection(Frame&, local map points): they
+// differ in who produced mp's fields (fr non-null: frustum_kernel, launched here).  The slots
+// are the caller's device arrays, written in place once the candidates are known to fit;
+// res = {nmatches, nToMatch, status}.
+int sbp_local_device_fallback(orbfe_matcher* m, const orbfe_frame_view* frame, const FrustumArgs* fr,
+                         const SbpMps& mp, float nnratio, float th, const int32_t* d_mp_ids,
+                         int32_t* d_frame_mp, int32_t* d_frame_mp_obs, int res[3]) {
+    int st;
+    // (the fast path passes mvScaleFactors in its kernel arguments; this one reads them from
+    // device memory)
+    if ((st = m->m_f4.ensure(std::max<size_t>(16, (size_t)frame->nlevels * 4)))) return st;
+    ORBFE_HIP(hipMemcpyAsync(m->m_f4.p, frame->scale_factors, (size_t)frame->nlevels * 4,
+                             hipMemcpyHostToDevice, m->stream));
+    ORBFE_HIP(hipMemsetAsync(m->scal.p, 0, 16, m->stream));  // nmatches, nToMatch, status
+    if (fr && fr->n)
+        hipLaunchKernelGGL(frustum_kernel, dim3((fr->n + 255) / 256), dim3(256), 0, m->stream, *fr);
+    SbpLocalArgs a;
+    if ((st = m->frame_device(frame, a.f))) return st;  // AssignFeaturesToGrid
+    a.mp = mp;
+    a.scale = m->m_f4.as<float>();
+    a.th = th;
+    a.nlevels = frame->nlevels;
+    a.status = m->scal.as<int>() + 2;  // a predicted level outside the pyramid
+    // 16 per point to start
+    if ((st = m->cand_bounded(a, mp.m, 16, sbp_local_cand_kernel<0>, sbp_local_cand_kernel<1>))) return st;
+    GreedyArgs g{};
+    g.m = mp.m;
+    g.nkp = frame->n;
+    g.mode = kGreedyLocal;
+    g.nnratio = nnratio;
+    g.nobs = mp.nobs;
+    g.fmp0 = g.fmp = d_frame_mp;
+    g.fobs0 = g.fobs = d_frame_mp_obs;
+    g.ids = d_mp_ids;
+    if ((st = m->greedy(g, true))) return st;
+    if ((st = m->down(res, m->scal, 3 * sizeof(int)))) return st;
+    return m->sync();
 }
 }  // namespace
 
@@ -831,9 +969,7 @@ int orbfe_search_for_initialization(orbfe_matcher* m, float nnratio, int check_o
                                     int32_t* nmatches) {
     if (!frame_ok(f1) || !frame_ok(f2) || !nmatches || (f1->n && (!prev_matched || !matches12)))
         return ORBFE_ERR_ARG;
-    bool retried = false;
     return guarded(m, [&]() {
-        std::function<int()> attempt = [&]() -> int {
         int st;
         SfiArgs a;
         if ((st = m->up(m->s5, prev_matched, (size_t)f1->n * 2 * sizeof(float)))) return st;
@@ -844,35 +980,21 @@ int orbfe_search_for_initialization(orbfe_matcher* m, float nnratio, int check_o
         a.prev = m->s5.as<float>();
         a.window = (float)window;
         const int n1 = f1->n, n2 = f2->n;
-        // candidates without a host round trip: the fill is bounded by the current capacity,
-        // checked at the first synchronisation of the rounds (one retry with the exact total)
-        const size_t cap = std::max(m->cand.bytes / sizeof(int2), (size_t)64 * std::max(n1, 1));
-        if ((st = m->cand.ensure(cap * sizeof(int2)))) return st;
-        if ((st = m->cnt.ensure(std::max(n1, 1) * sizeof(int)))) return st;
-        if ((st = m->off.ensure((n1 + 1) * sizeof(int)))) return st;
-        a.cnt = m->cnt.as<int>();
-        a.off = m->off.as<int>();
-        a.cand = m->cand.as<int2>();
-        a.cand_cap = (long long)cap;
-        const int qb = std::max(1, (n1 + 3) / 4);
-        hipLaunchKernelGGL(sfi_cand_kernel<false>, dim3(qb), dim3(256), 0, m->stream, a);
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, m->stream, m->cnt.as<int>(), n1, m->off.as<int>());
-        hipLaunchKernelGGL(sfi_cand_kernel<true>, dim3(qb), dim3(256), 0, m->stream, a);
+        // 64 candidates per F1 keypoint to start; the first synchronisation of the rounds
+        // checks that they fit
+        if ((st = m->cand_bounded(a, n1, 64, sfi_cand_kernel<false>, sfi_cand_kernel<true>))) return st;
         // fixed-point rounds (sfi_round_kernel): decisions, slot lists, change flags
         const int L2 = std::max(n2, 1);
         if ((st = m->g_dec.ensure((size_t)2 * std::max(n1, 1) * sizeof(int)))) return st;
         if ((st = m->g_t1.ensure((size_t)3 * L2 * sizeof(int)))) return st;
         if ((st = m->g_chg.ensure((size_t)(n1 + 4) * sizeof(int)))) return st;  // overflow, -, rounds 0..n1
         if ((st = m->s2.ensure(std::max(n1, 1) * 2 * sizeof(int)))) return st;
-        if ((st = m->flush())) return st;
-        int total = 0;  // read back with the first batch's change flags
-        if ((st = m->down_ptr(&total, m->off.as<int>() + n1, sizeof(int)))) return st;
         SfiRoundArgs r{};
         r.n1 = n1;
         r.n2 = n2;
-        r.off = m->off.as<int>();
-        r.cand = m->cand.as<int2>();
-        r.cand_cap = (long long)cap;
+        r.off = a.c.off;
+        r.cand = a.c.cand;
+        r.cand_cap = a.c.cand_cap;
         r.nnratio = nnratio;
         r.dec[0] = m->g_dec.as<int>();
         r.dec[1] = r.dec[0] + std::max(n1, 1);
@@ -911,15 +1033,7 @@ int orbfe_search_for_initialization(orbfe_matcher* m, float nnratio, int check_o
                 chg_h.assign(rr - r0 + 2, 0);
                 if ((st = m->down_ptr(chg_h.data(), m->g_chg.as<int>(), sizeof(int)))) return st;
                 if ((st = m->down_ptr(chg_h.data() + 2, r.chg + r0, (size_t)(rr - r0) * sizeof(int)))) return st;
-                if ((st = m->sync())) return st;
-                if ((size_t)total > cap) {
-                    if (retried) return ORBFE_ERR_HIP;
-                    if ((st = m->cand.ensure((size_t)total * sizeof(int2)))) return st;
-                    retried = true;
-                    ++m->capacity_retries;
-                    m->begin();
-                    return attempt();
-                }
+                if ((st = m->sync())) return st;  // the first one: ORBFE_ERR_CAPACITY and the rerun
                 ovf = chg_h[0];
                 if (ovf) break;
                 for (int q = 0; q < rr - r0; ++q)
@@ -954,8 +1068,6 @@ int orbfe_search_for_initialization(orbfe_matcher* m, float nnratio, int check_o
         if ((st = m->sync())) return st;
         *nmatches = res[0];
         return res[1];
-        };
-        return attempt();
     });
 }
 
@@ -973,21 +1085,8 @@ int orbfe_search_by_projection_local(orbfe_matcher* m, float nnratio,
         if (mps->track_in_view[i] && !mps->is_bad[i] &&
             (mps->pred_level[i] < 0 || mps->pred_level[i] >= f->nlevels))
             return ORBFE_ERR_UNSUPPORTED;
-    // fixed-slot candidates (one kernel, no mid-call count read-back) unless a point has more
-    // than kSbpFix of them: then the CSR path from the saved slots
-    std::vector<int32_t> fmp_in, fobs_in;
-    bool fix = f->n > 0 && M > 0;
-    if (fix) {
-        fmp_in.assign(frame_mp, frame_mp + f->n);
-        fobs_in.assign(frame_mp_obs, frame_mp_obs + f->n);
-    }
     return guarded(m, [&]() {
-      for (;;) {
         int st;
-        SbpLocalArgs a;
-        const int32_t zero[4] = {0, 0, 0, 0};  // nmatches, -, overflow
-        if ((st = m->up(m->scal, zero, sizeof(zero)))) return st;
-        if ((st = m->frame(f, false, a.f))) return st;
         if ((st = m->up(m->m_u0, mps->track_in_view, M))) return st;
         if ((st = m->up(m->m_u1, mps->is_bad, M))) return st;
         if ((st = m->up(m->m_f0, mps->proj_x, (size_t)M * 4))) return st;
@@ -997,68 +1096,25 @@ int orbfe_search_by_projection_local(orbfe_matcher* m, float nnratio,
         if ((st = m->up(m->m_f3, mps->view_cos, (size_t)M * 4))) return st;
         if ((st = m->up(m->m_d, mps->desc, (size_t)M * 32))) return st;
         if ((st = m->up(m->m_i1, mps->n_obs, (size_t)M * 4))) return st;
-        if ((st = m->up(m->m_f4, f->scale_factors, (size_t)f->nlevels * 4))) return st;
         if (mp_ids && (st = m->up(m->o_i, mp_ids, (size_t)M * 4))) return st;
-        a.mp = SbpMps{M, m->m_u0.as<uint8_t>(), m->m_u1.as<uint8_t>(), m->m_f0.as<float>(),
-                      m->m_f1.as<float>(), m->m_f2.as<float>(), m->m_i0.as<int>(),
-                      m->m_f3.as<float>(), m->m_d.as<uint4>(), m->m_i1.as<int>()};
-        a.scale = m->m_f4.as<float>();
-        a.th = th;
-        a.nlevels = f->nlevels;
-        a.status = nullptr;  // levels were checked on the host
-        a.cand_cap = LLONG_MAX;
-        a.kfix = kSbpFix;
-        a.ovf = m->scal.as<int>() + 2;
-        if (fix) {
-            if ((st = m->cnt.ensure((size_t)M * sizeof(int)))) return st;
-            if ((st = m->cand.ensure((size_t)M * kSbpFix * sizeof(int2)))) return st;
-            a.cnt = m->cnt.as<int>();
-            a.cand = m->cand.as<int2>();
-            if ((st = m->flush())) return st;
-            hipLaunchKernelGGL(sbp_local_cand_kernel<2>, dim3((M + 3) / 4), dim3(256), 0, m->stream, a);
-            ORBFE_HIP(hipGetLastError());
-        } else {
-            int total = 0;
-            if ((st = m->csr(a, M, sbp_local_cand_kernel<0>, sbp_local_cand_kernel<1>, total, 4)))
-                return st;
-        }
-        const int N = f->n;
-        if ((st = m->up(m->s1, frame_mp, (size_t)N * 4))) return st;
-        if ((st = m->up(m->s2, frame_mp_obs, (size_t)N * 4))) return st;
-        if ((st = m->s3.ensure(std::max(N, 1) * sizeof(int)))) return st;
-        if ((st = m->scal.ensure(16))) return st;
-        GreedyArgs g{};
-        g.m = M;
-        g.nkp = N;
-        g.mode = kGreedyLocal;
-        g.nnratio = nnratio;
-        g.off = m->off.as<int>();
-        g.cand = m->cand.as<int2>();
-        g.nobs = m->m_i1.as<int>();
-        g.fmp0 = g.fmp = m->s1.as<int>();
-        g.fobs0 = g.fobs = m->s2.as<int>();
-        g.ids = mp_ids ? m->o_i.as<int>() : nullptr;
-        if (fix) {
-            g.kfix = kSbpFix;
-            g.fcnt = m->cnt.as<int>();
-        }
-        if ((st = m->greedy(g))) return st;
-        if ((st = m->down(frame_mp, m->s1, (size_t)N * 4))) return st;
-        if ((st = m->down(frame_mp_obs, m->s2, (size_t)N * 4))) return st;
-        int res[3] = {0, 0, 0};  // {nmatches, -, overflow}
-        if ((st = m->down(res, m->scal, sizeof(res)))) return st;
-        if ((st = m->sync())) return st;
-        if (fix && res[2] > 0) {  // a point past kSbpFix candidates: the CSR path from the input
-            std::memcpy(frame_mp, fmp_in.data(), (size_t)N * 4);
-            std::memcpy(frame_mp_obs, fobs_in.data(), (size_t)N * 4);
-            fix = false;
-            ++m->capacity_retries;
-            m->begin();
-            continue;
-        }
-        *nmatches = res[0];
-        return ORBFE_OK;
-      }
+        // kSbpFix slots per point, else the CSR path
+        return sbp_search(
+            m, f, M, kSbpFix, sbp_local_cand_kernel<0>, sbp_local_cand_kernel<1>,
+            sbp_local_cand_kernel<2>, frame_mp, frame_mp_obs, nmatches,
+            [&](SbpLocalArgs& a, GreedyArgs& g, const DevFrame& F) {
+                a.f = F;
+                a.mp = SbpMps{M, m->m_u0.as<uint8_t>(), m->m_u1.as<uint8_t>(), m->m_f0.as<float>(),
+                              m->m_f1.as<float>(), m->m_f2.as<float>(), m->m_i0.as<int>(),
+                              m->m_f3.as<float>(), m->m_d.as<uint4>(), m->m_i1.as<int>()};
+                a.scale = m->m_f4.as<float>();
+                a.th = th;
+                a.nlevels = f->nlevels;
+                a.status = nullptr;  // levels were checked on the host
+                g.mode = kGreedyLocal;
+                g.nnratio = nnratio;
+                g.nobs = m->m_i1.as<int>();
+                g.ids = mp_ids ? m->o_i.as<int>() : nullptr;
+            });
     });
 }
 
@@ -1082,112 +1138,48 @@ int orbfe_search_by_projection_last(orbfe_matcher* m, int check_ori,
     for (int i = 0; i < n_last; ++i)
         if (last_mp_valid[i] && (last_keys[i].octave < 0 || last_keys[i].octave >= cur->nlevels))
             return ORBFE_ERR_UNSUPPORTED;
-    // fixed-slot candidates unless a point has more than kSbpLastFix (then the CSR path from the
-    // saved slots), as the keyframe overload below; 64 slots: the mono th = 15 window over three
-    // octaves holds more than 16 keypoints for some points of a 1000-keypoint frame
-    std::vector<int32_t> fmp_in, fobs_in;
-    bool fix = cur->n > 0 && n_last > 0;
-    if (fix) {
-        fmp_in.assign(frame_mp, frame_mp + cur->n);
-        fobs_in.assign(frame_mp_obs, frame_mp_obs + cur->n);
-    }
+    std::vector<float> qa(n_last);
+    for (int i = 0; i < n_last; ++i) qa[i] = last_keys[i].angle;
     return guarded(m, [&]() {
-      for (;;) {
         int st;
-        SbpLastArgs a;
-        const int32_t zero[4] = {0, 0, 0, 0};  // nmatches, -, overflow
-        if ((st = m->up(m->scal, zero, sizeof(zero)))) return st;
-        if ((st = m->frame(cur, false, a.cur))) return st;
         if ((st = m->up(m->fb_k, last_keys, (size_t)n_last * sizeof(orbfe_keypoint)))) return st;
         if ((st = m->up(m->m_u0, last_mp_valid, n_last))) return st;
         if ((st = m->up(m->m_u1, last_outlier, n_last))) return st;
         if ((st = m->up(m->m_f0, last_mp_xyz, (size_t)n_last * 12))) return st;
         if ((st = m->up(m->m_d, last_mp_desc, (size_t)n_last * 32))) return st;
         if ((st = m->up(m->m_i1, last_mp_nobs, (size_t)n_last * 4))) return st;
-        if ((st = m->up(m->m_f4, cur->scale_factors, (size_t)cur->nlevels * 4))) return st;
-        if (last_mp_ids && (st = m->up(m->o_i, last_mp_ids, (size_t)n_last * 4))) return st;
-        a.n_last = n_last;
-        a.lk = m->fb_k.as<orbfe_keypoint>();
-        a.valid = m->m_u0.as<uint8_t>();
-        a.outlier = m->m_u1.as<uint8_t>();
-        a.xyz = m->m_f0.as<float>();
-        a.desc = m->m_d.as<uint4>();
-        std::memcpy(a.T, tcw_cur, sizeof(a.T));
-        a.fx = cam->fx;
-        a.fy = cam->fy;
-        a.cx = cam->cx;
-        a.cy = cam->cy;
-        a.bf = cam->bf;
-        a.minx = cur->min_x;
-        a.maxx = cur->max_x;
-        a.miny = cur->min_y;
-        a.maxy = cur->max_y;
-        a.scale = m->m_f4.as<float>();
-        a.th = th;
-        float twc[3], tlc[3];  // 1341-1352: motion direction for stereo/RGB-D
-        camera_center(tcw_cur, twc);
-        rigid(tcw_last, twc, tlc);
-        const bool fwd = tlc[2] > cam->b && !mono;
-        const bool bwd = -tlc[2] > cam->b && !mono;
-        a.mode = fwd ? 1 : bwd ? 2 : 0;
-        a.kfix = kSbpLastFix;
-        a.ovf = m->scal.as<int>() + 2;
-        if (fix) {
-            if ((st = m->cnt.ensure((size_t)n_last * sizeof(int)))) return st;
-            if ((st = m->cand.ensure((size_t)n_last * kSbpLastFix * sizeof(int2)))) return st;
-            a.cnt = m->cnt.as<int>();
-            a.cand = m->cand.as<int2>();
-            if ((st = m->flush())) return st;
-            hipLaunchKernelGGL(sbp_last_cand_kernel<2>, dim3((n_last + 3) / 4), dim3(256), 0, m->stream, a);
-            ORBFE_HIP(hipGetLastError());
-        } else if ((st = m->csr_async(a, n_last, sbp_last_cand_kernel<0>, sbp_last_cand_kernel<1>, 4))) {
-            return st;
-        }
-        const int N = cur->n;
-        if ((st = m->up(m->s1, frame_mp, (size_t)N * 4))) return st;
-        if ((st = m->up(m->s2, frame_mp_obs, (size_t)N * 4))) return st;
-        if ((st = m->s3.ensure(std::max(N, 1) * sizeof(int)))) return st;
-        if ((st = m->s4.ensure(std::max(n_last, 1) * sizeof(int2)))) return st;
-        if ((st = m->scal.ensure(16))) return st;
-        if ((st = m->o_f3.ensure(std::max<size_t>(16, (size_t)n_last * 4)))) return st;
-        std::vector<float> qa(n_last);
-        for (int i = 0; i < n_last; ++i) qa[i] = last_keys[i].angle;
         if ((st = m->up(m->o_f3, qa.data(), (size_t)n_last * 4))) return st;
-        GreedyArgs g{};
-        g.m = n_last;
-        g.nkp = N;
-        g.mode = kGreedyMaxD;
-        g.max_dist = kThHigh;
-        g.off = m->off.as<int>();
-        g.cand = m->cand.as<int2>();
-        g.nobs = m->m_i1.as<int>();
-        g.fmp0 = g.fmp = m->s1.as<int>();
-        g.fobs0 = g.fobs = m->s2.as<int>();
-        g.check_ori = check_ori;
-        g.q_angle = m->o_f3.as<float>();
-        g.k = a.cur.k;
-        g.ids = last_mp_ids ? m->o_i.as<int>() : nullptr;
-        if (fix) {
-            g.kfix = kSbpLastFix;
-            g.fcnt = m->cnt.as<int>();
-        }
-        if ((st = m->greedy(g))) return st;
-        if ((st = m->down(frame_mp, m->s1, (size_t)N * 4))) return st;
-        if ((st = m->down(frame_mp_obs, m->s2, (size_t)N * 4))) return st;
-        int res[3] = {0, 0, 0};  // {nmatches, -, overflow}
-        if ((st = m->down(res, m->scal, sizeof(res)))) return st;
-        if ((st = m->sync())) return st;
-        if (fix && res[2] > 0) {  // a point past kSbpLastFix candidates: the CSR path from the input
-            std::memcpy(frame_mp, fmp_in.data(), (size_t)N * 4);
-            std::memcpy(frame_mp_obs, fobs_in.data(), (size_t)N * 4);
-            fix = false;
-            ++m->capacity_retries;
-            m->begin();
-            continue;
-        }
-        *nmatches = res[0];
-        return ORBFE_OK;
-      }
+        if (last_mp_ids && (st = m->up(m->o_i, last_mp_ids, (size_t)n_last * 4))) return st;
+        // 64 slots: the mono th = 15 window over three octaves holds more than 16 keypoints for
+        // some points of a 1000-keypoint frame
+        return sbp_search(
+            m, cur, n_last, kSbpLastFix, sbp_last_cand_kernel<0>, sbp_last_cand_kernel<1>,
+            sbp_last_cand_kernel<2>, frame_mp, frame_mp_obs, nmatches,
+            [&](SbpLastArgs& a, GreedyArgs& g, const DevFrame& F) {
+                a.cur = F;
+                a.n_last = n_last;
+                a.lk = m->fb_k.as<orbfe_keypoint>();
+                a.valid = m->m_u0.as<uint8_t>();
+                a.outlier = m->m_u1.as<uint8_t>();
+                a.xyz = m->m_f0.as<float>();
+                a.desc = m->m_d.as<uint4>();
+                put_view(a, tcw_cur, cam, cur->min_x, cur->max_x, cur->min_y, cur->max_y);
+                a.bf = cam->bf;
+                a.scale = m->m_f4.as<float>();
+                a.th = th;
+                float twc[3], tlc[3];  // 1341-1352: motion direction for stereo/RGB-D
+                camera_center(tcw_cur, twc);
+                rigid(tcw_last, twc, tlc);
+                const bool fwd = tlc[2] > cam->b && !mono;
+                const bool bwd = -tlc[2] > cam->b && !mono;
+                a.mode = fwd ? 1 : bwd ? 2 : 0;
+                g.mode = kGreedyMaxD;
+                g.max_dist = kThHigh;
+                g.nobs = m->m_i1.as<int>();
+                g.check_ori = check_ori;
+                g.q_angle = m->o_f3.as<float>();
+                g.ids = last_mp_ids ? m->o_i.as<int>() : nullptr;
+            });
     });
 }
 
@@ -1204,21 +1196,8 @@ int orbfe_search_by_projection_keyframe(orbfe_matcher* m, int check_ori,
         (n_kf && (!kf_key_angle || !kf_mp_valid || !kf_mp_bad || !already_found || !kf_mp_xyz ||
                   !kf_mp_desc || !kf_mp_min_dist || !kf_mp_max_dist)))
         return ORBFE_ERR_ARG;
-    // the fixed-slot candidates (one kernel instead of count / scan / fill) unless a point has
-    // more than kSbpFix of them: then the call runs again on the CSR path from the saved slots
-    std::vector<int32_t> fmp_in;
-    bool fix = cur->n > 0 && n_kf > 0;
-    if (fix) fmp_in.assign(frame_mp, frame_mp + cur->n);
     return guarded(m, [&]() {
-      for (;;) {
         int st;
-        SbpKfArgs a;
-        // every upload is staged before the frame's flush: one H2D copy + one scatter launch;
-        // the status word is cleared by the same copy
-        const int32_t zero[4] = {0, 0, 0, 0};
-        if ((st = m->up(m->scal, zero, sizeof(zero)))) return st;
-        // a slot already holding a map point blocks (1529-1530), whatever its observations
-        if ((st = m->up(m->s1, frame_mp, (size_t)cur->n * 4))) return st;
         if ((st = m->up(m->m_u0, kf_mp_valid, n_kf))) return st;
         if ((st = m->up(m->m_u1, kf_mp_bad, n_kf))) return st;
         if ((st = m->up(m->o_u, already_found, n_kf))) return st;
@@ -1227,81 +1206,35 @@ int orbfe_search_by_projection_keyframe(orbfe_matcher* m, int check_ori,
         if ((st = m->up(m->m_f2, kf_mp_max_dist, (size_t)n_kf * 4))) return st;
         if ((st = m->up(m->m_f3, kf_key_angle, (size_t)n_kf * 4))) return st;
         if ((st = m->up(m->m_d, kf_mp_desc, (size_t)n_kf * 32))) return st;
-        if ((st = m->up(m->m_f4, cur->scale_factors, (size_t)cur->nlevels * 4))) return st;
         if (kf_mp_ids && (st = m->up(m->o_i, kf_mp_ids, (size_t)n_kf * 4))) return st;
-        if ((st = m->frame(cur, false, a.cur))) return st;
-        a.n = n_kf;
-        a.valid = m->m_u0.as<uint8_t>();
-        a.bad = m->m_u1.as<uint8_t>();
-        a.found = m->o_u.as<uint8_t>();
-        a.xyz = m->m_f0.as<float>();
-        a.mind = m->m_f1.as<float>();
-        a.maxd = m->m_f2.as<float>();
-        a.desc = m->m_d.as<uint4>();
-        std::memcpy(a.T, tcw_cur, sizeof(a.T));
-        camera_center(tcw_cur, a.ow);
-        a.fx = cam->fx;
-        a.fy = cam->fy;
-        a.cx = cam->cx;
-        a.cy = cam->cy;
-        a.minx = cur->min_x;
-        a.maxx = cur->max_x;
-        a.miny = cur->min_y;
-        a.maxy = cur->max_y;
-        a.scale = m->m_f4.as<float>();
-        a.nlevels = cur->nlevels;
-        a.log_scale = log_scale_factor;
-        a.th = th;
-        a.status = m->scal.as<int>() + 1;
-        a.kfix = kSbpFix;
-        a.ovf = m->scal.as<int>() + 2;
-        if (fix) {
-            if ((st = m->cnt.ensure((size_t)n_kf * sizeof(int)))) return st;
-            if ((st = m->cand.ensure((size_t)n_kf * kSbpFix * sizeof(int2)))) return st;
-            a.cnt = m->cnt.as<int>();
-            a.cand = m->cand.as<int2>();
-            if ((st = m->flush())) return st;
-            hipLaunchKernelGGL(sbp_kf_cand_kernel<2>, dim3((n_kf + 3) / 4), dim3(256), 0, m->stream, a);
-            ORBFE_HIP(hipGetLastError());
-        } else if ((st = m->csr_async(a, n_kf, sbp_kf_cand_kernel<0>, sbp_kf_cand_kernel<1>, 4))) {
-            return st;
-        }
-        const int N = cur->n;
-        GreedyArgs g{};
-        g.m = n_kf;
-        g.nkp = N;
-        g.mode = kGreedyMaxD;
-        g.max_dist = orb_dist;
-        g.off = m->off.as<int>();
-        g.cand = m->cand.as<int2>();
-        g.nobs = nullptr;
-        g.fmp0 = g.fmp = m->s1.as<int>();
-        g.fobs0 = g.fobs = nullptr;
-        g.check_ori = check_ori;
-        g.q_angle = m->m_f3.as<float>();  // pKF->mvKeysUn[i].angle (1549)
-        g.k = a.cur.k;
-        g.ids = kf_mp_ids ? m->o_i.as<int>() : nullptr;
-        if (fix) {
-            g.kfix = kSbpFix;
-            g.fcnt = m->cnt.as<int>();
-        }
-        if ((st = m->greedy(g))) return st;
-        if ((st = m->down(frame_mp, m->s1, (size_t)N * 4))) return st;
-        // {nmatches, status, overflow}: status != 0 is a predicted level outside the pyramid
-        // (outputs then unspecified)
-        int res[3] = {0, 0, 0};
-        if ((st = m->down(res, m->scal, sizeof(res)))) return st;
-        if ((st = m->sync())) return st;
-        if (fix && res[2] > 0) {  // a point past kSbpFix candidates: the CSR path from the input
-            std::memcpy(frame_mp, fmp_in.data(), (size_t)N * 4);
-            fix = false;
-            ++m->capacity_retries;
-            m->begin();
-            continue;
-        }
-        *nmatches = res[0];
-        return res[1];
-      }
+        // no observation counts: a slot already holding a map point blocks (1529-1530).  The
+        // status word: a predicted level outside the pyramid (outputs then unspecified)
+        return sbp_search(
+            m, cur, n_kf, kSbpFix, sbp_kf_cand_kernel<0>, sbp_kf_cand_kernel<1>,
+            sbp_kf_cand_kernel<2>, frame_mp, nullptr, nmatches,
+            [&](SbpKfArgs& a, GreedyArgs& g, const DevFrame& F) {
+                a.cur = F;
+                a.n = n_kf;
+                a.valid = m->m_u0.as<uint8_t>();
+                a.bad = m->m_u1.as<uint8_t>();
+                a.found = m->o_u.as<uint8_t>();
+                a.xyz = m->m_f0.as<float>();
+                a.mind = m->m_f1.as<float>();
+                a.maxd = m->m_f2.as<float>();
+                a.desc = m->m_d.as<uint4>();
+                put_view(a, tcw_cur, cam, cur->min_x, cur->max_x, cur->min_y, cur->max_y);
+                camera_center(tcw_cur, a.ow);
+                a.scale = m->m_f4.as<float>();
+                a.nlevels = cur->nlevels;
+                a.log_scale = log_scale_factor;
+                a.th = th;
+                a.status = m->scal.as<int>() + 1;
+                g.mode = kGreedyMaxD;
+                g.max_dist = orb_dist;
+                g.check_ori = check_ori;
+                g.q_angle = m->m_f3.as<float>();  // pKF->mvKeysUn[i].angle (1549)
+                g.ids = kf_mp_ids ? m->o_i.as<int>() : nullptr;
+            });
     });
 }
 
@@ -1366,137 +1299,43 @@ int orbfe_search_local_points_device(orbfe_matcher* m, const orbfe_frame_view* f
         if ((st = m->scal.ensure(64))) return st;
         for (DevBuf* b : {&m->o_f0, &m->o_f1, &m->o_f2, &m->o_f3, &m->o_i})
             if ((st = b->ensure(std::max<size_t>(16, (size_t)M * 4)))) return st;
-        int* d_cnt = m->scal.as<int>() + 1;     // nToMatch
-        int* d_status = m->scal.as<int>() + 2;  // UB level
-        // fast path (sbp_local_fast), else / on its fallback the CSR path below
-        if (N <= kSbpFixKp && frame->nlevels <= kMaxLevels && M > 0) {
-            FrustumArgs fa{};
-            fa.n = M;
-            fa.xyz = d_xyz;
-            fa.normal = d_normal;
-            fa.mind = d_min_dist;
-            fa.maxd = d_max_dist;
-            std::memcpy(fa.T, tcw, sizeof(fa.T));
-            camera_center(tcw, fa.ow);
-            fa.fx = cam->fx;
-            fa.fy = cam->fy;
-            fa.cx = cam->cx;
-            fa.cy = cam->cy;
-            fa.bf = cam->bf;
-            fa.minx = frame->min_x;
-            fa.maxx = frame->max_x;
-            fa.miny = frame->min_y;
-            fa.maxy = frame->max_y;
-            fa.log_scale = log_scale_factor;
-            fa.cos_limit = viewing_cos_limit;
-            fa.in_view = d_in_view;
-            fa.skip = d_skip;
-            fa.bad = d_bad;
-            SbpMps mp{};
-            mp.m = M;
-            mp.desc = reinterpret_cast<const uint4*>(d_desc);
-            int host[6];
-            if ((st = sbp_local_fast<false>(m, frame, fa, mp, nnratio, th, d_nobs, d_mp_ids, d_frame_mp,
-                                            d_frame_mp_obs, host)))
-                return st;
-            if (!host[3] && host[4] == 0) {  // no overflow, converged
-                counts[0] = host[0];
-                counts[1] = host[1];
-                return host[2] ? host[2] : ORBFE_OK;
-            }
-        }
-        bool retried = false;
-        // (the fast path above passes mvScaleFactors in its kernel arguments)
-        if ((st = m->m_f4.ensure(std::max<size_t>(16, (size_t)frame->nlevels * 4)))) return st;
-        ORBFE_HIP(hipMemcpyAsync(m->m_f4.p, frame->scale_factors, (size_t)frame->nlevels * 4,
-                                 hipMemcpyHostToDevice, m->stream));
-        std::function<int()> attempt = [&]() -> int {
-        ORBFE_HIP(hipMemsetAsync(m->scal.p, 0, 16, m->stream));
         // Tracking::SearchLocalPoints: isInFrustum(pMP, 0.5) over the local map (1425-1438)
-        FrustumArgs fa;
+        FrustumArgs fa = frustum_view(tcw, cam, frame->min_x, frame->max_x, frame->min_y,
+                                      frame->max_y, log_scale_factor, viewing_cos_limit);
         fa.n = M;
         fa.xyz = d_xyz;
         fa.normal = d_normal;
         fa.mind = d_min_dist;
         fa.maxd = d_max_dist;
-        std::memcpy(fa.T, tcw, sizeof(fa.T));
-        camera_center(tcw, fa.ow);
-        fa.fx = cam->fx;
-        fa.fy = cam->fy;
-        fa.cx = cam->cx;
-        fa.cy = cam->cy;
-        fa.bf = cam->bf;
-        fa.minx = frame->min_x;
-        fa.maxx = frame->max_x;
-        fa.miny = frame->min_y;
-        fa.maxy = frame->max_y;
-        fa.log_scale = log_scale_factor;
-        fa.cos_limit = viewing_cos_limit;
         fa.in_view = d_in_view;
-        fa.px = m->o_f0.as<float>();
-        fa.py = m->o_f1.as<float>();
-        fa.pxr = m->o_f2.as<float>();
-        fa.lvl = m->o_i.as<int>();
-        fa.vcos = m->o_f3.as<float>();
         fa.skip = d_skip;
         fa.bad = d_bad;
-        fa.n_in_view = d_cnt;
-        if (M) hipLaunchKernelGGL(frustum_kernel, dim3((M + 255) / 256), dim3(256), 0, m->stream, fa);
-        // SearchByProjection(F, vpLocalMapPoints, th) (1440-1453, ORBmatcher.cc:45-129)
-        SbpLocalArgs a;
-        if ((st = m->frame_device(frame, a.f))) return st;
-        a.mp = SbpMps{M, d_in_view, d_bad, fa.px, fa.py, fa.pxr, fa.lvl, fa.vcos,
-                      reinterpret_cast<const uint4*>(d_desc), d_nobs};
-        a.scale = m->m_f4.as<float>();
-        a.th = th;
-        a.nlevels = frame->nlevels;
-        a.status = d_status;
-        // candidates without a host round trip: the fill is bounded by the current capacity
-        // (16 per point to start); the total is checked after the first greedy batch and the
-        // call is redone once with the exact capacity if it did not fit
-        const size_t cap = std::max(m->cand.bytes / sizeof(int2), (size_t)16 * std::max(M, 1));
-        if ((st = m->cand.ensure(cap * sizeof(int2)))) return st;
-        if ((st = m->cnt.ensure(std::max(M, 1) * sizeof(int)))) return st;
-        if ((st = m->off.ensure((M + 1) * sizeof(int)))) return st;
-        a.cnt = m->cnt.as<int>();
-        a.off = m->off.as<int>();
-        a.cand = m->cand.as<int2>();
-        a.cand_cap = (long long)cap;
-        const int qb = std::max(1, (M + 3) / 4);  // one wave per map point
-        hipLaunchKernelGGL(sbp_local_cand_kernel<0>, dim3(qb), dim3(256), 0, m->stream, a);
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, m->stream, m->cnt.as<int>(), M, m->off.as<int>());
-        hipLaunchKernelGGL(sbp_local_cand_kernel<1>, dim3(qb), dim3(256), 0, m->stream, a);
-        int total = 0;
-        ORBFE_HIP(hipMemcpyAsync(&total, m->off.as<int>() + M, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        GreedyArgs g{};
-        g.m = M;
-        g.nkp = N;
-        g.mode = kGreedyLocal;
-        g.nnratio = nnratio;
-        g.off = m->off.as<int>();
-        g.cand = m->cand.as<int2>();
-        g.nobs = d_nobs;
-        g.fmp0 = g.fmp = d_frame_mp;
-        g.fobs0 = g.fobs = d_frame_mp_obs;
-        g.ids = d_mp_ids;
-        // synchronizes per batch of rounds; ORBFE_ERR_CAPACITY (nothing written yet) when the
-        // candidates did not fit: grow to the exact total and run again
-        st = m->greedy(g, 8, &total, cap);
-        if (st == ORBFE_ERR_CAPACITY && !retried) {
-            if ((st = m->cand.ensure((size_t)total * sizeof(int2)))) return st;
-            retried = true;
-            ++m->capacity_retries;
-            return attempt();
+        int res[6];  // {nmatches, nToMatch, status, ...}
+        // fast path (sbp_local_fast), else / on its rerun the CSR path
+        if (N <= kSbpFixKp && frame->nlevels <= kMaxLevels && M > 0 && !m->rerun.no_fixed) {
+            SbpMps mp{};
+            mp.m = M;
+            mp.desc = reinterpret_cast<const uint4*>(d_desc);
+            st = sbp_local_fast<false>(m, frame, fa, mp, nnratio, th, d_nobs, d_mp_ids, d_frame_mp,
+                                       d_frame_mp_obs, res);
+        } else {
+            // SearchByProjection(F, vpLocalMapPoints, th) (1440-1453, ORBmatcher.cc:45-129) on
+            // the projections frustum_kernel leaves in the scratch
+            fa.px = m->o_f0.as<float>();
+            fa.py = m->o_f1.as<float>();
+            fa.pxr = m->o_f2.as<float>();
+            fa.lvl = m->o_i.as<int>();
+            fa.vcos = m->o_f3.as<float>();
+            fa.n_in_view = m->scal.as<int>() + 1;
+            const SbpMps mp{M, d_in_view, d_bad, fa.px, fa.py, fa.pxr, fa.lvl, fa.vcos,
+                            reinterpret_cast<const uint4*>(d_desc), d_nobs};
+            st = sbp_local_device_fallback(m, frame, &fa, mp, nnratio, th, d_mp_ids, d_frame_mp,
+                                      d_frame_mp_obs, res);
         }
         if (st) return st;
-        int host[3] = {0, 0, 0};
-        ORBFE_HIP(hipMemcpyAsync(host, m->scal.p, sizeof(host), hipMemcpyDeviceToHost, m->stream));
-        ORBFE_HIP(hipStreamSynchronize(m->stream));
-        counts[0] = host[0];  // nmatches
-        counts[1] = host[1];  // nToMatch
-        return host[2] ? host[2] : ORBFE_OK;
-        };
-        return attempt();
+        counts[0] = res[0];  // nmatches
+        counts[1] = res[1];  // nToMatch
+        return res[2] ? res[2] : ORBFE_OK;
     });
 }
 
@@ -1515,82 +1354,23 @@ int orbfe_search_by_projection_local_device(orbfe_matcher* m, float nnratio,
         return ORBFE_ERR_ARG;
     return guarded(m, [&]() {
         int st;
-        const int N = frame->n;
         if ((st = m->scal.ensure(64))) return st;
+        const SbpMps mp{M, d_mps->track_in_view, d_mps->is_bad, d_mps->proj_x, d_mps->proj_y,
+                        d_mps->proj_xr, d_mps->pred_level, d_mps->view_cos,
+                        reinterpret_cast<const uint4*>(d_mps->desc), d_mps->n_obs};
+        int res[6];  // {nmatches, -, status, ...}
         // fast path (sbp_local_fast on the resident isInFrustum outputs; the scale factors go
-        // as kernel arguments), else / on its fallback the CSR path below
-        if (N <= kSbpFixKp && frame->nlevels <= kMaxLevels && M > 0 &&
-            !std::getenv("ORBFE_SBP_DEVICE_CSR")) {
-            const SbpMps mp{M, d_mps->track_in_view, d_mps->is_bad, d_mps->proj_x, d_mps->proj_y,
-                            d_mps->proj_xr, d_mps->pred_level, d_mps->view_cos,
-                            reinterpret_cast<const uint4*>(d_mps->desc), d_mps->n_obs};
-            int host[6];
-            if ((st = sbp_local_fast<true>(m, frame, FrustumArgs{}, mp, nnratio, th, d_mps->n_obs,
-                                           d_mp_ids, d_frame_mp, d_frame_mp_obs, host)))
-                return st;
-            if (!host[3] && host[4] == 0) {  // no overflow, converged
-                *nmatches = host[0];
-                return host[2] ? host[2] : ORBFE_OK;
-            }
-        }
-        // the CSR path reads the scale factors from device memory
-        if ((st = m->m_f4.ensure(std::max<size_t>(16, (size_t)frame->nlevels * 4)))) return st;
-        ORBFE_HIP(hipMemcpyAsync(m->m_f4.p, frame->scale_factors, (size_t)frame->nlevels * 4,
-                                 hipMemcpyHostToDevice, m->stream));
-        bool retried = false;
-        std::function<int()> attempt = [&]() -> int {
-            ORBFE_HIP(hipMemsetAsync(m->scal.p, 0, 16, m->stream));
-            SbpLocalArgs a;
-            if ((st = m->frame_device(frame, a.f))) return st;  // AssignFeaturesToGrid
-            a.mp = SbpMps{M, d_mps->track_in_view, d_mps->is_bad, d_mps->proj_x, d_mps->proj_y,
-                          d_mps->proj_xr, d_mps->pred_level, d_mps->view_cos,
-                          reinterpret_cast<const uint4*>(d_mps->desc), d_mps->n_obs};
-            a.scale = m->m_f4.as<float>();
-            a.th = th;
-            a.nlevels = frame->nlevels;
-            a.status = m->scal.as<int>() + 2;  // a predicted level outside the pyramid
-            // count -> scan -> fill bounded by the grow-only capacity; checked after the first
-            // batch of greedy rounds, redone once with the exact total if it did not fit
-            const size_t cap = std::max(m->cand.bytes / sizeof(int2), (size_t)16 * std::max(M, 1));
-            if ((st = m->cand.ensure(cap * sizeof(int2)))) return st;
-            if ((st = m->cnt.ensure(std::max(M, 1) * sizeof(int)))) return st;
-            if ((st = m->off.ensure((M + 1) * sizeof(int)))) return st;
-            a.cnt = m->cnt.as<int>();
-            a.off = m->off.as<int>();
-            a.cand = m->cand.as<int2>();
-            a.cand_cap = (long long)cap;
-            const int qb = std::max(1, (M + 3) / 4);  // one wave per map point
-            hipLaunchKernelGGL(sbp_local_cand_kernel<0>, dim3(qb), dim3(256), 0, m->stream, a);
-            hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, m->stream, m->cnt.as<int>(), M, m->off.as<int>());
-            hipLaunchKernelGGL(sbp_local_cand_kernel<1>, dim3(qb), dim3(256), 0, m->stream, a);
-            int total = 0;
-            ORBFE_HIP(hipMemcpyAsync(&total, m->off.as<int>() + M, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-            GreedyArgs g{};
-            g.m = M;
-            g.nkp = N;
-            g.mode = kGreedyLocal;
-            g.nnratio = nnratio;
-            g.off = m->off.as<int>();
-            g.cand = m->cand.as<int2>();
-            g.nobs = d_mps->n_obs;
-            g.fmp0 = g.fmp = d_frame_mp;
-            g.fobs0 = g.fobs = d_frame_mp_obs;
-            g.ids = d_mp_ids;
-            st = m->greedy(g, 8, &total, cap);
-            if (st == ORBFE_ERR_CAPACITY && !retried) {
-                if ((st = m->cand.ensure((size_t)total * sizeof(int2)))) return st;
-                retried = true;
-                ++m->capacity_retries;
-                return attempt();
-            }
-            if (st) return st;
-            int host[3] = {0, 0, 0};
-            ORBFE_HIP(hipMemcpyAsync(host, m->scal.p, sizeof(host), hipMemcpyDeviceToHost, m->stream));
-            ORBFE_HIP(hipStreamSynchronize(m->stream));
-            *nmatches = host[0];
-            return host[2] ? host[2] : ORBFE_OK;
-        };
-        return attempt();
+        // as kernel arguments), else / on its rerun the CSR path
+        if (frame->n <= kSbpFixKp && frame->nlevels <= kMaxLevels && M > 0 && !m->rerun.no_fixed &&
+            !std::getenv("ORBFE_SBP_DEVICE_CSR"))
+            st = sbp_local_fast<true>(m, frame, FrustumArgs{}, mp, nnratio, th, d_mps->n_obs,
+                                      d_mp_ids, d_frame_mp, d_frame_mp_obs, res);
+        else
+            st = sbp_local_device_fallback(m, frame, nullptr, mp, nnratio, th, d_mp_ids, d_frame_mp,
+                                      d_frame_mp_obs, res);
+        if (st) return st;
+        *nmatches = res[0];
+        return res[2] ? res[2] : ORBFE_OK;
     });
 }
 
@@ -1604,29 +1384,31 @@ int orbfe_features_in_area(orbfe_matcher* m, const orbfe_frame_view* f, int nq, 
     return guarded(m, [&]() {
         int st;
         FiaArgs a;
+        DevBuf& cnt = m->cl.cnt;
+        DevBuf& offs = m->cl.off;
         if ((st = m->up(m->m_f0, x, (size_t)nq * 4))) return st;
         if ((st = m->up(m->m_f1, y, (size_t)nq * 4))) return st;
         if ((st = m->up(m->m_f2, r, (size_t)nq * 4))) return st;
         if ((st = m->up(m->m_i0, min_level, (size_t)nq * 4))) return st;
         if ((st = m->up(m->m_i1, max_level, (size_t)nq * 4))) return st;
         if ((st = m->frame(f, false, a.f))) return st;  // AssignFeaturesToGrid (flushes)
-        if ((st = m->cnt.ensure(std::max(nq, 1) * sizeof(int)))) return st;
-        if ((st = m->off.ensure((size_t)(nq + 1) * sizeof(int)))) return st;
+        if ((st = cnt.ensure(std::max(nq, 1) * sizeof(int)))) return st;
+        if ((st = offs.ensure((size_t)(nq + 1) * sizeof(int)))) return st;
         a.nq = nq;
         a.x = m->m_f0.as<float>();
         a.y = m->m_f1.as<float>();
         a.r = m->m_f2.as<float>();
         a.lo = m->m_i0.as<int>();
         a.hi = m->m_i1.as<int>();
-        a.cnt = m->cnt.as<int>();
-        a.off = m->off.as<int>();
+        a.cnt = cnt.as<int>();
+        a.off = offs.as<int>();
         const int blocks = std::max(1, wave ? (nq + 3) / 4 : (nq + 255) / 256);
         if (wave) hipLaunchKernelGGL(fia_wave_kernel<false>, dim3(blocks), dim3(256), 0, m->stream, a);
         else hipLaunchKernelGGL(fia_thread_kernel<false>, dim3(blocks), dim3(256), 0, m->stream, a);
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, m->stream, m->cnt.as<int>(), nq,
-                           m->off.as<int>());
+        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, m->stream, cnt.as<int>(), nq,
+                           offs.as<int>());
         ORBFE_HIP(hipGetLastError());
-        if ((st = m->down(off, m->off, (size_t)(nq + 1) * 4))) return st;
+        if ((st = m->down(off, offs, (size_t)(nq + 1) * 4))) return st;
         if ((st = m->sync())) return st;
         const int total = off[nq];
         if (total > items_cap) return ORBFE_ERR_CAPACITY;
@@ -1682,33 +1464,20 @@ int orbfe_is_in_frustum(orbfe_matcher* m, int n, const float* xyz, const float* 
         if ((st = m->up(m->o_f2, proj_xr, (size_t)n * 4))) return st;
         if ((st = m->up(m->o_f3, view_cos, (size_t)n * 4))) return st;
         if ((st = m->up(m->o_i, pred_level, (size_t)n * 4))) return st;
-        FrustumArgs a;
+        // skip, bad and n_in_view stay null: the plain isInFrustum
+        FrustumArgs a = frustum_view(tcw, cam, min_x, max_x, min_y, max_y, log_scale_factor,
+                                     viewing_cos_limit);
         a.n = n;
         a.xyz = m->m_f0.as<float>();
         a.normal = m->m_f1.as<float>();
         a.mind = m->m_f2.as<float>();
         a.maxd = m->m_f3.as<float>();
-        std::memcpy(a.T, tcw, sizeof(a.T));
-        camera_center(tcw, a.ow);
-        a.fx = cam->fx;
-        a.fy = cam->fy;
-        a.cx = cam->cx;
-        a.cy = cam->cy;
-        a.bf = cam->bf;
-        a.minx = min_x;
-        a.maxx = max_x;
-        a.miny = min_y;
-        a.maxy = max_y;
-        a.log_scale = log_scale_factor;
-        a.cos_limit = viewing_cos_limit;
         a.in_view = m->o_u.as<uint8_t>();
         a.px = m->o_f0.as<float>();
         a.py = m->o_f1.as<float>();
         a.pxr = m->o_f2.as<float>();
         a.lvl = m->o_i.as<int>();
         a.vcos = m->o_f3.as<float>();
-        a.skip = a.bad = nullptr;
-        a.n_in_view = nullptr;
         if ((st = m->flush())) return st;
         hipLaunchKernelGGL(frustum_kernel, dim3((n + 255) / 256), dim3(256), 0, m->stream, a);
         ORBFE_HIP(hipGetLastError());

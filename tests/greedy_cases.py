@@ -684,12 +684,14 @@ def local_mps(c):
                      proj_xr=pxr)
 
 
-def local_ties(seed, stereo=False, th=2.0, nnratio=0.8):
+def local_ties(seed, stereo=False, th=2.0, nnratio=0.8, b=None):
     """-> dict(f, lm, cam, th, nnratio): the local map as world points (identity pose) whose
-    isInFrustum outputs are the SearchByProjection inputs (local_mps)."""
-    b = Builder(2000 + seed)
-    _populate(b, TH_HIGH, stereo=stereo, spread=6.0 if th >= 2.0 else 3.0)
-    _fillers(b, 60, ("bad", "skip", "behind", "outside"))
+    isInFrustum outputs are the SearchByProjection inputs (local_mps).  b: a Builder that
+    already holds the keypoints and queries, in place of the seeded gadgets."""
+    if b is None:
+        b = Builder(2000 + seed)
+        _populate(b, TH_HIGH, stereo=stereo, spread=6.0 if th >= 2.0 else 3.0)
+        _fillers(b, 60, ("bad", "skip", "behind", "outside"))
     _shuffle_kp(b)
     tcw = np.hstack([np.eye(3), np.zeros((3, 1))]).astype(F32)
     m = len(b.q)
@@ -745,15 +747,19 @@ LAST_TCW = {"mono": (0.02, -0.01, 0.03), "near": (0.01, 0.0, 0.05), "forward": (
             "backward": (0.01, 0.0, 0.3)}
 
 
-def last_ties(seed, motion="mono", th=None, bins=None):
+def last_ties(seed, motion="mono", th=None, bins=None, b=None):
     """-> a scenarios.sbp_last_case dict plus th, mono, frame_mp, frame_mp_obs.  motion: mono,
-    near (stereo, |tlc.z| <= mb), forward, backward (tlc.z beyond mb either way)."""
+    near (stereo, |tlc.z| <= mb), forward, backward (tlc.z beyond mb either way).  b: as
+    local_ties'."""
     mono = motion == "mono"
     th = (15.0 if mono else 7.0) if th is None else th
-    b = Builder(3000 + seed, stride=2 if bins is not None else 1)
-    if bins is not None:
+    if b is not None:
+        pass
+    elif bins is not None:
+        b = Builder(3000 + seed, stride=2)
         _bins(b, bins)
     else:
+        b = Builder(3000 + seed)
         _populate(b, TH_HIGH, stereo=not mono)
         _fillers(b, 60, ("invalid", "outlier", "behind", "outside"))
     _shuffle_kp(b)
@@ -807,13 +813,17 @@ def last_prefix(c, m=None, n=None):
     return out
 
 
-def keyframe_ties(seed, th=3.0, orb_dist=64, cluster=0, bins=None):
+def keyframe_ties(seed, th=3.0, orb_dist=64, cluster=0, bins=None, b=None):
     """-> a scenarios.sbp_keyframe_case dict plus th, orb_dist.  cluster = 16 / 17: one more
-    point whose window holds exactly that many candidates (the fixed candidate slots hold 16)."""
-    b = Builder(4000 + seed, stride=2 if bins is not None else 1)
-    if bins is not None:
+    point whose window holds exactly that many candidates (the fixed candidate slots hold 16).
+    b: as local_ties'."""
+    if b is not None:
+        pass
+    elif bins is not None:
+        b = Builder(4000 + seed, stride=2)
         _bins(b, bins)
     else:
+        b = Builder(4000 + seed)
         _populate(b, orb_dist, kf=True, spread=3.0, n_sites=len(b.sites) - 1)
         _fillers(b, 40, ("invalid", "bad", "found", "outside"))
     if cluster:

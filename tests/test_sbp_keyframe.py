@@ -116,7 +116,7 @@ def test_oracle_vs_restatement(seed, th, od):
                                             (4, 40, 100, True)])
 def test_gpu_sbp_keyframe(seed, th, od, ori):
     """The host form: candidates in fixed slots (16 per map point, one kernel) and, when a point
-    has more (th = 40), the rerun on the CSR path from the saved slots — both bit-exact."""
+    has more (th = 40), the rerun on the CSR path from the untouched slots — both bit-exact."""
     from orbslam_mapsave_amd.native import ORBmatcher
     c = S.sbp_keyframe_case(seed)
     m = ORBmatcher(0.9, ori, device=0)
