@@ -542,6 +542,69 @@ int orbfe_fuse_search_batch_device(orbfe_matcher* m, int n_kf, const orbfe_keypo
                                    int mode, int32_t* d_best_idx, int32_t* d_best_dist,
                                    int32_t* d_status);
 
+/* Loop-closing ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw,
+ * const vector<MapPoint*>& vpPoints, vector<MapPoint*>& vpMatched, int th)
+ * (ORBmatcher.cc:293-406), called by LoopClosing::ComputeSim3 with ORBmatcher(0.75, true) and
+ * th = 10 on the loop keyframe's covisible points (LoopClosing.cc:376).  Per point the tests are
+ * those of Fuse's Sim3 overload (depth, KeyFrame::IsInImage, the 0.8 / 1.2 distance window, the
+ * 60-degree viewing angle, MapPoint::PredictScale, KeyFrame::GetFeaturesInArea without a level
+ * filter, octave in [lvl - 1, lvl]); the tail is greedy: a keypoint that holds a point before
+ * the call, or that an earlier point of the list took, is passed over (378, 399), and the best
+ * remaining candidate is accepted at a distance <= TH_LOW.
+ *   kf, tcw, cam, log_scale_factor : as for orbfe_fuse_search in ORBFE_FUSE_SIM3 mode — tcw is
+ *            the normalised [R|t] (R = sRcw / scw, t = tcw / scw, ORBmatcher.cc:302-305), which
+ *            the caller computes (include/orbfe_orbslam.hpp does).
+ *   points : n_mp world positions (x 3), normals (x 3), mfMinDistance / mfMaxDistance and
+ *            descriptors (x 32), in vpPoints order.
+ *   skip   : NULL or n_mp bytes: isBad() || spAlreadyFound.count(pMP) (320).  The reference
+ *            builds that set once before the loop, so a point listed twice may match twice; the
+ *            caller owns the flags and this call never changes them.
+ *   mp_ids : NULL or n_mp ids; a match writes mp_ids[i] (or i) into the keypoint's slot.
+ *   th     : the reference's int.
+ *   kf_matched : inout kf->n ids (vpMatched, -1 = NULL), caller-owned.
+ * *nmatches as returned.  A predicted scale level outside the pyramid returns
+ * ORBFE_ERR_UNSUPPORTED; such a point gets no match and every other result is valid.
+ * Synchronous; host buffers. */
+int orbfe_search_by_projection_sim3(orbfe_matcher* m, const orbfe_frame_view* kf,
+                                    const float* tcw, const orbfe_camera* cam,
+                                    float log_scale_factor, int n_mp, const float* mp_xyz,
+                                    const float* mp_normal, const float* mp_min_dist,
+                                    const float* mp_max_dist, const uint8_t* mp_desc,
+                                    const uint8_t* skip, const int32_t* mp_ids, int th,
+                                    int32_t* kf_matched, int32_t* nmatches);
+
+/* ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (ORBmatcher.cc:1105-1329),
+ * called inside the RANSAC loop of LoopClosing::ComputeSim3 with ORBmatcher(0.75, true) and
+ * th = 7.5 (LoopClosing.cc:324).  Each keyframe's map points are projected into the other
+ * keyframe and matched to the keypoint with the smallest descriptor distance (the MapPoint's
+ * descriptor against the keypoints', first in KeyFrame::GetFeaturesInArea order on ties, octave
+ * in [lvl - 1, lvl], accepted at <= TH_HIGH); a pair is kept when both directions chose it.
+ *   kf1, kf2 : the keyframes' mvKeysUn, mDescriptors, image bounds, grid constants and
+ *            mvScaleFactors (nlevels <= 16 each; the two may differ).
+ *   cam1   : pKF1's intrinsics, used in both directions (1108-1111).
+ *   t1w, t2w : row-major 3x4 [R|t] world -> camera of the two keyframes.
+ *   s12, s21 : row-major 3x4 [sR12|t12] and [sR21|t21] of lines 1122-1124, evaluated by the
+ *            caller (include/orbfe_orbslam.hpp does).
+ *   log_scale_factor1 / 2 : the keyframes' mfLogScaleFactor (the target's is the one read).
+ *   per keyframe k, kfk->n entries each, caller-owned: searchk[i] != 0 <=> feature i holds a
+ *            point that is not bad and is not already matched (vbAlreadyMatchedk, 1135-1145,
+ *            filters sources only); xyzk (x 3), min_distk / max_distk and desck (x 32) of that
+ *            point (entries with searchk[i] == 0 are not read for a result).
+ * match12[i1] = idx2 for the agreeing pairs (1310-1326), -1 otherwise; vn_match1 / vn_match2
+ * (each may be NULL) receive the two directions' own answers (vnMatch1, vnMatch2);
+ * *n_found = nFound.  A predicted scale level outside the target's pyramid returns
+ * ORBFE_ERR_UNSUPPORTED; that feature gets no match and every other result is valid.  Both
+ * directions run in one kernel launch; synchronous; host buffers. */
+int orbfe_search_by_sim3(orbfe_matcher* m, const orbfe_frame_view* kf1,
+                         const orbfe_frame_view* kf2, const orbfe_camera* cam1, const float* t1w,
+                         const float* t2w, const float* s12, const float* s21,
+                         float log_scale_factor1, float log_scale_factor2,
+                         const uint8_t* search1, const float* xyz1, const float* min_dist1,
+                         const float* max_dist1, const uint8_t* desc1, const uint8_t* search2,
+                         const float* xyz2, const float* min_dist2, const float* max_dist2,
+                         const uint8_t* desc2, float th, int32_t* match12, int32_t* vn_match1,
+                         int32_t* vn_match2, int32_t* n_found);
+
 /* MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:483-548) for n_mp map points at once
  * (LocalMapping calls it for every new / fused point, LocalMapping.cc:268, 489).  The
  * descriptors of map point i's observations in non-bad keyframes, in mObservations order, are
@@ -643,6 +706,42 @@ int orbfe_search_by_bow_batch_device(orbfe_matcher* m, float nnratio, int check_
                                      const int32_t* d_f_nn, const int32_t* d_f_node_ids,
                                      const int32_t* d_f_node_off, const int32_t* d_f_feat,
                                      int32_t* d_matches, int32_t* d_nmatches, int32_t* d_status);
+
+/* ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12)
+ * (ORBmatcher.cc:525-658), called by LoopClosing::ComputeSim3 with ORBmatcher(0.75, true) once
+ * per loop candidate (LoopClosing.cc:266).  Keyframe k: nk descriptors, keypoint angles
+ * (mvKeysUn), mp_okk[i] = GetMapPointMatches()[i] != NULL && !isBad() (561-565 for pKF1, 577-583
+ * for pKF2) and its FeatureVector (nnk nodes, CSR), all caller-owned host arrays.  Differences
+ * from orbfe_search_by_bow: the inner side needs a live map point too, a match needs
+ * bestDist1 < TH_LOW (strict, 601), and the output is indexed by the KF1 feature:
+ * matches12[i1] = the KF2 feature whose map point lands in vpMatches12[i1], or -1 (n1 entries);
+ * *nmatches as returned.  A common node holding more than 256 KF2 features, or a rotation bin
+ * beyond 30, returns ORBFE_ERR_UNSUPPORTED; a FeatureVector that repeats a
+ * feature index returns ORBFE_ERR_ARG.  Synchronous. */
+int orbfe_search_by_bow_keyframes(orbfe_matcher* m, float nnratio, int check_ori, int n1,
+                                  const uint8_t* desc1, const float* angle1,
+                                  const uint8_t* mp_ok1, int nn1, const int32_t* node_ids1,
+                                  const int32_t* node_off1, const int32_t* feat1, int n2,
+                                  const uint8_t* desc2, const float* angle2,
+                                  const uint8_t* mp_ok2, int nn2, const int32_t* node_ids2,
+                                  const int32_t* node_off2, const int32_t* feat2,
+                                  int32_t* matches12, int32_t* nmatches);
+/* Batched device form for ComputeSim3's candidate loop, which matches the current keyframe
+ * against every loop candidate: n_pairs (pKF1, pKF2) problems in one call (n_pairs <= 65535).
+ * Both sides are slots of one keyframe set in the layout orbfe_bow_transform_batch_device
+ * writes, with per-slot capacity cap: slot s holds descriptors at d_desc + s*cap*32, angles and
+ * map-point flags at s*cap, its FeatureVector's node ids and feature indices at s*cap, node
+ * offsets at s*(cap + 1) and node count d_nn[s].  Pair p matches slot d_pair_kf1[p] (pKF1)
+ * against slot d_pair_kf2[p]; d_matches12[p*cap + i1] = the KF2 feature matched to KF1 feature
+ * i1 or -1 (all cap entries written), d_nmatches[p] = the returned count.  *d_status = 0, or
+ * ORBFE_ERR_UNSUPPORTED / ORBFE_ERR_ARG (an offset or index outside its slot; that node is
+ * skipped).  Asynchronous on the matcher's stream. */
+int orbfe_search_by_bow_keyframes_batch_device(
+    orbfe_matcher* m, float nnratio, int check_ori, int n_pairs, const int32_t* d_pair_kf1,
+    const int32_t* d_pair_kf2, int cap, const uint8_t* d_desc, const float* d_angle,
+    const uint8_t* d_mp_ok, const int32_t* d_nn, const int32_t* d_node_ids,
+    const int32_t* d_node_off, const int32_t* d_feat, int32_t* d_matches12, int32_t* d_nmatches,
+    int32_t* d_status);
 
 /* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo)
  * (ORBmatcher.cc:660-826, CheckDistEpipolarLine 140-157) with ORBmatcher(nnratio, check_ori):

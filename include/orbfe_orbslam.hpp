@@ -6,6 +6,7 @@
 // on the C++ side only; nothing throws across the C ABI.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <stdexcept>
 #include <string>
@@ -178,6 +179,18 @@ struct KeyFrameData {
     const float* level_sigma2 = nullptr;
 };
 
+// The map points a keyframe's features hold (pKF->GetMapPointMatches()) as flat arrays, one entry
+// per feature (owns nothing): ids (-1 = NULL), isBad(), GetWorldPos() (n x 3), mfMinDistance /
+// mfMaxDistance and GetDescriptor() (n x 32).  Entries of a NULL slot are not read.
+struct KeyFramePoints {
+    const int* ids = nullptr;
+    const uint8_t* bad = nullptr;
+    const float* xyz = nullptr;
+    const float* min_dist = nullptr;
+    const float* max_dist = nullptr;
+    const uint8_t* desc = nullptr;
+};
+
 // Rows 0-2 of the 4x4 Sim3 matrix Scw = [s R | t] (row-major 3x4), LoopClosing's corrected pose.
 struct Sim3 {
     float m[12];
@@ -308,11 +321,8 @@ public:
     int Fuse(const FrameData& KF, const Sim3& Scw, const orbfe_camera& cam, float logScaleFactor,
              const FusePoints& pts, float th, Skipped skipped, Occupied slot_occupied,
              OnOccupied on_occupied, OnEmpty on_empty) {
-        const float* s = Scw.m;
-        const float scw = (float)std::sqrt((double)s[0] * s[0] + (double)s[1] * s[1] + (double)s[2] * s[2]);
-        const float inv = (float)(1.0 / (double)scw);
         float T[12];
-        for (int i = 0; i < 12; ++i) T[i] = s[i] * inv;
+        normalise(Scw, T);
         const std::vector<float> unused(KF.scale_factors.size(), 0.f);
         return fuse(KF, T, cam, logScaleFactor, unused, pts, th, ORBFE_FUSE_SIM3, skipped,
                     slot_occupied, on_occupied, on_empty);
@@ -355,6 +365,126 @@ public:
         return n;
     }
 
+    // SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12)
+    // (ORBmatcher.cc:525-658), as LoopClosing::ComputeSim3 calls it per loop candidate.  Only
+    // ids and bad of P1 / P2 are read (a feature takes part when it holds a point that is not
+    // bad, 561-565 and 577-583); fv1 / fv2 are the keyframes' mFeatVec.  vpMatches12 is
+    // overwritten: KF1.keys_un.size() entries, P2.ids[idx2] for a match, -1 = NULL.  Returns
+    // nmatches.
+    int SearchByBoW(const FrameData& KF1, const KeyFramePoints& P1, const FeatureVectorView& fv1,
+                    const FrameData& KF2, const KeyFramePoints& P2, const FeatureVectorView& fv2,
+                    std::vector<int>& vpMatches12) {
+        const size_t N1 = KF1.keys_un.size(), N2 = KF2.keys_un.size();
+        kf_angle_.resize(N1);
+        sim3_search1_.resize(N1);
+        for (size_t i = 0; i < N1; ++i) {
+            kf_angle_[i] = KF1.keys_un[i].angle;
+            sim3_search1_[i] = P1.ids[i] >= 0 && !P1.bad[i];
+        }
+        f_angle_.resize(N2);
+        sim3_search2_.resize(N2);
+        for (size_t i = 0; i < N2; ++i) {
+            f_angle_[i] = KF2.keys_un[i].angle;
+            sim3_search2_[i] = P2.ids[i] >= 0 && !P2.bad[i];
+        }
+        sim3_m12_.assign(N1, -1);
+        int n = 0;
+        check("orbfe_search_by_bow_keyframes",
+              orbfe_search_by_bow_keyframes(
+                  m_, mfNNratio, mbCheckOrientation, (int)N1, KF1.descriptors.data(),
+                  kf_angle_.data(), sim3_search1_.data(), fv1.nn, fv1.node_ids, fv1.node_off,
+                  fv1.feat, (int)N2, KF2.descriptors.data(), f_angle_.data(),
+                  sim3_search2_.data(), fv2.nn, fv2.node_ids, fv2.node_off, fv2.feat,
+                  sim3_m12_.data(), &n));
+        vpMatches12.assign(N1, -1);
+        for (size_t i = 0; i < N1; ++i)
+            if (sim3_m12_[i] >= 0) vpMatches12[i] = P2.ids[sim3_m12_[i]];
+        return n;
+    }
+
+    // SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints,
+    // vector<MapPoint*>& vpMatched, int th) (ORBmatcher.cc:293-406), as LoopClosing::ComputeSim3
+    // calls it (th = 10).  Scw is decomposed as for Fuse (302-305).  pts.skip is isBad() per
+    // point (NULL: none is bad); spAlreadyFound (309-310) is built here, once, from vpMatched as
+    // it stands before the call and mp_ids (NULL: a point's id is its index in the list), so a
+    // point listed twice can match twice, as in the reference.  vpMatched: KF's keypoint slots as
+    // ids, -1 = NULL; a match writes the point's id.  Returns nmatches.  A predicted level
+    // outside the pyramid throws Error(ORBFE_ERR_UNSUPPORTED) with vpMatched updated for every
+    // other point.
+    int SearchByProjection(const FrameData& KF, const Sim3& Scw, const orbfe_camera& cam,
+                           float logScaleFactor, const FusePoints& pts, const int* mp_ids,
+                           std::vector<int>& vpMatched, int th) {
+        float T[12];
+        normalise(Scw, T);
+        vpMatched.resize(KF.keys_un.size(), -1);
+        std::vector<int> found(vpMatched);
+        std::sort(found.begin(), found.end());
+        loop_skip_.assign(pts.n, 0);
+        for (int i = 0; i < pts.n; ++i) {
+            const int id = mp_ids ? mp_ids[i] : i;
+            loop_skip_[i] = (pts.skip && pts.skip[i]) ||
+                            (id >= 0 && std::binary_search(found.begin(), found.end(), id));
+        }
+        const orbfe_frame_view v = KF.view();
+        int n = 0;
+        check("orbfe_search_by_projection_sim3",
+              orbfe_search_by_projection_sim3(m_, &v, T, &cam, logScaleFactor, pts.n, pts.xyz,
+                                              pts.normal, pts.min_dist, pts.max_dist, pts.desc,
+                                              loop_skip_.data(), mp_ids, th, vpMatched.data(), &n));
+        return n;
+    }
+
+    // SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12, s12, R12, t12,
+    // th) (ORBmatcher.cc:1105-1329), as the RANSAC loop of LoopClosing::ComputeSim3 calls it
+    // (th = 7.5).  T1w / T2w: the keyframes' row-major 3x4 [R|t]; R12 3 x 3 row-major, t12 3.
+    // Lines 1122-1124 are evaluated here: sR12 = every entry times the float s12, sR21 = every
+    // entry of R12^T times (float)(1.0 / (double)s12), t21 = -((a0 t0 + a1 t1) + a2 t2) per row
+    // (DESIGN.md H16).  vpMatches12: KF1.keys_un.size() ids, -1 = NULL, as it stands before the
+    // call; index_in_kf2(id) is pMP->GetIndexInKeyFrame(pKF2) for such an id.  The agreeing
+    // pairs (1310-1326) are written as vpMatches12[i1] = P2.ids[idx2]; returns nFound.
+    template <class IndexInKF2>
+    int SearchBySim3(const FrameData& KF1, const KeyFramePoints& P1, const float* T1w,
+                     float logScaleFactor1, const FrameData& KF2, const KeyFramePoints& P2,
+                     const float* T2w, float logScaleFactor2, const orbfe_camera& cam1,
+                     std::vector<int>& vpMatches12, float s12, const float* R12, const float* t12,
+                     float th, IndexInKF2 index_in_kf2) {
+        const int N1 = (int)KF1.keys_un.size(), N2 = (int)KF2.keys_un.size();
+        vpMatches12.resize(N1, -1);
+        float S12[12], S21[12];
+        const float inv = (float)(1.0 / (double)s12);
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) {
+                S12[4 * r + c] = s12 * R12[3 * r + c];
+                S21[4 * r + c] = R12[3 * c + r] * inv;
+            }
+            S12[4 * r + 3] = t12[r];
+        }
+        for (int r = 0; r < 3; ++r)
+            S21[4 * r + 3] = -((S21[4 * r] * t12[0] + S21[4 * r + 1] * t12[1]) + S21[4 * r + 2] * t12[2]);
+        sim3_search1_.assign(N1, 0);
+        sim3_search2_.assign(N2, 0);
+        for (int i = 0; i < N2; ++i) sim3_search2_[i] = P2.ids[i] >= 0 && !P2.bad[i];
+        for (int i = 0; i < N1; ++i) {
+            sim3_search1_[i] = P1.ids[i] >= 0 && !P1.bad[i] && vpMatches12[i] < 0;
+            if (vpMatches12[i] >= 0) {  // 1135-1145
+                const int idx2 = index_in_kf2(vpMatches12[i]);
+                if (idx2 >= 0 && idx2 < N2) sim3_search2_[idx2] = 0;
+            }
+        }
+        sim3_m12_.assign(N1, -1);
+        const orbfe_frame_view v1 = KF1.view(), v2 = KF2.view();
+        int n = 0;
+        check("orbfe_search_by_sim3",
+              orbfe_search_by_sim3(m_, &v1, &v2, &cam1, T1w, T2w, S12, S21, logScaleFactor1,
+                                   logScaleFactor2, sim3_search1_.data(), P1.xyz, P1.min_dist,
+                                   P1.max_dist, P1.desc, sim3_search2_.data(), P2.xyz, P2.min_dist,
+                                   P2.max_dist, P2.desc, th, sim3_m12_.data(), nullptr, nullptr,
+                                   &n));
+        for (int i = 0; i < N1; ++i)
+            if (sim3_m12_[i] >= 0) vpMatches12[i] = P2.ids[sim3_m12_[i]];
+        return n;
+    }
+
     orbfe_matcher* handle() { return m_; }
 
 private:
@@ -384,6 +514,13 @@ private:
         }
         return nFused;
     }
+    // Scw -> the normalised [Rcw|tcw] of ORBmatcher.cc:302-305 / 989-992.
+    static void normalise(const Sim3& Scw, float T[12]) {
+        const float* s = Scw.m;
+        const float scw = (float)std::sqrt((double)s[0] * s[0] + (double)s[1] * s[1] + (double)s[2] * s[2]);
+        const float inv = (float)(1.0 / (double)scw);
+        for (int i = 0; i < 12; ++i) T[i] = s[i] * inv;
+    }
     static void prepare(FrameData& F) {
         F.map_points.resize(F.keys_un.size(), -1);
         F.map_point_obs.resize(F.keys_un.size(), 0);
@@ -394,6 +531,10 @@ private:
     std::vector<float> kf_angle_, f_angle_;  // SearchByBoW: the keypoints' angles as arrays
     std::vector<int> fuse_idx_;              // Fuse: best_idx of the device search
     std::vector<int> tri_m12_;               // SearchForTriangulation: vMatches12
+    std::vector<uint8_t> loop_skip_;         // loop-closing SearchByProjection: the skip flags
+    // SearchBySim3 / SearchByBoW(KF, KF): the per-feature masks and the index-valued matches
+    std::vector<uint8_t> sim3_search1_, sim3_search2_;
+    std::vector<int> sim3_m12_;
 };
 
 }  // namespace orbfe

@@ -9,5 +9,6 @@
 #include "orbfe_match_api.hip"
 #include "orbfe_fuse.hip"
 #include "orbfe_bow.hip"
+#include "orbfe_loop.hip"
 #include "orbfe_triangulate.hip"
 #include "orbfe_archive.hip"

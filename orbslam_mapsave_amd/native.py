@@ -7,7 +7,9 @@ reference interface for the hot path:
   (include/ORBmatcher.h:38-110): ``DescriptorDistance``, ``SearchForInitialization`` and the two
   tracking ``SearchByProjection`` overloads, the search of ``Fuse`` (``FuseSearch``,
   ``fuse_search_batch_device``), ``SearchForTriangulation`` (and
-  ``search_for_triangulation_batch_device``), plus the brute-force match of config 3.
+  ``search_for_triangulation_batch_device``), the loop-closing matchers
+  (``SearchByBoWKeyFrames``, ``SearchBySim3``, ``SearchByProjectionSim3``), plus the brute-force
+  match of config 3.
 
 There is no CPU fallback: importing works anywhere, but constructing an extractor or matcher
 needs the built library and a gfx950 device, and raises otherwise.
@@ -50,6 +52,8 @@ EXPORTED = [
     "orbfe_vocabulary_create", "orbfe_vocabulary_destroy", "orbfe_vocabulary_info",
     "orbfe_vocabulary_set_stream", "orbfe_bow_transform", "orbfe_bow_transform_batch_device",
     "orbfe_search_by_bow", "orbfe_search_by_bow_batch_device",
+    "orbfe_search_by_bow_keyframes", "orbfe_search_by_bow_keyframes_batch_device",
+    "orbfe_search_by_projection_sim3", "orbfe_search_by_sim3",
     "orbfe_search_for_triangulation", "orbfe_search_for_triangulation_batch_device",
     "orbfe_archive_mat_bytes",
     "orbfe_archive_write_keypoints_device", "orbfe_archive_read_keypoints_device",
@@ -879,6 +883,111 @@ class ORBmatcher:
             v(d_kf_nn), v(d_kf_node_ids), v(d_kf_node_off), v(d_kf_feat), f_cap, v(d_f_desc),
             v(d_f_angle), v(d_f_nn), v(d_f_node_ids), v(d_f_node_off), v(d_f_feat),
             v(d_matches), v(d_nmatches), v(d_status)))
+
+    def SearchByBoWKeyFrames(self, desc1, angle1, mp_ok1, fv1, desc2, angle2, mp_ok2, fv2):
+        """SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) (ORBmatcher.cc:525-658)
+        through orbfe_search_by_bow_keyframes; mp_ok*: the feature holds a map point that is not
+        bad; fv*: (node_ids, node_off, feat) FeatureVectors.  Returns (matches12, nmatches):
+        per KF1 feature the KF2 feature whose map point it takes, or -1."""
+        d1 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32)
+        d2 = np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32)
+        a1 = np.ascontiguousarray(angle1, np.float32)
+        a2 = np.ascontiguousarray(angle2, np.float32)
+        ok1 = np.ascontiguousarray(mp_ok1, np.uint8)
+        ok2 = np.ascontiguousarray(mp_ok2, np.uint8)
+        n1, o1, f1 = (np.ascontiguousarray(x, np.int32) for x in fv1)
+        n2, o2, f2 = (np.ascontiguousarray(x, np.int32) for x in fv2)
+        out = np.full(len(d1), -1, np.int32)
+        nm = C.c_int32(0)
+        st = lib().orbfe_search_by_bow_keyframes(
+            self._h, C.c_float(self.mfNNratio), int(self.mbCheckOrientation), len(d1), ptr(d1),
+            ptr(a1), ptr(ok1), len(n1), ptr(n1), ptr(o1), ptr(f1), len(d2), ptr(d2), ptr(a2),
+            ptr(ok2), len(n2), ptr(n2), ptr(o2), ptr(f2), ptr(out), C.byref(nm))
+        if st != ORBFE_OK:
+            e = OrbfeError("orbfe_search_by_bow_keyframes", st)
+            e.results = (out, nm.value)
+            raise e
+        return out, nm.value
+
+    def search_by_bow_keyframes_batch_device(self, n_pairs: int, d_pair_kf1: int,
+                                             d_pair_kf2: int, cap: int, d_desc: int,
+                                             d_angle: int, d_mp_ok: int, d_nn: int,
+                                             d_node_ids: int, d_node_off: int, d_feat: int,
+                                             d_matches12: int, d_nmatches: int,
+                                             d_status: int) -> None:
+        """SearchByBoW(pKF1, pKF2, ...) over n_pairs pairs of slots of one keyframe set
+        (LoopClosing::ComputeSim3's candidate loop, LoopClosing.cc:266); device pointers in the
+        layout of Vocabulary.transform_batch_device.  Asynchronous on the matcher's stream."""
+        v = C.c_void_p
+        _check("orbfe_search_by_bow_keyframes_batch_device",
+               lib().orbfe_search_by_bow_keyframes_batch_device(
+                   self._h, C.c_float(self.mfNNratio), int(self.mbCheckOrientation), n_pairs,
+                   v(d_pair_kf1), v(d_pair_kf2), cap, v(d_desc), v(d_angle), v(d_mp_ok), v(d_nn),
+                   v(d_node_ids), v(d_node_off), v(d_feat), v(d_matches12), v(d_nmatches),
+                   v(d_status)))
+
+    def SearchByProjectionSim3(self, kf: Frame, tcw, cam: Camera, log_scale: float, mp_xyz,
+                               mp_normal, mp_min_dist, mp_max_dist, mp_desc, th: int = 10,
+                               skip=None, mp_ids=None, kf_matched=None):
+        """Loop-closing SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)
+        (ORBmatcher.cc:293-406) through orbfe_search_by_projection_sim3, with the normalised
+        [R|t] of Scw.  skip: isBad() || spAlreadyFound.count(pMP) per point; kf_matched: the
+        keyframe's slots before the call (ids, -1 = NULL).  Returns (kf_matched, nmatches).  A
+        predicted level outside the pyramid raises OrbfeError(ORBFE_ERR_UNSUPPORTED) carrying
+        the valid results of every other point as ``.results``."""
+        a = [np.ascontiguousarray(tcw, np.float32).reshape(12),
+             np.ascontiguousarray(mp_xyz, np.float32).reshape(-1, 3),
+             np.ascontiguousarray(mp_normal, np.float32).reshape(-1, 3),
+             np.ascontiguousarray(mp_min_dist, np.float32),
+             np.ascontiguousarray(mp_max_dist, np.float32),
+             np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)]
+        n = len(a[1])
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        ids = None if mp_ids is None else np.ascontiguousarray(mp_ids, np.int32)
+        km = (np.full(kf.n, -1, np.int32) if kf_matched is None
+              else np.ascontiguousarray(kf_matched, np.int32).copy())
+        nm = C.c_int32(0)
+        kv = kf.view()
+        st = lib().orbfe_search_by_projection_sim3(
+            self._h, C.byref(kv), ptr(a[0]), C.byref(cam), C.c_float(log_scale), n,
+            *(ptr(x) for x in a[1:]), ptr(sk), ptr(ids), int(th), ptr(km), C.byref(nm))
+        if st != ORBFE_OK:
+            e = OrbfeError("orbfe_search_by_projection_sim3", st)
+            e.results = (km, nm.value)
+            raise e
+        return km, nm.value
+
+    def SearchBySim3(self, kf1: Frame, kf2: Frame, cam1: Camera, t1w, t2w, s12, s21,
+                     log_scale1: float, log_scale2: float, pts1, pts2, th: float = 7.5):
+        """SearchBySim3 (ORBmatcher.cc:1105-1329) through orbfe_search_by_sim3.  s12 / s21: the
+        3 x 4 [sR12|t12] and [sR21|t21] of lines 1122-1124; pts*: per keyframe a tuple
+        (search, xyz, min_dist, max_dist, desc) over its features, search[i] != 0 <=> the
+        feature holds a point that is not bad and is not already matched.  Returns (match12,
+        vnMatch1, vnMatch2, nFound).  A predicted level outside the target's pyramid raises
+        OrbfeError(ORBFE_ERR_UNSUPPORTED) carrying the other results as ``.results``."""
+        mats = [np.ascontiguousarray(x, np.float32).reshape(12) for x in (t1w, t2w, s12, s21)]
+        p = []
+        for kf, (search, xyz, mind, maxd, desc) in ((kf1, pts1), (kf2, pts2)):
+            q = [np.ascontiguousarray(search, np.uint8),
+                 np.ascontiguousarray(xyz, np.float32).reshape(-1, 3),
+                 np.ascontiguousarray(mind, np.float32), np.ascontiguousarray(maxd, np.float32),
+                 np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)]
+            assert all(len(x) == kf.n for x in q)
+            p += q
+        m12 = np.full(kf1.n, -1, np.int32)
+        vn1 = np.full(kf1.n, -1, np.int32)
+        vn2 = np.full(kf2.n, -1, np.int32)
+        nf = C.c_int32(0)
+        v1, v2 = kf1.view(), kf2.view()
+        st = lib().orbfe_search_by_sim3(
+            self._h, C.byref(v1), C.byref(v2), C.byref(cam1), *(ptr(x) for x in mats),
+            C.c_float(log_scale1), C.c_float(log_scale2), *(ptr(x) for x in p), C.c_float(th),
+            ptr(m12), ptr(vn1), ptr(vn2), C.byref(nf))
+        if st != ORBFE_OK:
+            e = OrbfeError("orbfe_search_by_sim3", st)
+            e.results = (m12, vn1, vn2, nf.value)
+            raise e
+        return m12, vn1, vn2, nf.value
 
     def SearchForTriangulation(self, KF1: Frame, has_mp1, fv1, KF2: Frame, has_mp2, fv2, F12,
                                epipole, level_sigma2, bOnlyStereo: bool = False,

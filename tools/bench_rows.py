@@ -584,10 +584,167 @@ def row_bow(tmpdir):
     m.close()
 
 
+def jrow(row, unit, units, t, note, **extra):
+    line = {"row": row, "unit": unit, "value": round(units / t, 2), "ms_per_call": round(t * 1e3, 4),
+            "units_per_call": units, "cpu_value": None, "note": note}
+    line.update(extra)
+    print(json.dumps(line), flush=True)
+
+
+def row_loop():
+    """The three matchers of LoopClosing::ComputeSim3, each beside the existing row it should
+    resemble, measured in the same process: the loop SearchByProjection(pKF, Scw, ...) against the
+    relocalisation SearchByProjection (the same driver), SearchBySim3 against two Sim3
+    orbfe_fuse_search calls at the same N (it does that work in one launch), SearchByBoW(pKF1,
+    pKF2) against SearchByBoW(pKF, F), host form and batch, at the same shapes.  No CPU leg: the
+    oracle has no port of these matchers."""
+    import fuse_cases as FC
+    import loop_cases as LC
+    import scenarios as S
+    from test_bow import pack_slots
+    # -- loop SearchByProjection / relocalisation SearchByProjection
+    c = LC.sbp_case(0)
+    m = native.ORBmatcher(0.75, True, device=0)
+    sargs = (c["kf"], c["tcw"], c["cam"], c["log_scale"], c["xyz"], c["normal"], c["min_dist"],
+             c["max_dist"], c["desc"])
+    skw = dict(th=10, skip=c["skip"], mp_ids=c["ids"], kf_matched=c["matched0"])
+    nm = m.SearchByProjectionSim3(*sargs, **skw)[1]
+    t = timed(lambda: m.SearchByProjectionSim3(*sargs, **skw), 100)
+    r = S.sbp_keyframe_case(0)
+    rargs = (r["cur"], r["tcw_cur"], r["cam"], r["log_scale"], r["kf_angle"], r["kf_valid"],
+             r["kf_bad"], r["found"], r["kf_xyz"], r["kf_desc"], r["kf_min"], r["kf_max"], 10, 100)
+    rkw = dict(frame_mp=r["frame_mp"], kf_ids=r["kf_ids"])
+    m.SearchByProjectionKeyFrame(*rargs, **rkw)
+    tr = timed(lambda: m.SearchByProjectionKeyFrame(*rargs, **rkw), 100)
+    jrow(f"loop SearchByProjection(pKF, Scw, vpPoints, vpMatched, th 10) (host ABI, {len(c['xyz'])} "
+         f"points, {c['kf'].n} kp)", "calls/s", 1, t,
+         "host ABI (uploads included): scatter, grid, fixed-slot candidates, resolver, gather; one "
+         "wait on a done word", nmatches=nm, rounds=m.last_rounds(),
+         comparator_ms=round(tr * 1e3, 4), over_comparator=round(t / tr, 3),
+         comparator=f"relocalisation SearchByProjection host form ({len(r['kf_valid'])} points, "
+         f"{r['cur'].n} kp, th 10), same process")
+    # -- SearchBySim3 / two Sim3 Fuse searches at the same N
+    s = LC.sim3_case(0)
+    _, _, s1, s2 = LC.masks(s)
+    S12, S21 = LC.sim3_mats(s["s12"], s["R12"], s["t12"])
+    p1, p2 = s["pts1"], s["pts2"]
+    a3 = (s["kf1"], s["kf2"], s["cam1"], s["T1w"], s["T2w"], S12, S21, s["log1"], s["log2"],
+          (s1, p1["xyz"], p1["min_dist"], p1["max_dist"], p1["desc"]),
+          (s2, p2["xyz"], p2["min_dist"], p2["max_dist"], p2["desc"]))
+    nf = m.SearchBySim3(*a3, th=7.5)[3]
+    t = timed(lambda: m.SearchBySim3(*a3, th=7.5), 100)
+    isg = FC.inv_sigma2()
+    s12f = float(s["s12"])
+
+    def fuse_pose(Tsw, Sm, sc):
+        """The normalised [R|t] under which Fuse's Sim3 search projects a source keyframe's
+        points where SearchBySim3 does; its distance is the world one, 1 / sc times ‖p3Dc‖, so
+        the distance bounds are scaled alike and both predict the same levels."""
+        Tsw, Sm = Tsw.astype(np.float64), Sm.astype(np.float64)
+        R = Sm[:, :3] / sc @ Tsw[:, :3]
+        t = (Sm[:, :3] @ Tsw[:, 3] + Sm[:, 3]) / sc
+        return np.hstack([R, t[:, None]]).astype(np.float32)
+    fa = [(s["kf2"], fuse_pose(s["T1w"], S21, 1.0 / s12f), s["cam1"], s["log2"], isg, p1["xyz"],
+           p1["normal"], p1["min_dist"] * np.float32(s12f), p1["max_dist"] * np.float32(s12f),
+           p1["desc"], 7.5, FC.SIM3),
+          (s["kf1"], fuse_pose(s["T2w"], S12, s12f), s["cam1"], s["log1"], isg, p2["xyz"],
+           p2["normal"], p2["min_dist"] / np.float32(s12f), p2["max_dist"] / np.float32(s12f),
+           p2["desc"], 7.5, FC.SIM3)]
+
+    def two_fuse():
+        return [m.FuseSearch(*a)[2] for a in fa]
+    nfuse = two_fuse()
+    tf = timed(two_fuse, 100)
+    jrow(f"SearchBySim3 (host ABI, {s['kf1'].n} x {s['kf2'].n} features, th 7.5)", "calls/s", 1, t,
+         "host ABI (uploads included): scatter, two grids, one search launch for both directions, "
+         "the agreement, gather; one wait on a done word", n_found=nf, comparator_found=nfuse,
+         comparator_ms=round(tf * 1e3, 4), over_comparator=round(t / tf, 3),
+         comparator="two orbfe_fuse_search calls in Sim3 mode on the same keyframes and points "
+         "(th 7.5), same process")
+    m.close()
+    # -- SearchByBoW(pKF1, pKF2) / SearchByBoW(pKF, F): host form, then the batch
+    f0 = S.extract_frame(0, 1000, ini=20)
+    parent, word, desc, weight = vocab_arrays(10, 6, 0, anchors=f0.desc[::97])
+    import ctypes as C
+    st = C.c_int(0)
+    h = native.lib().orbfe_vocabulary_create(10, 6, 0, 0, len(parent), native.ptr(parent),
+                                             native.ptr(word), native.ptr(desc), native.ptr(weight), 0,
+                                             C.byref(st))
+    assert h, st.value
+    ov = native.Vocabulary.__new__(native.Vocabulary)   # the FeatureVectors come from the device
+    ov._h = C.c_void_p(h)
+    kf, f = f0, S.extract_frame(0, 1000, shift=(2, -3), ini=20)
+    kf_fv, f_fv = ov.transform(kf.desc, 4)[2:], ov.transform(f.desc, 4)[2:]
+    ok1, ok2 = np.ones(kf.n, np.uint8), np.ones(f.n, np.uint8)
+    m = native.ORBmatcher(0.75, True, device=0)
+    kk = (kf.desc, kf.keys["angle"], ok1, kf_fv, f.desc, f.keys["angle"], ok2, f_fv)
+    kfr = (kf.desc, kf.keys["angle"], ok1, kf_fv, f.desc, f.keys["angle"], f_fv)
+    nkk = m.SearchByBoWKeyFrames(*kk)[1]
+    t = timed(lambda: m.SearchByBoWKeyFrames(*kk), 100)
+    m.SearchByBoW(*kfr)
+    tb = timed(lambda: m.SearchByBoW(*kfr), 100)
+    jrow(f"SearchByBoW(pKF1, pKF2) (host ABI, {kf.n} x {f.n} features, levelsup 4)", "calls/s", 1, t,
+         "host ABI (uploads included): the pair-indexed path with one pair — scatter, init, search "
+         "(orientation filter in the last workgroup), gather", nmatches=nkk,
+         comparator_ms=round(tb * 1e3, 4), over_comparator=round(t / tb, 3),
+         comparator="SearchByBoW(pKF, F) host form on the same two feature sets (its gathered "
+         "one-launch path), same process")
+    P, cap = 64, 1100
+    kfs = [S.extract_frame(q, 1000, shift=(q % 5, -(q % 3)), ini=20) for q in range(8)]
+    rng = np.random.Generator(np.random.PCG64(1))
+    items = [(x.desc, x.keys["angle"], (rng.uniform(size=x.n) < 0.8).astype(np.uint8),
+              ov.transform(x.desc, 4)[2:]) for x in kfs]
+    cur = (f.desc, f.keys["angle"], ok2, f_fv)
+    K = [torch.from_numpy(x).to(DEV) for x in pack_slots(items + [cur], cap)]
+    pk = torch.arange(P, dtype=torch.int32, device=DEV) % len(items)
+    pc = torch.full((P,), len(items), dtype=torch.int32, device=DEV)
+    pz = torch.zeros(P, dtype=torch.int32, device=DEV)
+    out = torch.empty((P, cap), dtype=torch.int32, device=DEV)
+    nmv = torch.empty(P, dtype=torch.int32, device=DEV)
+    stv = torch.empty(1, dtype=torch.int32, device=DEV)
+    m.set_stream(torch.cuda.current_stream(DEV).cuda_stream)
+    kp = [x.data_ptr() for x in K]
+
+    def gokk():   # the current keyframe (the last slot) against P candidates
+        m.search_by_bow_keyframes_batch_device(P, pc.data_ptr(), pk.data_ptr(), cap, kp[0], kp[1],
+                                               kp[2], kp[3], kp[4], kp[5], kp[6], out.data_ptr(),
+                                               nmv.data_ptr(), stv.data_ptr())
+    t = timed(gokk, 100)
+    assert int(stv[0]) == 0
+    tot = int(nmv.sum())
+
+    def gokk_swapped():   # the candidates as pKF1: the outer / inner shape of the comparator
+        m.search_by_bow_keyframes_batch_device(P, pk.data_ptr(), pc.data_ptr(), cap, kp[0], kp[1],
+                                               kp[2], kp[3], kp[4], kp[5], kp[6], out.data_ptr(),
+                                               nmv.data_ptr(), stv.data_ptr())
+    ts = timed(gokk_swapped, 100)
+    assert int(stv[0]) == 0
+    F = [x[len(items):].contiguous() for x in K]
+    fp = [x.data_ptr() for x in F]
+
+    def gob():    # SearchByBoW's batch: the same candidates as keyframes, the same frame
+        m.search_by_bow_batch_device(P, pk.data_ptr(), pz.data_ptr(), cap, kp[0], kp[1], kp[2],
+                                     kp[3], kp[4], kp[5], kp[6], cap, fp[0], fp[1], fp[3], fp[4],
+                                     fp[5], fp[6], out.data_ptr(), nmv.data_ptr(), stv.data_ptr())
+    tb = timed(gob, 100)
+    assert int(stv[0]) == 0
+    jrow(f"SearchByBoW(pKF1, pKF2), ComputeSim3's candidate loop (keyframe vs {P} candidates, "
+         f"~{kf.n} features)", "pairs/s", P, t,
+         "device batch, FeatureVectors resident; 2 launches (init; search with the orientation "
+         "filter in each pair's last workgroup); issued back to back", matches=tot,
+         us_per_pair=round(t * 1e6 / P, 3), comparator_ms=round(tb * 1e3, 4),
+         over_comparator=round(t / tb, 3), swapped_ms=round(ts * 1e3, 4),
+         swapped_over_comparator=round(ts / tb, 3),
+         comparator=f"orbfe_search_by_bow_batch_device on the same slots ({P} pairs), same process")
+    m.close()
+    ov.close()
+
+
 if __name__ == "__main__":
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         rows = {"single": row_single, "color": row_color, "stereo": row_stereo, "reloc": row_reloc, "fuse": row_fuse, "triangulation": row_triangulation, "track": row_track,
-                "distinctive": row_distinctive, "bow": lambda: row_bow(td)}
+                "distinctive": row_distinctive, "bow": lambda: row_bow(td),
+                "loop": row_loop}
         for name in (sys.argv[1:] or list(rows)):
             rows[name]()
