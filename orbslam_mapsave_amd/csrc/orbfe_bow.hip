@@ -252,17 +252,19 @@ struct BowMatchArgs {
     int out_n;
 };
 
-// One workgroup per pair: vpMapPointMatches = NULL (164), empty histogram, nmatches = 0, the
-// pair's finished-workgroup counter; workgroup 0 clears the status.
-__global__ __launch_bounds__(256) void bow_init_kernel(BowMatchArgs a) {
+// The start state of a search over pairs (SearchByBoW's two forms and SearchForTriangulation),
+// one workgroup per pair: the pair's cap match slots NULL (-1), empty histogram, nmatches = 0,
+// the pair's finished-workgroup counter; workgroup 0 clears the status.
+__global__ __launch_bounds__(256) void pair_init_kernel(int* matches, int cap, int* hist, int* nm,
+                                                        int* done, int* status) {
     const int p = blockIdx.x;
-    int* mt = a.matches + (size_t)p * a.f_cap;
-    for (int j = threadIdx.x; j < a.f_cap; j += 256) mt[j] = -1;
-    if (threadIdx.x < 32) a.hist[p * 32 + threadIdx.x] = 0;
+    int* mt = matches + (size_t)p * cap;
+    for (int j = threadIdx.x; j < cap; j += 256) mt[j] = -1;
+    if (threadIdx.x < 32) hist[p * 32 + threadIdx.x] = 0;
     if (threadIdx.x == 0) {
-        a.nm[p] = 0;
-        a.done[p] = 0;
-        if (p == 0) *a.status = 0;
+        nm[p] = 0;
+        done[p] = 0;
+        if (p == 0) *status = 0;
     }
 }
 
@@ -284,23 +286,28 @@ __device__ void ori_filter(int* matches, const int* bins, const int* hist, int* 
     }
     if (removed) atomicSub(nm, removed);
 }
-__device__ void bow_ori_filter(const BowMatchArgs& a, int p) {
-    ori_filter(a.matches + (size_t)p * a.f_cap, a.bins + (size_t)p * a.f_cap, a.hist + p * 32,
-               &a.nm[p], a.f_cap);
-}
-
-// A frame feature belongs to exactly one vocabulary node, so the blocking
-// (vpMapPointMatches[realIdxF] != NULL) only couples keyframe features of the same common node:
-// each node's loop (198-245) is run by one wave, in the reference's order, and the nodes run in
-// parallel (waves stride over the keyframe's nodes; grid.y = pairs).  Lanes hold the node's
-// frame features (candidate rank r = lane + 64 j, i.e. vIndicesF order); for each keyframe
-// feature the wave computes every unmatched candidate's distance, best = min (distance << 16 |
-// rank) -- the first minimum in order -- and second = the smallest distance of the other
-// candidates, which is exactly what the sequential best/second update yields.  The rotation
-// histogram is accumulated with atomics; bow_ori_kernel then applies ComputeThreeMaxima
-// (259-281) and clears the slots of the non-top bins.
+// A feature belongs to exactly one vocabulary node, so the blocking (vpMapPointMatches[realIdxF]
+// != NULL, 212; vbMatched2, 579) only couples outer features of the same common node: each
+// node's loop (198-245) is run by one wave, in the reference's order, and the nodes run in
+// parallel (waves stride over the outer side's nodes; grid.y = pairs).  Lanes hold the node's
+// inner features (candidate rank r = lane + 64 j, i.e. vIndicesF order); for each outer feature
+// the wave computes every unmatched candidate's distance, best = min (distance << 16 | rank) --
+// the first minimum in order -- and second = the smallest distance of the other candidates,
+// which is exactly what the sequential best/second update yields.  The rotation histogram is
+// accumulated with atomics; the pair's last workgroup then applies ComputeThreeMaxima (259-281)
+// and clears the slots of the non-top bins.
+//
+// One loop for both overloads.  kKK = false: SearchByBoW(KeyFrame*, Frame&) (159-291), the outer
+// side kf_* the keyframe, the inner side f_* the frame.  kKK = true: SearchByBoW(pKF1, pKF2)
+// (525-658), outer pKF1, inner pKF2.  The reference's differences between the two:
+//                         (KeyFrame, Frame)            (KeyFrame, KeyFrame)
+//   inner candidate       any frame feature            f_ok: a live map point (577-583)
+//   acceptance            bestDist1 <= TH_LOW (231)    bestDist1 < TH_LOW (601)
+//   result, bin           per inner feature (235)      per outer feature (605, 617)
+//   histogram bin         rot_bin's, as it comes       range-checked: ORBFE_ERR_UNSUPPORTED
+//   out_host copy         host form                    none
 constexpr int kBowSearchBlock = 256;   // 4 waves
-constexpr int kBowNodeMax = 256;  // frame features per node handled in registers (4 per lane)
+constexpr int kBowNodeMax = 256;  // inner features per node handled in registers (4 per lane)
 __device__ __forceinline__ int bow_pair_of(const int* f_node_ids, int f_nn, int id) {
     int lo = 0, hi = f_nn;  // FeatureVector::lower_bound in the frame's nodes
     while (lo < hi) {
@@ -310,8 +317,9 @@ __device__ __forceinline__ int bow_pair_of(const int* f_node_ids, int f_nn, int 
     return (lo < f_nn && f_node_ids[lo] == id) ? lo : -1;
 }
 
-__global__ __launch_bounds__(kBowSearchBlock) void bow_search_kernel(BowMatchArgs a, float nnratio,
-                                                                     int check_ori) {
+template <bool kKK>
+__device__ __forceinline__ void bow_pair_search(const BowMatchArgs& a, const uint8_t* f_ok,
+                                                float nnratio, int check_ori) {
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.y;
     const int ks = a.pair_kf ? a.pair_kf[p] : 0, fs = a.pair_f ? a.pair_f[p] : 0;
@@ -326,10 +334,12 @@ __global__ __launch_bounds__(kBowSearchBlock) void bow_search_kernel(BowMatchArg
     const int* f_node_ids = a.f_node_ids + fbase;
     const int* f_node_off = a.f_node_off + (size_t)fs * (a.f_cap + 1);
     const int* f_feat = a.f_feat + fbase;
+    if (kKK) f_ok += fbase;
     const uint4* f_desc = a.f_desc + 2 * fbase;
     const float* f_angle = a.f_angle + fbase;
-    int* matches = a.matches + (size_t)p * a.f_cap;
-    int* bins = a.bins + (size_t)p * a.f_cap;
+    const int res_cap = kKK ? a.kf_cap : a.f_cap;  // match slots of a pair
+    int* matches = a.matches + (size_t)p * res_cap;
+    int* bins = a.bins + (size_t)p * res_cap;
     int* hist = a.hist + p * 32;
     const bool bad = kf_nn < 0 || kf_nn > a.kf_cap || f_nn < 0 || f_nn > a.f_cap;
     if (bad && threadIdx.x == 0) atomicExch(a.status, ORBFE_ERR_ARG);
@@ -355,11 +365,13 @@ __global__ __launch_bounds__(kBowSearchBlock) void bow_search_kernel(BowMatchArg
         for (int j = 0; j < 4; ++j) {
             const int r = lane + 64 * j;
             jf[j] = r < ny ? f_feat[y0 + r] : -1;
-            free_[j] = jf[j] >= 0 && jf[j] < a.f_cap;
+            const bool in = jf[j] >= 0 && jf[j] < a.f_cap;
+            if (kKK) free_[j] = in && f_ok[in ? jf[j] : 0] != 0;
+            else free_[j] = in;
             d0[j] = free_[j] ? f_desc[2 * jf[j]] : make_uint4(0, 0, 0, 0);
             d1[j] = free_[j] ? f_desc[2 * jf[j] + 1] : make_uint4(0, 0, 0, 0);
         }
-        // the node's keyframe features are fetched by the lanes in parallel (64 at a time) and
+        // the node's outer features are fetched by the lanes in parallel (64 at a time) and
         // broadcast in order, so the sequential loop carries no memory latency
         for (int xb = 0; xb < nx; xb += 64) {
             const int xl = xb + lane;
@@ -377,17 +389,10 @@ __global__ __launch_bounds__(kBowSearchBlock) void bow_search_kernel(BowMatchArg
             const int cnt = min(64, nx - xb);
             const int nj = (ny + 63) >> 6;  // candidate registers in use (wave-uniform)
             for (int t = 0; t < cnt; ++t) {
-                // t is wave-uniform: v_readlane into scalar registers, no LDS round trip
                 const int ikf = __builtin_amdgcn_readlane(my_ikf, t);
                 if (ikf < 0) continue;
-                const uint4 q0 = make_uint4(__builtin_amdgcn_readlane(my0.x, t),
-                                            __builtin_amdgcn_readlane(my0.y, t),
-                                            __builtin_amdgcn_readlane(my0.z, t),
-                                            __builtin_amdgcn_readlane(my0.w, t));
-                const uint4 q1 = make_uint4(__builtin_amdgcn_readlane(my1.x, t),
-                                            __builtin_amdgcn_readlane(my1.y, t),
-                                            __builtin_amdgcn_readlane(my1.z, t),
-                                            __builtin_amdgcn_readlane(my1.w, t));
+                uint4 q0, q1;
+                readlane_desc(my0, my1, t, q0, q1);
                 uint32_t key = 0xffffffffu;
                 int dist[4];
 #pragma unroll
@@ -406,16 +411,19 @@ __global__ __launch_bounds__(kBowSearchBlock) void bow_search_kernel(BowMatchArg
                 for (int j = 0; j < 4; ++j)
                     if (j < nj && free_[j] && lane + 64 * j != brank) sec = min(sec, dist[j]);
                 sec = __ockl_wfred_min_i32(sec);
-                if (b1 <= kThLow && (float)b1 < nnratio * (float)sec) {  // TH_LOW, ratio (233-237)
+                const bool low = kKK ? b1 < kThLow : b1 <= kThLow;  // 601 / 231
+                if (low && (float)b1 < nnratio * (float)sec) {      // the ratio test (603 / 233)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         if (lane + 64 * j == brank) {
-                            free_[j] = false;
-                            matches[jf[j]] = ikf;
-                            if (check_ori) {
+                            free_[j] = false;  // vbMatched2[bestIdx2] (606) / the slot below
+                            const int slot = kKK ? ikf : jf[j];
+                            matches[slot] = kKK ? jf[j] : ikf;  // 605 / 235
+                            if (check_ori) {                    // 608-618 / 238-248
                                 const int bin = rot_bin(kf_angle[ikf], f_angle[jf[j]]);
-                                bins[jf[j]] = bin;
-                                atomicAdd(&hist[bin], 1);
+                                bins[slot] = bin;
+                                if (!kKK || (bin >= 0 && bin < kHistLen)) atomicAdd(&hist[bin], 1);
+                                else atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);
                             }
                             atomicAdd(&a.nm[p], 1);
                         }
@@ -424,9 +432,11 @@ __global__ __launch_bounds__(kBowSearchBlock) void bow_search_kernel(BowMatchArg
             }
         }
     }
-    if (!check_ori && !a.out_host) return;
-    // the pair's last workgroup to finish runs the orientation filter: release this
-    // workgroup's matches / bins, count it, and the last one acquires everyone's
+    if (!check_ori && (kKK || !a.out_host)) return;
+    // the pair's last workgroup to finish runs the orientation filter (259-281 / 637-655).  Not
+    // last_workgroup() (orbfe_grid.hip): a fence in every wave ahead of the barrier made the
+    // 64-pair batches 1.6 times slower (profiles/kernelshell/), so this kernel keeps the form it
+    // was measured with -- barrier, then thread 0 fences and counts the workgroup
     __shared__ int last;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -436,8 +446,8 @@ __global__ __launch_bounds__(kBowSearchBlock) void bow_search_kernel(BowMatchArg
     __syncthreads();
     if (!last) return;
     __threadfence();
-    if (check_ori) bow_ori_filter(a, p);
-    if (a.out_host) {  // host form: results straight into the pinned staging buffer
+    if (check_ori) ori_filter(matches, bins, hist, &a.nm[p], res_cap);
+    if (!kKK && a.out_host) {  // host form: results straight into the pinned staging buffer
         __syncthreads();
         for (int j = threadIdx.x; j < a.out_n; j += blockDim.x) a.out_host[2 + j] = matches[j];
         if (threadIdx.x == 0) {
@@ -445,6 +455,11 @@ __global__ __launch_bounds__(kBowSearchBlock) void bow_search_kernel(BowMatchArg
             a.out_host[1] = atomicAdd(a.status, 0);
         }
     }
+}
+
+__global__ __launch_bounds__(kBowSearchBlock) void bow_search_kernel(BowMatchArgs a, float nnratio,
+                                                                     int check_ori) {
+    bow_pair_search<false>(a, nullptr, nnratio, check_ori);
 }
 
 // Host form, one (keyframe, frame) pair with at most kBow1Nodes common nodes: the host walks the
@@ -931,7 +946,9 @@ static int bow_launch(orbfe_vocabulary* v, int nframes, int cap, const uint8_t* 
 
 static int bow_search_launch(orbfe_matcher* m, const BowMatchArgs& a, int n_pairs, int gx,
                              float nnratio, int check_ori, bool init = true) {
-    if (init) hipLaunchKernelGGL(bow_init_kernel, dim3(n_pairs), dim3(256), 0, m->stream, a);
+    if (init)  // vpMapPointMatches = NULL (164) per frame feature
+        hipLaunchKernelGGL(pair_init_kernel, dim3(n_pairs), dim3(256), 0, m->stream, a.matches,
+                           a.f_cap, a.hist, a.nm, a.done, a.status);
     hipLaunchKernelGGL(bow_search_kernel, dim3(gx, n_pairs), dim3(kBowSearchBlock), 0, m->stream,
                        a, nnratio, check_ori);
     ORBFE_HIP(hipGetLastError());
@@ -1127,7 +1144,7 @@ int orbfe_search_by_bow(orbfe_matcher* m, float nnratio, int check_ori, int n_kf
         if ((st = m->up(m->fb_co, f_feat, (size_t)f_tot * 4))) return st;
         if ((st = m->up(m->nq, nn, sizeof(nn)))) return st;
         if ((st = m->s1.ensure((size_t)f_cap * 4))) return st;  // bins per frame feature
-        // bow_init_kernel's work as uploads (the scatter runs anyway): every match NULL (164),
+        // pair_init_kernel's work as uploads (the scatter runs anyway): every match NULL (164),
         // an empty histogram, the finished-workgroup counter, nmatches and status 0
         const bool zc = m->stg.pin_dev != nullptr;
         if (zc) {

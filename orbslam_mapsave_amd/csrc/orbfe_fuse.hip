@@ -77,11 +77,8 @@ __global__ __launch_bounds__(256) void fuse_search_kernel(FuseArgs a) {
     const float P[3] = {a.xyz[3 * i], a.xyz[3 * i + 1], a.xyz[3 * i + 2]};
     const float nv[3] = {a.normal[3 * i], a.normal[3 * i + 1], a.normal[3 * i + 2]};
     const float maxd = a.maxd[i], mind = a.mind[i];
-    const float* T = a.T[kl];
     float pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-        pc[r] = ((T[4 * r] * P[0] + T[4 * r + 1] * P[1]) + T[4 * r + 2] * P[2]) + T[4 * r + 3];
+    pose_apply(a.T[kl], P, pc);
     const float invz = 1.0f / pc[2];
     const float x = pc[0] * invz, y = pc[1] * invz;
     const float u = a.fx * x + a.cx, v = a.fy * y + a.cy;
@@ -89,18 +86,15 @@ __global__ __launch_bounds__(256) void fuse_search_kernel(FuseArgs a) {
     const float po0 = P[0] - a.ow[kl][0], po1 = P[1] - a.ow[kl][1], po2 = P[2] - a.ow[kl][2];
     const float dist = (float)sqrt((double)po0 * po0 + (double)po1 * po1 + (double)po2 * po2);
     const double dot = (double)po0 * nv[0] + (double)po1 * nv[1] + (double)po2 * nv[2];
-    // GetMin/MaxDistanceInvariance (MapPoint.cc:621-631); KeyFrame::IsInImage (KeyFrame.cc:1352)
-    const float dmax = 1.2f * maxd, dmin = 0.8f * mind;
+    const float dmax = kMaxDistInvariance * maxd, dmin = kMinDistInvariance * mind;
+    // KeyFrame::IsInImage (KeyFrame.cc:1352): strict upper bounds
     const bool ok = !sk && !(pc[2] < 0.0f) && u >= a.minx && u < a.maxx && v >= a.miny &&
                     v < a.maxy && !(dist < dmin || dist > dmax) && !(dot < 0.5 * (double)dist);
     unsigned long long key = 256ull << 32;  // (distance, rank): strict <, bestDist starts at 256
     int kidx = -1;
     if (ok) {
-        const float ratio = maxd / dist;
-        const int lvl = (int)ceilf((float)log((double)ratio) / a.log_scale);
-        if (lvl < 0 || lvl >= a.nlevels) {
-            if ((threadIdx.x & 63) == 0) atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);  // mvScaleFactors[lvl]
-        } else {
+        const int lvl = predict_level(maxd, dist, a.log_scale);
+        if (level_in_pyramid(lvl, a.nlevels, a.status)) {
             const DevFrame F = fuse_frame(a, kf);
             const float radius = a.th * a.scale[lvl];
             const uint4 q0 = a.mdesc[2 * i], q1 = a.mdesc[2 * i + 1];
@@ -134,17 +128,7 @@ __global__ __launch_bounds__(256) void fuse_search_kernel(FuseArgs a) {
                 });
         }
     }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)key, s, 64);
-        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(key >> 32), s, 64);
-        const int oi = __shfl_xor(kidx, s, 64);
-        const unsigned long long c = ((unsigned long long)hi << 32) | lo;
-        if (c < key) {
-            key = c;
-            kidx = oi;
-        }
-    }
+    wave_first_min(key, kidx);
     if ((threadIdx.x & 63) == 0) {
         const int bd = (int)(key >> 32);
         a.best_idx[o] = bd <= kThLow ? kidx : -1;

@@ -326,15 +326,7 @@ __global__ __launch_bounds__(kGreedyBlock) void greedy_accept_kernel(GreedyArgs 
     // fused path: the last workgroup to finish writes the slots (greedy_slots_kernel's work),
     // sums the candidate kernel's per-workgroup tallies and reports convergence; it resets
     // the counter for the next call
-    __shared__ int is_last;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        is_last = atomicAdd(a.done, 1) == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!is_last) return;
-    __threadfence();
+    if (!last_workgroup(a.done)) return;
     // the slots and the tallies in batches whose loads are all issued before any is used (one
     // workgroup does this work alone: a dependent load chain per element would be serial)
     for (int s0 = 0; s0 < a.nkp; s0 += 4 * kGreedyBlock) {

@@ -11,6 +11,16 @@
 //   features_in_area(_wave)  Frame::GetFeaturesInArea (Frame.cc:445-498), a thread / a wave per
 //                         query
 //   fia_*_kernel          the same as a batch of queries (the grid's parity probe)
+//
+// and, at the end, the pieces the matcher kernels on top of it are made of, each written once:
+//
+//   CandArgs / CandSink   the candidate-list shell of every *_cand_kernel
+//   pose_apply            the 3 x 4 pose product
+//   kMin/kMaxDistInvariance / predict_level / level_in_pyramid
+//                         MapPoint's distance invariance and PredictScale
+//   wave_first_min        first-wins (distance, rank) minimum over a wave
+//   readlane_desc         a descriptor pair broadcast from one lane
+//   last_workgroup        "the last workgroup to finish runs the tail"
 #include <hip/hip_runtime.h>
 
 #include "../../include/orbfe.h"
@@ -313,6 +323,136 @@ __global__ __launch_bounds__(256) void fia_wave_kernel(FiaArgs a) {
             if (FILL) a.items[o + rank] = idx;
         });
     if (!FILL && (threadIdx.x & 63) == 0) a.cnt[q] = n;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The pieces the matcher kernels share (orbfe_match / _fuse / _bow / _loop / _triangulate /
+// _greedy.hip).  The build keeps -ffp-contract=off and every float expression below is
+// parenthesised as the reference evaluates it: a rounding detail or a bound is fixed here, once.
+// What differs between the searches by the reference's own choice -- how 1/z is formed, the
+// in-image and viewing tests, the level windows, the acceptance thresholds -- stays at the call
+// sites ("One shell for the candidate kernels").
+
+// The candidate lists a *_cand_kernel writes, filled in by the host's candidate builder
+// (orbfe_match_api.hip): CSR lists (count -> scan -> fill) or kfix fixed slots per query.
+struct CandArgs {
+    long long cand_cap;  // fill writes only lists that end within the capacity
+    int* cnt;            // per query
+    const int* off;      // queries + 1
+    int2* cand;          // (index, payload): the distance, or dist | octave << 16 (local map)
+    int kfix;            // fixed-slot form: candidate slots per query
+    int* ovf;            // fixed-slot form: queries with more candidates than kfix
+};
+
+// The shell of a candidate kernel, one wave per query q.  kMode 0: count the candidates,
+// 1: fill the CSR lists (after the scan), 2: the fixed-slot form in one pass -- the first kfix
+// candidates of query q at q * kfix, min(n, kfix) in cnt[q], and a query with more raises *ovf
+// (the host then reruns the call on the CSR path).
+template <int kMode>
+struct CandSink {
+    const CandArgs& c;
+    const int q;
+    // fill: the query's list ends within the capacity (else the host reruns with more)
+    __device__ __forceinline__ bool room() const { return kMode != 1 || c.off[q + 1] <= c.cand_cap; }
+    __device__ __forceinline__ int2* out() const {
+        return kMode == 1 ? c.cand + c.off[q] : kMode == 2 ? c.cand + (size_t)q * c.kfix : nullptr;
+    }
+    // the candidate of rank `rank` (features_in_area_wave's emit), on the lane that owns it;
+    // payload() -- the descriptor loads and the distance -- runs only for a candidate that is
+    // stored, so the count mode's walk stays free of them
+    template <class Payload>
+    __device__ __forceinline__ void put(int2* out, int rank, int idx, Payload payload) const {
+        if (kMode == 1 || (kMode == 2 && rank < c.kfix)) out[rank] = make_int2(idx, payload());
+    }
+    // the query's n candidates are through (n = 0: a query that is not searched)
+    __device__ __forceinline__ void finish(int n) const {
+        const bool lead = (threadIdx.x & 63) == 0;  // the lane that writes the query's words
+        if (kMode == 0 && lead) c.cnt[q] = n;
+        if (kMode == 2 && lead) {
+            c.cnt[q] = min(n, c.kfix);
+            if (n > c.kfix) atomicAdd(c.ovf, 1);
+        }
+    }
+};
+
+// pc = [R|t] P for a row-major 3 x 4 pose T, each row summed left to right as cv::Mat's float
+// product followed by + t does.
+__device__ __forceinline__ void pose_apply(const float* T, const float* P, float* pc) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        pc[r] = ((T[4 * r] * P[0] + T[4 * r + 1] * P[1]) + T[4 * r + 2] * P[2]) + T[4 * r + 3];
+}
+
+// MapPoint::GetMinDistanceInvariance / GetMaxDistanceInvariance (MapPoint.cc:621-631): the
+// factors on mfMinDistance / mfMaxDistance.  The bounds and the test on them,
+// !(dist < dmin || dist > dmax), are written out in each search's chain of tests: as constants
+// they leave every kernel's code as it was (a helper returning the bool made frustum_kernel
+// branch, and even one returning a bound moved its registers).
+constexpr float kMinDistInvariance = 0.8f, kMaxDistInvariance = 1.2f;
+
+// MapPoint::PredictScale (MapPoint.cc:633-642) before its clamp, which none of the callers has:
+// the log in double, the quotient in float.
+__device__ __forceinline__ int predict_level(float maxd, float dist, float log_scale) {
+    const float ratio = maxd / dist;
+    return (int)ceilf((float)log((double)ratio) / log_scale);
+}
+
+// mvScaleFactors[lvl] is in range; otherwise the reference reads past the vector and the wave
+// raises ORBFE_ERR_UNSUPPORTED in *status.
+__device__ __forceinline__ bool level_in_pyramid(int lvl, int nlevels, int* status) {
+    if (lvl < 0 || lvl >= nlevels) {
+        if ((threadIdx.x & 63) == 0) atomicExch(status, ORBFE_ERR_UNSUPPORTED);
+        return false;
+    }
+    return true;
+}
+
+// The wave's smallest key = distance << 32 | rank and the idx that came with it, into every
+// lane: the first candidate in rank order among equal distances, as a strict-< loop picks.
+// (The reduction runs on copies: on the references themselves fuse_search_kernel grew by 23
+// instructions and its batch row by 0.8 %.)
+__device__ __forceinline__ void wave_first_min(unsigned long long& key_io, int& idx_io) {
+    unsigned long long key = key_io;
+    int idx = idx_io;
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)key, s, 64);
+        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(key >> 32), s, 64);
+        const int oi = __shfl_xor(idx, s, 64);
+        const unsigned long long c = ((unsigned long long)hi << 32) | lo;
+        if (c < key) {
+            key = c;
+            idx = oi;
+        }
+    }
+    key_io = key;
+    idx_io = idx;
+}
+
+// The descriptor (my0, my1) of lane t into scalar registers (t is wave-uniform: v_readlane, no
+// LDS round trip).
+__device__ __forceinline__ void readlane_desc(const uint4& my0, const uint4& my1, int t, uint4& q0,
+                                              uint4& q1) {
+    q0 = make_uint4(__builtin_amdgcn_readlane(my0.x, t), __builtin_amdgcn_readlane(my0.y, t),
+                    __builtin_amdgcn_readlane(my0.z, t), __builtin_amdgcn_readlane(my0.w, t));
+    q1 = make_uint4(__builtin_amdgcn_readlane(my1.x, t), __builtin_amdgcn_readlane(my1.y, t),
+                    __builtin_amdgcn_readlane(my1.z, t), __builtin_amdgcn_readlane(my1.w, t));
+}
+
+// True in every thread of the last of the grid's gridDim.x workgroups (of one blockIdx.y) to get
+// here; *counter is 0 before the launch and counts them.  Every thread releases its own stores,
+// the workgroup is counted behind a barrier, and the last one acquires everyone's: what the
+// others wrote before their call is visible after it.  Every thread of the workgroup calls it,
+// once per kernel.
+__device__ __forceinline__ bool last_workgroup(int* counter) {
+    __shared__ int last;
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) last = atomicAdd(counter, 1) == (int)gridDim.x - 1;
+    __syncthreads();
+    if (!last) return false;
+    __threadfence();
+    return true;
 }
 
 }  // namespace orbfe

@@ -1,9 +1,11 @@
 // orbfe_loop.hip — the matchers LoopClosing::ComputeSim3 calls on a loop candidate:
 //
 //   SearchByProjection(KeyFrame* pKF, cv::Mat Scw, vpPoints, vpMatched, int th)
-//       (ORBmatcher.cc:293-406, LoopClosing.cc:376): the projection block of Fuse's Sim3
-//       overload per point, then a greedy tail — a keypoint that held a point before the call, or
-//       that an earlier point of the list took (378, 399), is blocked.  sbp_loop_cand_kernel
+//       (ORBmatcher.cc:293-406, LoopClosing.cc:376): projection, in-image, distance and viewing
+//       tests and the predicted level per point (this overload's own forms of them around the
+//       shared pieces of orbfe_grid.hip), then a greedy tail — a keypoint that held a point
+//       before the call, or that an earlier point of the list took (378, 399), is blocked.
+//       sbp_loop_cand_kernel
 //       builds every point's candidates in parallel; orbfe_greedy.hip resolves the order
 //       dependence (kGreedyMaxD, max_dist = TH_LOW, every acceptance blocks), driven by
 //       sbp_search (orbfe_match_api.hip) like the other host forms.
@@ -44,18 +46,18 @@ struct SbpLoopArgs {
     CandArgs c;               // kMode 2 uses kfix / ovf
 };
 
-// kMode as sbp_kf_cand_kernel's: 0 count, 1 fill the CSR lists, 2 fixed slots in one pass.  The
-// arithmetic is fuse_search_kernel<true>'s (x = X * invz before fx * x + cx, invz a float divide,
-// KeyFrame::IsInImage's strict upper bounds, dot < 0.5 * dist in double); the [lvl - 1, lvl]
-// window sits in the keep filter, so the survivors of KeyFrame::GetFeaturesInArea(u, v, radius)
-// (no level filter, KeyFrame.cc:1311) keep the reference's order.
+// kMode: CandSink's (orbfe_grid.hip).  This overload's own choices (334-362): invz a float
+// divide, x = X * invz before fx * x + cx, KeyFrame::IsInImage's strict upper bounds, dot <
+// 0.5 * dist in double; the [lvl - 1, lvl] window sits in the keep filter, so the survivors of
+// KeyFrame::GetFeaturesInArea(u, v, radius) (no level filter, KeyFrame.cc:1311) keep the
+// reference's order.
 template <int kMode>
 __global__ __launch_bounds__(256) void sbp_loop_cand_kernel(SbpLoopArgs a) {
-    constexpr bool FILL = kMode == 1;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per point of the list
     if (i >= a.n) return;
+    const CandSink<kMode> sink{a.c, i};
     // every per-point input is read up front and feeds the unconditional arithmetic below
-    const bool room = !FILL || a.c.off[i + 1] <= a.c.cand_cap;
+    const bool room = sink.room();
     const bool sk = a.skip && a.skip[i];
     const float P[3] = {a.xyz[3 * i], a.xyz[3 * i + 1], a.xyz[3 * i + 2]};
     const float nv[3] = {a.normal[3 * i], a.normal[3 * i + 1], a.normal[3 * i + 2]};
@@ -64,27 +66,22 @@ __global__ __launch_bounds__(256) void sbp_loop_cand_kernel(SbpLoopArgs a) {
     int n = 0;
     {
         float pc[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            pc[r] = ((a.T[4 * r] * P[0] + a.T[4 * r + 1] * P[1]) + a.T[4 * r + 2] * P[2]) + a.T[4 * r + 3];
+        pose_apply(a.T, P, pc);
         const float invz = 1.0f / pc[2];  // 1/p3Dc.at<float>(2): a float divide (334)
         const float x = pc[0] * invz, y = pc[1] * invz;
         const float u = a.fx * x + a.cx, v = a.fy * y + a.cy;
         const float po0 = P[0] - a.ow[0], po1 = P[1] - a.ow[1], po2 = P[2] - a.ow[2];
         const float dist = (float)sqrt((double)po0 * po0 + (double)po1 * po1 + (double)po2 * po2);
         const double dot = (double)po0 * nv[0] + (double)po1 * nv[1] + (double)po2 * nv[2];
-        const float dmax = 1.2f * maxd, dmin = 0.8f * mind;  // MapPoint.cc:621-631
+        const float dmax = kMaxDistInvariance * maxd, dmin = kMinDistInvariance * mind;
         const bool ok = !sk && !(pc[2] < 0.0f) && u >= a.minx && u < a.maxx && v >= a.miny &&
                         v < a.maxy && !(dist < dmin || dist > dmax) && !(dot < 0.5 * (double)dist);
         if (ok) {
-            const float ratio = maxd / dist;
-            const int lvl = (int)ceilf((float)log((double)ratio) / a.log_scale);
-            if (lvl < 0 || lvl >= a.nlevels) {
-                if ((threadIdx.x & 63) == 0) atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);  // mvScaleFactors[lvl]
-            } else {
+            const int lvl = predict_level(maxd, dist, a.log_scale);
+            if (level_in_pyramid(lvl, a.nlevels, a.status)) {
                 const float radius = a.th * a.scale[lvl];
                 const uint4 q0 = a.desc[2 * i], q1 = a.desc[2 * i + 1];
-                int2* out = FILL ? a.c.cand + a.c.off[i] : kMode == 2 ? a.c.cand + (size_t)i * a.c.kfix : nullptr;
+                int2* out = sink.out();
                 n = features_in_area_wave(
                     a.kf, u, v, radius, -1, -1,
                     [&](int i2) {  // 381-384
@@ -92,19 +89,15 @@ __global__ __launch_bounds__(256) void sbp_loop_cand_kernel(SbpLoopArgs a) {
                         return !(o < lvl - 1 || o > lvl);
                     },
                     [&](int i2, int rank) {
-                        if (FILL || (kMode == 2 && rank < a.c.kfix)) {
+                        sink.put(out, rank, i2, [&] {
                             const uint4* d = a.kf.desc + 2 * i2;
-                            out[rank] = make_int2(i2, hamming256(q0, q1, d[0], d[1]));
-                        }
+                            return hamming256(q0, q1, d[0], d[1]);
+                        });
                     });
             }
         }
     }
-    if (kMode == 0 && (threadIdx.x & 63) == 0) a.c.cnt[i] = n;
-    if (kMode == 2 && (threadIdx.x & 63) == 0) {
-        a.c.cnt[i] = min(n, a.c.kfix);
-        if (n > a.c.kfix) atomicAdd(a.c.ovf, 1);
-    }
+    sink.finish(n);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -142,18 +135,14 @@ __global__ __launch_bounds__(256) void sim3_search_kernel(Sim3Args a) {
     const float P[3] = {s.xyz[3 * i], s.xyz[3 * i + 1], s.xyz[3 * i + 2]};
     const float maxd = s.maxd[i], mind = s.mind[i];
     float p1[3], p2[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-        p1[r] = ((s.Tsw[4 * r] * P[0] + s.Tsw[4 * r + 1] * P[1]) + s.Tsw[4 * r + 2] * P[2]) + s.Tsw[4 * r + 3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-        p2[r] = ((s.S[4 * r] * p1[0] + s.S[4 * r + 1] * p1[1]) + s.S[4 * r + 2] * p1[2]) + s.S[4 * r + 3];
+    pose_apply(s.Tsw, P, p1);  // world -> source camera (1162)
+    pose_apply(s.S, p1, p2);   // -> target camera (1163)
     const float invz = (float)(1.0 / (double)p2[2]);  // 1.0/p3Dc2.at<float>(2): double divide (1169)
     const float x = p2[0] * invz, y = p2[1] * invz;
     const float u = a.fx * x + a.cx, v = a.fy * y + a.cy;
     // cv::norm of the camera-frame vector, accumulated in double (1182)
     const float dist = (float)sqrt((double)p2[0] * p2[0] + (double)p2[1] * p2[1] + (double)p2[2] * p2[2]);
-    const float dmax = 1.2f * maxd, dmin = 0.8f * mind;  // MapPoint.cc:621-631
+    const float dmax = kMaxDistInvariance * maxd, dmin = kMinDistInvariance * mind;
     const DevFrame& F = s.tgt;
     const bool ok = live && !(p2[2] < 0.0f) && u >= F.minx && u < F.maxx && v >= F.miny &&
                     v < F.maxy && !(dist < dmin || dist > dmax);
@@ -161,11 +150,8 @@ __global__ __launch_bounds__(256) void sim3_search_kernel(Sim3Args a) {
     unsigned long long key = 257ull << 32;
     int kidx = -1;
     if (ok) {
-        const float ratio = maxd / dist;
-        const int lvl = (int)ceilf((float)log((double)ratio) / s.log_scale);
-        if (lvl < 0 || lvl >= s.nlevels) {
-            if ((threadIdx.x & 63) == 0) atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);  // mvScaleFactors[lvl]
-        } else {
+        const int lvl = predict_level(maxd, dist, s.log_scale);
+        if (level_in_pyramid(lvl, s.nlevels, a.status)) {
             const float radius = a.th * s.scale[lvl];
             const uint4 q0 = s.desc[2 * i], q1 = s.desc[2 * i + 1];
             features_in_area_wave(
@@ -185,17 +171,7 @@ __global__ __launch_bounds__(256) void sim3_search_kernel(Sim3Args a) {
                 });
         }
     }
-#pragma unroll
-    for (int sh = 32; sh > 0; sh >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)key, sh, 64);
-        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(key >> 32), sh, 64);
-        const int oi = __shfl_xor(kidx, sh, 64);
-        const unsigned long long c = ((unsigned long long)hi << 32) | lo;
-        if (c < key) {
-            key = c;
-            kidx = oi;
-        }
-    }
+    wave_first_min(key, kidx);
     if ((threadIdx.x & 63) == 0) s.vn[i] = (int)(key >> 32) <= kThHigh ? kidx : -1;  // 1224
 }
 
@@ -227,151 +203,11 @@ struct BowKkArgs {
     const uint8_t* f_ok;   // pKF2's features: map point present and not bad
 };
 
-// One workgroup per pair: vpMatches12 = NULL (537), empty histogram, nmatches = 0, the pair's
-// finished-workgroup counter; workgroup 0 clears the status.
-__global__ __launch_bounds__(256) void bow_kk_init_kernel(BowKkArgs k) {
-    const BowMatchArgs& a = k.b;
-    const int p = blockIdx.x;
-    int* mt = a.matches + (size_t)p * a.kf_cap;
-    for (int j = threadIdx.x; j < a.kf_cap; j += 256) mt[j] = -1;
-    if (threadIdx.x < 32) a.hist[p * 32 + threadIdx.x] = 0;
-    if (threadIdx.x == 0) {
-        a.nm[p] = 0;
-        a.done[p] = 0;
-        if (p == 0) *a.status = 0;
-    }
-}
-
+// pKF1 is the outer loop and owns the result, so the search is bow_pair_search<true>
+// (orbfe_bow.hip), which holds those differences as compile-time branches.
 __global__ __launch_bounds__(kBowSearchBlock) void bow_search_kk_kernel(BowKkArgs k, float nnratio,
                                                                         int check_ori) {
-    const BowMatchArgs& a = k.b;
-    const int lane = threadIdx.x & 63;
-    const int p = blockIdx.y;
-    const int ks = a.pair_kf ? a.pair_kf[p] : 0, fs = a.pair_f ? a.pair_f[p] : 0;
-    const int kf_nn = a.kf_nn[ks], f_nn = a.f_nn[fs];
-    const size_t kb = (size_t)ks * a.kf_cap, fbase = (size_t)fs * a.f_cap;
-    const int* kf_node_ids = a.kf_node_ids + kb;
-    const int* kf_node_off = a.kf_node_off + (size_t)ks * (a.kf_cap + 1);
-    const int* kf_feat = a.kf_feat + kb;
-    const uint8_t* kf_ok = a.kf_ok + kb;
-    const uint4* kf_desc = a.kf_desc + 2 * kb;
-    const float* kf_angle = a.kf_angle + kb;
-    const int* f_node_ids = a.f_node_ids + fbase;
-    const int* f_node_off = a.f_node_off + (size_t)fs * (a.f_cap + 1);
-    const int* f_feat = a.f_feat + fbase;
-    const uint8_t* f_ok = k.f_ok + fbase;
-    const uint4* f_desc = a.f_desc + 2 * fbase;
-    const float* f_angle = a.f_angle + fbase;
-    int* matches = a.matches + (size_t)p * a.kf_cap;
-    int* bins = a.bins + (size_t)p * a.kf_cap;
-    int* hist = a.hist + p * 32;
-    const bool bad = kf_nn < 0 || kf_nn > a.kf_cap || f_nn < 0 || f_nn > a.f_cap;
-    if (bad && threadIdx.x == 0) atomicExch(a.status, ORBFE_ERR_ARG);
-    const int nwaves = gridDim.x * (kBowSearchBlock / 64);
-    const int n_nodes = bad ? 0 : kf_nn;
-    for (int na = blockIdx.x * (kBowSearchBlock / 64) + (threadIdx.x >> 6); na < n_nodes; na += nwaves) {
-        const int fb = bow_pair_of(f_node_ids, f_nn, kf_node_ids[na]);
-        if (fb < 0) continue;
-        const int y0 = f_node_off[fb], ny = f_node_off[fb + 1] - y0;
-        const int x0 = kf_node_off[na], nx = kf_node_off[na + 1] - x0;
-        if (y0 < 0 || ny < 0 || y0 + ny > a.f_cap || x0 < 0 || nx < 0 || x0 + nx > a.kf_cap) {
-            if (lane == 0) atomicExch(a.status, ORBFE_ERR_ARG);
-            continue;
-        }
-        if (ny > kBowNodeMax) {
-            if (lane == 0) atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);
-            continue;
-        }
-        // lanes hold the node's KF2 features (rank r = lane + 64 j, f2it->second order); one
-        // without a live map point is never a candidate (579-583)
-        int jf[4];
-        uint4 d0[4], d1[4];
-        bool free_[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int r = lane + 64 * j;
-            jf[j] = r < ny ? f_feat[y0 + r] : -1;
-            const bool in = jf[j] >= 0 && jf[j] < a.f_cap;
-            free_[j] = in && f_ok[in ? jf[j] : 0] != 0;
-            d0[j] = free_[j] ? f_desc[2 * jf[j]] : make_uint4(0, 0, 0, 0);
-            d1[j] = free_[j] ? f_desc[2 * jf[j] + 1] : make_uint4(0, 0, 0, 0);
-        }
-        for (int xb = 0; xb < nx; xb += 64) {
-            const int xl = xb + lane;
-            int my_ikf = -1;
-            uint4 my0 = make_uint4(0, 0, 0, 0), my1 = my0;
-            if (xl < nx) {
-                my_ikf = kf_feat[x0 + xl];
-                if (my_ikf < 0 || my_ikf >= a.kf_cap || !kf_ok[my_ikf]) {
-                    my_ikf = -1;
-                } else {
-                    my0 = kf_desc[2 * my_ikf];
-                    my1 = kf_desc[2 * my_ikf + 1];
-                }
-            }
-            const int cnt = min(64, nx - xb);
-            const int nj = (ny + 63) >> 6;  // candidate registers in use (wave-uniform)
-            for (int t = 0; t < cnt; ++t) {
-                const int ikf = __builtin_amdgcn_readlane(my_ikf, t);
-                if (ikf < 0) continue;
-                const uint4 q0 = make_uint4(__builtin_amdgcn_readlane(my0.x, t),
-                                            __builtin_amdgcn_readlane(my0.y, t),
-                                            __builtin_amdgcn_readlane(my0.z, t),
-                                            __builtin_amdgcn_readlane(my0.w, t));
-                const uint4 q1 = make_uint4(__builtin_amdgcn_readlane(my1.x, t),
-                                            __builtin_amdgcn_readlane(my1.y, t),
-                                            __builtin_amdgcn_readlane(my1.z, t),
-                                            __builtin_amdgcn_readlane(my1.w, t));
-                uint32_t key = 0xffffffffu;
-                int dist[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    dist[j] = 256;
-                    if (j < nj && free_[j]) {
-                        dist[j] = hamming256(q0, q1, d0[j], d1[j]);
-                        key = min(key, ((uint32_t)dist[j] << 16) | (uint32_t)(lane + 64 * j));
-                    }
-                }
-                key = __ockl_wfred_min_u32(key);
-                const int b1 = key == 0xffffffffu ? 256 : (int)(key >> 16);
-                const int brank = (int)(key & 0xffff);
-                int sec = 256;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (j < nj && free_[j] && lane + 64 * j != brank) sec = min(sec, dist[j]);
-                sec = __ockl_wfred_min_i32(sec);
-                if (b1 < kThLow && (float)b1 < nnratio * (float)sec) {  // strict TH_LOW (601-603)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (lane + 64 * j == brank) {
-                            free_[j] = false;      // vbMatched2[bestIdx2] (606)
-                            matches[ikf] = jf[j];  // 605
-                            if (check_ori) {       // 608-618 (H15)
-                                const int bin = rot_bin(kf_angle[ikf], f_angle[jf[j]]);
-                                bins[ikf] = bin;
-                                if (bin >= 0 && bin < kHistLen) atomicAdd(&hist[bin], 1);
-                                else atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);
-                            }
-                            atomicAdd(&a.nm[p], 1);
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (!check_ori) return;
-    // the pair's last workgroup to finish runs the orientation filter (637-655), as
-    // bow_search_kernel does
-    __shared__ int last;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        last = atomicAdd(&a.done[p], 1) == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    ori_filter(matches, bins, hist, &a.nm[p], a.kf_cap);
+    bow_pair_search<true>(k.b, k.f_ok, nnratio, check_ori);
 }
 
 }  // namespace orbfe
@@ -381,7 +217,9 @@ using namespace orbfe;
 namespace {
 int bow_kk_launch(orbfe_matcher* m, const BowKkArgs& k, int n_pairs, int gx, float nnratio,
                   int check_ori) {
-    hipLaunchKernelGGL(bow_kk_init_kernel, dim3(n_pairs), dim3(256), 0, m->stream, k);
+    // vpMatches12 = NULL (537) per KF1 feature
+    hipLaunchKernelGGL(pair_init_kernel, dim3(n_pairs), dim3(256), 0, m->stream, k.b.matches,
+                       k.b.kf_cap, k.b.hist, k.b.nm, k.b.done, k.b.status);
     hipLaunchKernelGGL(bow_search_kk_kernel, dim3(gx, n_pairs), dim3(kBowSearchBlock), 0,
                        m->stream, k, nnratio, check_ori);
     ORBFE_HIP(hipGetLastError());

@@ -5,7 +5,8 @@
 //   bf_match_kernel      brute-force best/second (config 3) on the i8 matrix cores: Hamming
 //                        as popc(r) - 2 r.q + popc(q), references streamed through LDS
 //   *_cand_kernel        GetFeaturesInArea (features_in_area_wave) + distances for every query
-//                        in parallel (counts, scan, fill)
+//                        in parallel (counts, scan, fill, or fixed slots): each kernel is its own
+//                        projection and tests inside the one shell, CandSink (orbfe_grid.hip)
 //   sfi_round_kernel     SearchForInitialization's sequential greedy-with-steals semantics (H7)
 //                        as Jacobi rounds to the unique fixed point of the in-order loop (a
 //                        wave per query, lanes over candidates); sfi_final_kernel applies the
@@ -539,17 +540,6 @@ using BfKernel = void (*)(const uint8_t*, long long, const int*, int, const uint
 
 // ---------------------------------------------------------------------------------------------
 // SearchForInitialization (ORBmatcher.cc:408-523)
-// The candidate lists a *_cand_kernel writes, filled in by the host's candidate builder
-// (orbfe_match_api.hip): CSR lists (count -> scan -> fill) or kfix fixed slots per query.
-struct CandArgs {
-    long long cand_cap;  // fill writes only lists that end within the capacity
-    int* cnt;            // per query
-    const int* off;      // queries + 1
-    int2* cand;          // (index, dist [| octave << 16])
-    int kfix;            // fixed-slot form: candidate slots per query
-    int* ovf;            // fixed-slot form: queries with more candidates than kfix
-};
-
 struct SfiArgs {
     DevFrame f1, f2;
     const float* prev;  // 2 per F1 keypoint
@@ -557,29 +547,28 @@ struct SfiArgs {
     CandArgs c;         // one list per F1 keypoint of (i2, dist)
 };
 
-template <bool FILL>
+// kMode 0: count, 1: fill the CSR lists (CandSink, orbfe_grid.hip; no fixed-slot form here)
+template <int kMode>
 __global__ __launch_bounds__(256) void sfi_cand_kernel(SfiArgs a) {
     const int i1 = blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per F1 keypoint
     if (i1 >= a.f1.n) return;
-    if (FILL && a.c.off[i1 + 1] > a.c.cand_cap) return;
+    const CandSink<kMode> sink{a.c, i1};
+    if (!sink.room()) return;
     const orbfe_keypoint k1 = a.f1.k[i1];
-    if (k1.octave > 0) {
-        if (!FILL && (threadIdx.x & 63) == 0) a.c.cnt[i1] = 0;
-        return;
-    }
+    if (k1.octave > 0) return sink.finish(0);
     const uint4* d1 = a.f1.desc + 2 * i1;
     const uint4 q0 = d1[0], q1 = d1[1];
-    int2* out = FILL ? a.c.cand + a.c.off[i1] : nullptr;
+    int2* out = sink.out();
     const int n = features_in_area_wave(
         a.f2, a.prev[2 * i1], a.prev[2 * i1 + 1], a.window, k1.octave, k1.octave,
         [](int) { return true; },
         [&](int i2, int rank) {
-            if (FILL) {
+            sink.put(out, rank, i2, [&] {
                 const uint4* d2 = a.f2.desc + 2 * i2;
-                out[rank] = make_int2(i2, hamming256(q0, q1, d2[0], d2[1]));
-            }
+                return hamming256(q0, q1, d2[0], d2[1]);
+            });
         });
-    if (!FILL && (threadIdx.x & 63) == 0) a.c.cnt[i1] = n;
+    sink.finish(n);
 }
 
 __device__ __forceinline__ int rot_bin(float a1, float a2) {  // ORBmatcher.cc:478-483
@@ -788,51 +777,40 @@ struct SbpLocalArgs {
     CandArgs c;          // (idx, dist | octave << 16); kMode 2 uses kfix / ovf
 };
 
-// kMode 0: count, 1: fill the CSR lists, 2: fixed slots in one pass (the first kfix candidates at
-// i * kfix, min(n, kfix) in cnt[i]; a point with more raises *ovf).  One wave per map point
-// (features_in_area_wave): one thread per point (features_in_area, round 5) left a 2,000-point
-// map 8 workgroups walking their windows serially (0.17 ms of kernel; the host call 0.252 ->
-// 0.097 ms) and was slower at 50,000 points too (the host call 0.41 -> 0.32 ms).
+// kMode: CandSink's (orbfe_grid.hip).  One wave per map point (features_in_area_wave): one
+// thread per point (features_in_area, round 5) left a 2,000-point map 8 workgroups walking
+// their windows serially (0.17 ms of kernel; the host call 0.252 -> 0.097 ms) and was slower at
+// 50,000 points too (the host call 0.41 -> 0.32 ms).
 template <int kMode>
 __global__ __launch_bounds__(256) void sbp_local_cand_kernel(SbpLocalArgs a) {
-    constexpr bool FILL = kMode == 1;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= a.mp.m) return;
-    const bool lead = (threadIdx.x & 63) == 0;  // the lane that writes the point's words
-    if (!a.mp.in_view[i] || a.mp.bad[i]) {
-        if (!FILL && lead) a.c.cnt[i] = 0;
-        return;
-    }
+    const CandSink<kMode> sink{a.c, i};
+    if (!a.mp.in_view[i] || a.mp.bad[i]) return sink.finish(0);
     const int pl = a.mp.lvl[i];
     if (pl < 0 || pl >= a.nlevels) {  // F.mvScaleFactors[nPredictedLevel] out of range
-        if (a.status && lead) atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);
-        if (!FILL && lead) a.c.cnt[i] = 0;
-        return;
+        if (a.status && (threadIdx.x & 63) == 0) atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);
+        return sink.finish(0);
     }
     float r = a.mp.vcos[i] > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos (131-137)
     if (a.th != 1.0) r *= a.th;
     const float rs = r * a.scale[pl];
     const float pxr = a.mp.pxr[i];
-    if (FILL && a.c.off[i + 1] > a.c.cand_cap) return;
+    if (!sink.room()) return;
     const uint4 q0 = a.mp.desc[2 * i], q1 = a.mp.desc[2 * i + 1];
-    int n = 0;
-    int2* out = FILL ? a.c.cand + a.c.off[i] : kMode == 2 ? a.c.cand + (size_t)i * a.c.kfix : nullptr;
-    n = features_in_area_wave(
+    int2* out = sink.out();
+    const int n = features_in_area_wave(
         a.f, a.mp.px[i], a.mp.py[i], rs, pl - 1, pl,
         [&](int idx) {  // stereo consistency (91-96)
             return !(a.f.ur && a.f.ur[idx] > 0 && fabsf(pxr - a.f.ur[idx]) > r * a.scale[pl]);
         },
-        [&](int idx, int rank) {
-            if (FILL || (kMode == 2 && rank < a.c.kfix)) {
+        [&](int idx, int rank) {  // the octave rides along for the resolver's per-level bests
+            sink.put(out, rank, idx, [&] {
                 const uint4* d = a.f.desc + 2 * idx;
-                out[rank] = make_int2(idx, hamming256(q0, q1, d[0], d[1]) | (a.f.k[idx].octave << 16));
-            }
+                return hamming256(q0, q1, d[0], d[1]) | (a.f.k[idx].octave << 16);
+            });
         });
-    if (kMode == 0 && lead) a.c.cnt[i] = n;
-    if (kMode == 2 && lead) {
-        a.c.cnt[i] = min(n, a.c.kfix);
-        if (n > a.c.kfix) atomicAdd(a.c.ovf, 1);
-    }
+    sink.finish(n);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -854,14 +832,14 @@ struct SbpLastArgs {
     CandArgs c;            // kMode 2 uses kfix / ovf
 };
 
-// kMode as sbp_kf_cand_kernel's: 0 count, 1 fill the CSR lists, 2 fixed slots in one pass
+// kMode: CandSink's (orbfe_grid.hip)
 template <int kMode>
 __global__ __launch_bounds__(256) void sbp_last_cand_kernel(SbpLastArgs a) {
-    constexpr bool FILL = kMode == 1;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per last-frame point
     if (i >= a.n_last) return;
+    const CandSink<kMode> sink{a.c, i};
     // Inputs read up front, as in sbp_kf_cand_kernel.
-    const bool room = !FILL || a.c.off[i + 1] <= a.c.cand_cap;
+    const bool room = sink.room();
     const bool live = a.valid[i] && !a.outlier[i];
     const float P[3] = {a.xyz[3 * i], a.xyz[3 * i + 1], a.xyz[3 * i + 2]};
     const int o = a.lk[i].octave;
@@ -869,9 +847,7 @@ __global__ __launch_bounds__(256) void sbp_last_cand_kernel(SbpLastArgs a) {
     int n = 0;
     {
         float pc[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            pc[r] = ((a.T[4 * r] * P[0] + a.T[4 * r + 1] * P[1]) + a.T[4 * r + 2] * P[2]) + a.T[4 * r + 3];
+        pose_apply(a.T, P, pc);
         const float invz = (float)(1.0 / (double)pc[2]);
         const float u = a.fx * pc[0] * invz + a.cx;
         const float v = a.fy * pc[1] * invz + a.cy;
@@ -880,24 +856,20 @@ __global__ __launch_bounds__(256) void sbp_last_cand_kernel(SbpLastArgs a) {
             const int lo = a.mode == 0 ? o - 1 : a.mode == 1 ? o : 0;
             const int hi = a.mode == 0 ? o + 1 : a.mode == 1 ? -1 : o;
             const uint4 q0 = a.desc[2 * i], q1 = a.desc[2 * i + 1];
-            int2* out = FILL ? a.c.cand + a.c.off[i] : kMode == 2 ? a.c.cand + (size_t)i * a.c.kfix : nullptr;
+            int2* out = sink.out();
             const float ur = u - a.bf * invz;
             n = features_in_area_wave(
                 a.cur, u, v, radius, lo, hi,
                 [&](int i2) { return !(a.cur.ur && a.cur.ur[i2] > 0 && fabsf(ur - a.cur.ur[i2]) > radius); },
                 [&](int i2, int rank) {
-                    if (FILL || (kMode == 2 && rank < a.c.kfix)) {
+                    sink.put(out, rank, i2, [&] {
                         const uint4* d = a.cur.desc + 2 * i2;
-                        out[rank] = make_int2(i2, hamming256(q0, q1, d[0], d[1]));
-                    }
+                        return hamming256(q0, q1, d[0], d[1]);
+                    });
                 });
         }
     }
-    if (kMode == 0 && (threadIdx.x & 63) == 0) a.c.cnt[i] = n;
-    if (kMode == 2 && (threadIdx.x & 63) == 0) {
-        a.c.cnt[i] = min(n, a.c.kfix);
-        if (n > a.c.kfix) atomicAdd(a.c.ovf, 1);
-    }
+    sink.finish(n);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -926,17 +898,15 @@ struct SbpKfArgs {
     CandArgs c;               // kMode 2 uses kfix / ovf
 };
 
-// kMode 0: count the candidates, 1: fill the CSR lists (after the scan), 2: the fixed-slot form
-// in one pass — the first kfix candidates of point i at i * kfix, min(n, kfix) in cnt[i], and a
-// point with more raises *ovf (the host then reruns the call on the CSR path).
+// kMode: CandSink's (orbfe_grid.hip)
 template <int kMode>
 __global__ __launch_bounds__(256) void sbp_kf_cand_kernel(SbpKfArgs a) {
-    constexpr bool FILL = kMode == 1;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per keyframe map point
     if (i >= a.n) return;
+    const CandSink<kMode> sink{a.c, i};
     // Every per-point input is read up front and feeds the unconditional arithmetic below, so
     // the loads issue together instead of one flag test (and one memory round trip) at a time.
-    const bool room = !FILL || a.c.off[i + 1] <= a.c.cand_cap;
+    const bool room = sink.room();
     const bool live = a.valid[i] && !a.bad[i] && !a.found[i];
     const float P[3] = {a.xyz[3 * i], a.xyz[3 * i + 1], a.xyz[3 * i + 2]};
     const float maxd = a.maxd[i], mind = a.mind[i];
@@ -944,42 +914,33 @@ __global__ __launch_bounds__(256) void sbp_kf_cand_kernel(SbpKfArgs a) {
     int n = 0;
     {
         float pc[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            pc[r] = ((a.T[4 * r] * P[0] + a.T[4 * r + 1] * P[1]) + a.T[4 * r + 2] * P[2]) + a.T[4 * r + 3];
+        pose_apply(a.T, P, pc);
         const float invz = (float)(1.0 / (double)pc[2]);  // 1.0/x3Dc.at<float>(2): double divide
         const float u = a.fx * pc[0] * invz + a.cx;
         const float v = a.fy * pc[1] * invz + a.cy;
         const float po0 = P[0] - a.ow[0], po1 = P[1] - a.ow[1], po2 = P[2] - a.ow[2];
         const float dist = (float)sqrt((double)po0 * po0 + (double)po1 * po1 + (double)po2 * po2);
-        const float dmax = 1.2f * maxd, dmin = 0.8f * mind;  // MapPoint.cc:621-631
+        const float dmax = kMaxDistInvariance * maxd, dmin = kMinDistInvariance * mind;
         const bool ok = live && !(u < a.minx || u > a.maxx) && !(v < a.miny || v > a.maxy) &&
                         !(dist < dmin || dist > dmax);
         if (ok) {
-            const float ratio = maxd / dist;
-            const int lvl = (int)ceilf((float)log((double)ratio) / a.log_scale);
-            if (lvl < 0 || lvl >= a.nlevels) {
-                if ((threadIdx.x & 63) == 0) atomicExch(a.status, ORBFE_ERR_UNSUPPORTED);  // mvScaleFactors[lvl]
-            } else {
+            const int lvl = predict_level(maxd, dist, a.log_scale);
+            if (level_in_pyramid(lvl, a.nlevels, a.status)) {
                 const float radius = a.th * a.scale[lvl];
                 const uint4 q0 = a.desc[2 * i], q1 = a.desc[2 * i + 1];
-                int2* out = FILL ? a.c.cand + a.c.off[i] : kMode == 2 ? a.c.cand + (size_t)i * a.c.kfix : nullptr;
+                int2* out = sink.out();
                 n = features_in_area_wave(
                     a.cur, u, v, radius, lvl - 1, lvl + 1, [](int) { return true; },
                     [&](int i2, int rank) {
-                        if (FILL || (kMode == 2 && rank < a.c.kfix)) {
+                        sink.put(out, rank, i2, [&] {
                             const uint4* d = a.cur.desc + 2 * i2;
-                            out[rank] = make_int2(i2, hamming256(q0, q1, d[0], d[1]));
-                        }
+                            return hamming256(q0, q1, d[0], d[1]);
+                        });
                     });
             }
         }
     }
-    if (kMode == 0 && (threadIdx.x & 63) == 0) a.c.cnt[i] = n;
-    if (kMode == 2 && (threadIdx.x & 63) == 0) {
-        a.c.cnt[i] = min(n, a.c.kfix);
-        if (n > a.c.kfix) atomicAdd(a.c.ovf, 1);
-    }
+    sink.finish(n);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1078,13 +1039,11 @@ __device__ __forceinline__ bool frustum_eval(const FrustumArgs& a, int i, Frustu
     const float maxd = a.maxd[i], mind = a.mind[i];
     const float Pv[3] = {P0, P1, P2};
     float pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-        pc[r] = ((a.T[4 * r] * Pv[0] + a.T[4 * r + 1] * Pv[1]) + a.T[4 * r + 2] * Pv[2]) + a.T[4 * r + 3];
+    pose_apply(a.T, Pv, pc);
     const float invz = 1.0f / pc[2];
     const float u = a.fx * pc[0] * invz + a.cx;
     const float v = a.fy * pc[1] * invz + a.cy;
-    const float dmax = 1.2f * maxd, dmin = 0.8f * mind;
+    const float dmax = kMaxDistInvariance * maxd, dmin = kMinDistInvariance * mind;
     const float po0 = P0 - a.ow[0], po1 = P1 - a.ow[1], po2 = P2 - a.ow[2];
     const float dist = (float)sqrt((double)po0 * po0 + (double)po1 * po1 + (double)po2 * po2);
     const double dot = (double)po0 * n0 + (double)po1 * n1 + (double)po2 * n2;
@@ -1092,8 +1051,8 @@ __device__ __forceinline__ bool frustum_eval(const FrustumArgs& a, int i, Frustu
     const bool in = !sk && !bd && !(pc[2] < 0.0f) && !(u < a.minx || u > a.maxx) &&
                     !(v < a.miny || v > a.maxy) && !(dist < dmin || dist > dmax) && !(vc < a.cos_limit);
     if (!in) return false;
-    const float ratio = maxd / dist;
-    o.lvl = (int)ceilf((float)log((double)ratio) / a.log_scale);
+    // stored as predicted: the local-map search judges it against the frame's pyramid
+    o.lvl = predict_level(maxd, dist, a.log_scale);
     o.u = u;
     o.ur = u - a.bf * invz;
     o.v = v;

@@ -982,7 +982,7 @@ int orbfe_search_for_initialization(orbfe_matcher* m, float nnratio, int check_o
         const int n1 = f1->n, n2 = f2->n;
         // 64 candidates per F1 keypoint to start; the first synchronisation of the rounds
         // checks that they fit
-        if ((st = m->cand_bounded(a, n1, 64, sfi_cand_kernel<false>, sfi_cand_kernel<true>))) return st;
+        if ((st = m->cand_bounded(a, n1, 64, sfi_cand_kernel<0>, sfi_cand_kernel<1>))) return st;
         // fixed-point rounds (sfi_round_kernel): decisions, slot lists, change flags
         const int L2 = std::max(n2, 1);
         if ((st = m->g_dec.ensure((size_t)2 * std::max(n1, 1) * sizeof(int)))) return st;

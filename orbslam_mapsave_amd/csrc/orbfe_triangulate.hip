@@ -69,20 +69,6 @@ struct TriArgs {
     int* status;               // ORBFE_ERR_UNSUPPORTED / ORBFE_ERR_ARG on bad input
 };
 
-// One workgroup per pair: vMatches12 = -1 (681), empty histogram, nmatches = 0 (679), the
-// pair's finished-workgroup counter; workgroup 0 clears the status.
-__global__ __launch_bounds__(256) void tri_init_kernel(TriArgs a) {
-    const int p = blockIdx.x;
-    int* mt = a.matches + (size_t)p * a.cap1;
-    for (int j = threadIdx.x; j < a.cap1; j += 256) mt[j] = -1;
-    if (threadIdx.x < 32) a.hist[p * 32 + threadIdx.x] = 0;
-    if (threadIdx.x == 0) {
-        a.nm[p] = 0;
-        a.done[p] = 0;
-        if (p == 0) *a.status = 0;
-    }
-}
-
 __device__ __forceinline__ float readlane_f(float v, int l) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
@@ -98,7 +84,6 @@ constexpr int kTriNodeMax = 256;  // keyframe-2 features per node held in regist
 __global__ __launch_bounds__(kTriBlock) void tri_search_kernel(TriArgs a) {
     __shared__ float s_epi_th[kMaxLevels];   // 100 * mvScaleFactors[octave] (750)
     __shared__ double s_line_th[kMaxLevels]; // 3.84 * mvLevelSigma2[octave], in double (156)
-    __shared__ int last;
     if (threadIdx.x < kMaxLevels) {
         const int l = threadIdx.x < a.nlevels ? threadIdx.x : 0;
         s_epi_th[threadIdx.x] = 100 * a.scale[l];
@@ -217,14 +202,8 @@ __global__ __launch_bounds__(kTriBlock) void tri_search_kernel(TriArgs a) {
                 // t is wave-uniform: v_readlane into scalar registers
                 const int i1 = __builtin_amdgcn_readlane(my_i1, t);
                 if (i1 < 0) continue;
-                const uint4 q0 = make_uint4(__builtin_amdgcn_readlane(my0.x, t),
-                                            __builtin_amdgcn_readlane(my0.y, t),
-                                            __builtin_amdgcn_readlane(my0.z, t),
-                                            __builtin_amdgcn_readlane(my0.w, t));
-                const uint4 q1 = make_uint4(__builtin_amdgcn_readlane(my1.x, t),
-                                            __builtin_amdgcn_readlane(my1.y, t),
-                                            __builtin_amdgcn_readlane(my1.z, t),
-                                            __builtin_amdgcn_readlane(my1.w, t));
+                uint4 q0, q1;
+                readlane_desc(my0, my1, t, q0, q1);
                 const float la = readlane_f(my_a, t), lb = readlane_f(my_b, t),
                             lc = readlane_f(my_c, t);
                 const bool st1 = __builtin_amdgcn_readlane(my_st1, t) != 0;
@@ -274,14 +253,8 @@ __global__ __launch_bounds__(kTriBlock) void tri_search_kernel(TriArgs a) {
         }
     }
     if (!a.check_ori) return;
-    // the pair's last workgroup to finish runs the orientation filter: every wave releases its
-    // matches / bins, the workgroup is counted, and the last one acquires everyone's
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(&a.done[p], 1) == (int)gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    // the pair's last workgroup to finish runs the orientation filter
+    if (!last_workgroup(&a.done[p])) return;
     ori_filter(matches, bins, hist, &a.nm[p], a.cap1);  // 794-813, shared with SearchByBoW
 }
 
@@ -291,7 +264,9 @@ using namespace orbfe;
 
 namespace {
 int tri_launch(orbfe_matcher* m, const TriArgs& a, int n_pairs, int gx) {
-    hipLaunchKernelGGL(tri_init_kernel, dim3(n_pairs), dim3(256), 0, m->stream, a);
+    // vMatches12 = -1 (681) per keyframe-1 feature, nmatches = 0 (679)
+    hipLaunchKernelGGL(pair_init_kernel, dim3(n_pairs), dim3(256), 0, m->stream, a.matches, a.cap1,
+                       a.hist, a.nm, a.done, a.status);
     hipLaunchKernelGGL(tri_search_kernel, dim3(gx, n_pairs), dim3(kTriBlock), 0, m->stream, a);
     ORBFE_HIP(hipGetLastError());
     return ORBFE_OK;

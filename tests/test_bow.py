@@ -286,7 +286,7 @@ def test_gpu_search_by_bow(ori, ratio, zc, path, vocab_paths, frames, monkeypatc
     device-mapped pinned memory, one bow_search1_kernel launch writing each frame feature's
     outcome to its pinned slot, the orientation filter on the host), the general path with
     the pair's last workgroup writing the results into pinned memory (ORBFE_BOW1=0), and through
-    bow_init_kernel + D2H copies (ORBFE_ZERO_COPY=0); three calls on one matcher (counters,
+    pair_init_kernel + D2H copies (ORBFE_ZERO_COPY=0); three calls on one matcher (counters,
     histogram and staging reused)."""
     monkeypatch.setenv("ORBFE_ZERO_COPY", zc)
     monkeypatch.setenv("ORBFE_BOW1", "1" if path == "gathered" else "0")
