@@ -807,6 +807,138 @@ int orbfe_search_for_triangulation_batch_device(
     const float* scale_factors, const float* level_sigma2, int nlevels, int32_t* d_matches12,
     int32_t* d_nmatches, int32_t* d_status);
 
+/* ---- BoW scores and the keyframe database -------------------------------------------------- */
+
+/* Which build of DBoW2's scoring loops orbfe_vocabulary_score* and the database queries
+ * reproduce.  DBoW2 is compiled -O3 -march=native
+ * (Thirdparty/DBoW2/CMakeLists.txt:4-5), so on an FMA host GCC contracts `score += vi * wi` of
+ * the L2 and dot-product loops (ScoringObject.cpp:91, :290) into fma(vi, wi, score):
+ * ORBFE_ARITH_X86_SIMD (the default) computes that, ORBFE_ARITH_SCALAR the uncontracted product
+ * and sum.  L1, chi-square and Bhattacharyya have no product feeding an add and are the same in
+ * both.  Applies to later calls. */
+int orbfe_vocabulary_set_arithmetic(orbfe_vocabulary* v, int mode);
+
+/* ORBVocabulary::score(v1, v2) (TemplatedVocabulary.h -> ScoringObject.cpp:23-311) with the
+ * vocabulary's scoring: 0 L1 (:23-68), 1 L2 (:73-120), 2 chi-square (:125-170),
+ * 4 Bhattacharyya (:226-266), 5 dot product (:271-311).  BowVectors are n ascending word ids +
+ * values (as orbfe_bow_transform writes them; any values are accepted).  The common words' terms
+ * are added to one double accumulator in ascending word order and the last step of each formula
+ * is as written, so *score has the reference's bits (double sqrt and / are correctly rounded on
+ * the device).  KL scoring (3, :175-221) returns ORBFE_ERR_UNSUPPORTED: it needs log, and the
+ * device log is within 1 ulp, not correctly rounded.  Word ids that are not strictly ascending
+ * return ORBFE_ERR_ARG.  Computed on the device; synchronous. */
+int orbfe_vocabulary_score(orbfe_vocabulary* v, const int32_t* ids1, const double* vals1, int n1,
+                           const int32_t* ids2, const double* vals2, int n2, double* score);
+/* Batched device form, e.g. the minScore loop of LoopClosing::DetectLoop (LoopClosing.cc:125-139):
+ * d_score[p] = score(slot d_pair_a[p], slot d_pair_b[p]) over slots in the layout
+ * orbfe_bow_transform_batch_device writes (word ids / values at s*cap, d_nw[s]).  One wave per
+ * pair; asynchronous on the vocabulary's stream. */
+int orbfe_vocabulary_score_batch_device(orbfe_vocabulary* v, int n_pairs, const int32_t* d_pair_a,
+                                        const int32_t* d_pair_b, int cap,
+                                        const int32_t* d_word_ids, const double* d_values,
+                                        const int32_t* d_nw, double* d_score);
+
+/* The keyframe database, KeyFrameDatabase (KeyFrameDatabase.h:48-94): keyframes are slots of
+ * device memory in the BoW-transform layout (word ids and values at s*cap, nw[s]); storage grows
+ * by doubling inside orbfe_kfdb_add*, never inside a query, and never shrinks.  The device keeps
+ * no inverted file: the order of the reference's walk over mvInvertedFile ("query words
+ * ascending, each word's list in add order") is the sort key (first common word, add sequence).
+ * A handle is not reentrant; the vocabulary must outlive it.  Queries run on the handle's own
+ * stream (orbfe_kfdb_set_stream) with the vocabulary's scoring and arithmetic. */
+typedef struct orbfe_kfdb orbfe_kfdb;
+
+/* The per-keyframe query state the reference keeps on the KeyFrame (KeyFrame.h:166-171):
+ * mnLoopQuery, mnLoopWords, mLoopScore, mnRelocQuery, mnRelocWords, mRelocScore.  The four
+ * integers start at 0 (KeyFrame.cc:35, :64); the two scores are not initialised by the
+ * reference: scores_set bit 0 / 1 tells whether loop_score / reloc_score was ever written (by a
+ * query or orbfe_kfdb_set_scores). */
+typedef struct orbfe_kfdb_state {
+    uint64_t loop_query, reloc_query;
+    int32_t  loop_words, reloc_words;
+    float    loop_score, reloc_score;
+    int32_t  scores_set;
+    int32_t  reserved;
+} orbfe_kfdb_state;
+
+/* KeyFrameDatabase::KeyFrameDatabase (KeyFrameDatabase.cc:33-37).  cap <= 4096 words per
+ * keyframe; slots_hint sizes the first allocation. */
+orbfe_kfdb* orbfe_kfdb_create(orbfe_vocabulary* voc, int cap, int slots_hint, int* status);
+void orbfe_kfdb_destroy(orbfe_kfdb* db);
+int  orbfe_kfdb_set_stream(orbfe_kfdb* db, void* hip_stream);
+/* Keyframes in the database. */
+int  orbfe_kfdb_size(const orbfe_kfdb* db);
+
+/* KeyFrameDatabase::add (KeyFrameDatabase.cc:115-121): a keyframe's BowVector (host arrays) into
+ * a slot, returned in *slot; the most recently freed slot is reused first.  Each add takes the
+ * next sequence number: add pushes the keyframe to the back of every word's list, so the order
+ * inside every inverted list is add order, whatever the slot.  The slot's state is a new
+ * KeyFrame's.  Word ids not strictly ascending, or one >= the vocabulary's word count (where the
+ * reference indexes mvInvertedFile out of range), return ORBFE_ERR_ARG. */
+int orbfe_kfdb_add(orbfe_kfdb* db, const int32_t* word_ids, const double* values, int nw,
+                   int32_t* slot);
+/* The same from device memory — one slot of a transform batch's output (d_word_ids + f*cap,
+ * d_values + f*cap, d_nw + f): a device-to-device copy, validated on the device. */
+int orbfe_kfdb_add_device(orbfe_kfdb* db, const int32_t* d_word_ids, const double* d_values,
+                          const int32_t* d_nw, int32_t* slot);
+/* KeyFrameDatabase::erase (KeyFrameDatabase.cc:123-142): frees the slot and removes it from
+ * every covisibility list, so a neighbour entry never names a recycled slot.  A slot that is not
+ * in use returns ORBFE_ERR_ARG. */
+int orbfe_kfdb_erase(orbfe_kfdb* db, int slot);
+/* KeyFrameDatabase::clear (KeyFrameDatabase.cc:144-148). */
+int orbfe_kfdb_clear(orbfe_kfdb* db);
+/* pKF->GetBestCovisibilityKeyFrames(10) (KeyFrame.cc:895-903) of the keyframe in `slot`, in its
+ * order: n <= 10 slots.  A neighbour that is not in the database is passed as -1: it keeps its
+ * place in the truncation and is skipped (no query can have touched it). */
+int orbfe_kfdb_set_covisibility(orbfe_kfdb* db, int slot, int n, const int32_t* neigh_slots);
+/* mLoopScore / mRelocScore of a keyframe loaded from a map archive (KeyFrame.cc:112-115). */
+int orbfe_kfdb_set_scores(orbfe_kfdb* db, int slot, float loop_score, float reloc_score);
+int orbfe_kfdb_get_state(orbfe_kfdb* db, int slot, orbfe_kfdb_state* state);
+
+/* KeyFrameDatabase::DetectLoopCandidates(pKF, minScore) (KeyFrameDatabase.cc:151-272).
+ * query_id = pKF->mnId, (word_ids, values, nw) = pKF->mBowVec, conn_slots = the slots of
+ * pKF->GetConnectedKeyFrames() (:153), min_score = minScore.  cand receives vpLoopCandidates as
+ * slots, in the reference's order; *n_cand their count (> cand_cap: ORBFE_ERR_CAPACITY and
+ * nothing copied).  Every touched slot's state is updated as the reference updates the
+ * KeyFrame, also on the early returns (:182, :216).  ORBFE_ERR_UNSUPPORTED with valid results:
+ * the accumulation (:236) read a score that was never written, computed as 0.0f.
+ * A query id equal to a slot's stored id (0 for a new keyframe) is reproduced literally
+ * (DESIGN.md H19).  More than 4096 keyframes in lScoreAndMatch: ORBFE_ERR_CAPACITY with
+ * *n_cand = that count (a limit of this implementation).  Either ORBFE_ERR_CAPACITY is returned
+ * after the query ran: every touched slot's query id, word count and score are already
+ * updated, as after a successful call, so a retry with a larger buffer must use a query id no
+ * slot stores, or it takes the H19 path and answers differently.  One kernel launch; the host
+ * waits on a done word in pinned memory. */
+int orbfe_kfdb_detect_loop_candidates(orbfe_kfdb* db, uint64_t query_id, const int32_t* word_ids,
+                                      const double* values, int nw, int n_conn,
+                                      const int32_t* conn_slots, float min_score, int32_t* cand,
+                                      int cand_cap, int32_t* n_cand);
+/* KeyFrameDatabase::DetectRelocalizationCandidates(F) (KeyFrameDatabase.cc:274-389);
+ * frame_id = F->mnId.  Otherwise as above (early returns :304, :335; the accumulation :353-356
+ * tests mnRelocQuery only, so it may read the mRelocScore an earlier query left). */
+int orbfe_kfdb_detect_relocalization_candidates(orbfe_kfdb* db, uint64_t frame_id,
+                                                const int32_t* word_ids, const double* values,
+                                                int nw, int32_t* cand, int cand_cap,
+                                                int32_t* n_cand);
+/* Device forms: the query vector (d_word_ids, d_values, *d_nw — e.g. one slot of a transform
+ * batch's output) and the connected slots are read from device memory and the candidates are
+ * left in d_cand (at most cand_cap written), ready to be the d_pair_kf of
+ * orbfe_search_by_bow_batch_device or the d_pair_kf2 of
+ * orbfe_search_by_bow_keyframes_batch_device; the count returns to the host in *n_cand, since
+ * n_pairs of those calls is a host argument.  The host waits once, on the done word.  The
+ * query vector is validated on the device before any state is touched: *d_nw outside
+ * [0, cap of the database] (e.g. a transform batch with a larger cap) or word ids that are not
+ * strictly ascending return ORBFE_ERR_ARG with *n_cand = 0, as the host forms do. */
+int orbfe_kfdb_detect_loop_candidates_device(orbfe_kfdb* db, uint64_t query_id,
+                                             const int32_t* d_word_ids, const double* d_values,
+                                             const int32_t* d_nw, int n_conn,
+                                             const int32_t* d_conn_slots, float min_score,
+                                             int32_t* d_cand, int cand_cap, int32_t* n_cand);
+int orbfe_kfdb_detect_relocalization_candidates_device(orbfe_kfdb* db, uint64_t frame_id,
+                                                       const int32_t* d_word_ids,
+                                                       const double* d_values,
+                                                       const int32_t* d_nw, int32_t* d_cand,
+                                                       int cand_cap, int32_t* n_cand);
+
 /* ---- map-archive records of the extractor outputs (device side) ---------------------------
  * The bodies the reference's Boost map archive stores for the extractor's outputs, written
  * from / read into HBM (MapPoint.h:196-247; KeyFrame::serialize KeyFrame.cc:133-134 / 354-355

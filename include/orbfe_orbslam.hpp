@@ -10,6 +10,7 @@
 #include <cmath>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -535,6 +536,143 @@ private:
     // SearchBySim3 / SearchByBoW(KF, KF): the per-feature masks and the index-valued matches
     std::vector<uint8_t> sim3_search1_, sim3_search2_;
     std::vector<int> sim3_m12_;
+};
+
+// A DBoW2::BowVector (std::map<WordId, WordValue>) as two parallel arrays, word ids ascending —
+// what orbfe_bow_transform writes.
+struct BowVector {
+    std::vector<int32_t> ids;
+    std::vector<double> values;
+};
+
+// ORB_SLAM2::ORBVocabulary (ORBVocabulary.h:31-32, DBoW2 TemplatedVocabulary<FORB>) held on the GPU.
+class ORBVocabulary {
+public:
+    // loadFromTextFile (TemplatedVocabulary.h:1351-1436)
+    explicit ORBVocabulary(const std::string& path, int device = 0) {
+        int st = ORBFE_OK;
+        v_ = orbfe_vocabulary_load_text(path.c_str(), device, &st);
+        if (!v_) throw Error("orbfe_vocabulary_load_text", st);
+    }
+    ~ORBVocabulary() { orbfe_vocabulary_destroy(v_); }
+    ORBVocabulary(const ORBVocabulary&) = delete;
+    ORBVocabulary& operator=(const ORBVocabulary&) = delete;
+
+    // size() (TemplatedVocabulary.h:122): the number of words
+    int size() const {
+        int32_t info[6];
+        check("orbfe_vocabulary_info", orbfe_vocabulary_info(v_, info));
+        return info[5];
+    }
+    // score(v1, v2) (TemplatedVocabulary.h -> ScoringObject.cpp:23-311)
+    double score(const BowVector& v1, const BowVector& v2) const {
+        double s = 0.0;
+        check("orbfe_vocabulary_score",
+              orbfe_vocabulary_score(v_, v1.ids.data(), v1.values.data(), (int)v1.ids.size(),
+                                     v2.ids.data(), v2.values.data(), (int)v2.ids.size(), &s));
+        return s;
+    }
+    orbfe_vocabulary* handle() const { return v_; }
+
+private:
+    orbfe_vocabulary* v_ = nullptr;
+};
+
+// ORB_SLAM2::KeyFrameDatabase (KeyFrameDatabase.h:48-94) keyed by the caller's keyframe ids
+// (KeyFrame::mnId); it holds the id <-> slot map of the device database.
+class KeyFrameDatabase {
+public:
+    explicit KeyFrameDatabase(const ORBVocabulary& voc, int cap = 4096, int slots_hint = 0) {
+        int st = ORBFE_OK;
+        db_ = orbfe_kfdb_create(voc.handle(), cap, slots_hint, &st);
+        if (!db_) throw Error("orbfe_kfdb_create", st);
+    }
+    ~KeyFrameDatabase() { orbfe_kfdb_destroy(db_); }
+    KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+    KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+
+    // add(pKF) (KeyFrameDatabase.cc:115-121).  An id already present throws
+    // Error(ORBFE_ERR_UNSUPPORTED): the reference would list the keyframe twice in every word's
+    // list and count its words double.
+    void add(uint64_t mnId, const BowVector& bow) {
+        if (slot_of(mnId) >= 0) throw Error("KeyFrameDatabase::add", ORBFE_ERR_UNSUPPORTED);
+        int32_t slot = -1;
+        check("orbfe_kfdb_add", orbfe_kfdb_add(db_, bow.ids.data(), bow.values.data(),
+                                               (int)bow.ids.size(), &slot));
+        if ((size_t)slot >= id_.size()) id_.resize((size_t)slot + 1, 0);
+        id_[slot] = mnId;
+        slot_[mnId] = slot;
+    }
+    // erase(pKF) (KeyFrameDatabase.cc:123-142); an unknown id is ignored, as there.
+    void erase(uint64_t mnId) {
+        const int slot = slot_of(mnId);
+        if (slot < 0) return;
+        check("orbfe_kfdb_erase", orbfe_kfdb_erase(db_, slot));
+        slot_.erase(mnId);
+    }
+    void clear() {  // KeyFrameDatabase.cc:144-148
+        check("orbfe_kfdb_clear", orbfe_kfdb_clear(db_));
+        slot_.clear();
+    }
+    // pKF->GetBestCovisibilityKeyFrames(10) (KeyFrame.cc:895-903) as ids, at most 10, in its
+    // order; ids that are not in the database keep their place and are skipped.  The ids are
+    // resolved to slots now: a neighbour that enters the database later is not seen until the
+    // list is set again (an erased one leaves every list by itself).
+    void SetBestCovisibilityKeyFrames(uint64_t mnId, const std::vector<uint64_t>& neighbours) {
+        const int slot = slot_of(mnId);
+        if (slot < 0 || neighbours.size() > 10)
+            throw Error("KeyFrameDatabase::SetBestCovisibilityKeyFrames", ORBFE_ERR_ARG);
+        int32_t n[10];
+        for (size_t i = 0; i < neighbours.size(); ++i) n[i] = slot_of(neighbours[i]);
+        check("orbfe_kfdb_set_covisibility",
+              orbfe_kfdb_set_covisibility(db_, slot, (int)neighbours.size(), n));
+    }
+    // DetectLoopCandidates(pKF, minScore) (KeyFrameDatabase.cc:151-272): mnId, mBowVec and
+    // GetConnectedKeyFrames() of pKF.  Returns vpLoopCandidates as ids.  `uninitialised` (may be
+    // null) is set when the reference would have read a score it never wrote.
+    std::vector<uint64_t> DetectLoopCandidates(uint64_t mnId, const BowVector& bow,
+                                               const std::vector<uint64_t>& connected,
+                                               float minScore, bool* uninitialised = nullptr) {
+        std::vector<int32_t> conn;
+        for (uint64_t c : connected) {
+            const int s = slot_of(c);
+            if (s >= 0) conn.push_back(s);
+        }
+        std::vector<int32_t> cand(std::max<size_t>(id_.size(), 1));
+        int32_t n = 0;
+        const int st = orbfe_kfdb_detect_loop_candidates(
+            db_, mnId, bow.ids.data(), bow.values.data(), (int)bow.ids.size(), (int)conn.size(),
+            conn.data(), minScore, cand.data(), (int)cand.size(), &n);
+        return result("orbfe_kfdb_detect_loop_candidates", st, cand, n, uninitialised);
+    }
+    // DetectRelocalizationCandidates(F) (KeyFrameDatabase.cc:274-389): mnId and mBowVec of F.
+    std::vector<uint64_t> DetectRelocalizationCandidates(uint64_t mnId, const BowVector& bow,
+                                                         bool* uninitialised = nullptr) {
+        std::vector<int32_t> cand(std::max<size_t>(id_.size(), 1));
+        int32_t n = 0;
+        const int st = orbfe_kfdb_detect_relocalization_candidates(
+            db_, mnId, bow.ids.data(), bow.values.data(), (int)bow.ids.size(), cand.data(),
+            (int)cand.size(), &n);
+        return result("orbfe_kfdb_detect_relocalization_candidates", st, cand, n, uninitialised);
+    }
+    orbfe_kfdb* handle() const { return db_; }
+
+private:
+    int slot_of(uint64_t mnId) const {
+        const auto it = slot_.find(mnId);
+        return it == slot_.end() ? -1 : it->second;
+    }
+    std::vector<uint64_t> result(const char* fn, int st, const std::vector<int32_t>& cand, int n,
+                                 bool* uninitialised) const {
+        if (st != ORBFE_OK && st != ORBFE_ERR_UNSUPPORTED) throw Error(fn, st);
+        if (uninitialised) *uninitialised = st == ORBFE_ERR_UNSUPPORTED;
+        std::vector<uint64_t> out;
+        for (int i = 0; i < n; ++i) out.push_back(id_[cand[i]]);
+        return out;
+    }
+    orbfe_kfdb* db_ = nullptr;
+    std::vector<uint64_t> id_;                 // slot -> mnId
+    std::unordered_map<uint64_t, int> slot_;   // mnId -> slot, the keyframes in the database
 };
 
 }  // namespace orbfe

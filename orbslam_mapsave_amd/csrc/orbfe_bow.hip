@@ -678,6 +678,10 @@ struct orbfe_vocabulary {
     DevBuf child_off, child_ids, desc, word, weight;
     // per-call scratch / staging (host forms)
     DevBuf s_desc, s_n, s_word, s_node, s_w, o_wid, o_val, o_nw, o_nid, o_noff, o_feat, o_nn;
+    // ORBVocabulary::score (orbfe_kfdb.hip): which build of the L2 / dot-product loops it
+    // reproduces (orbfe_vocabulary_set_arithmetic) and the host form's scratch
+    int arith = ORBFE_ARITH_X86_SIMD;
+    DevBuf k_score;
     hipStream_t own = nullptr, stream = nullptr;
     // the host transform's staging: descriptors in, results out, in one device-mapped pinned
     // block the kernels read and write directly (no H2D / D2H copies); null: DMA copies

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from .abi import (KEYPOINT_DTYPE, ORBFE_ERR_CAPACITY, ORBFE_OK, Camera, Frame, FrameView,
+from .abi import (KEYPOINT_DTYPE, ORBFE_ERR_CAPACITY, ORBFE_ERR_UNSUPPORTED, ORBFE_OK, Camera, Frame, FrameView,
                   MapPoints, MapPointView, OrbfeError, Params, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -55,6 +55,14 @@ EXPORTED = [
     "orbfe_search_by_bow_keyframes", "orbfe_search_by_bow_keyframes_batch_device",
     "orbfe_search_by_projection_sim3", "orbfe_search_by_sim3",
     "orbfe_search_for_triangulation", "orbfe_search_for_triangulation_batch_device",
+    "orbfe_vocabulary_set_arithmetic", "orbfe_vocabulary_score",
+    "orbfe_vocabulary_score_batch_device",
+    "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_set_stream", "orbfe_kfdb_size",
+    "orbfe_kfdb_add", "orbfe_kfdb_add_device", "orbfe_kfdb_erase", "orbfe_kfdb_clear",
+    "orbfe_kfdb_set_covisibility", "orbfe_kfdb_set_scores", "orbfe_kfdb_get_state",
+    "orbfe_kfdb_detect_loop_candidates", "orbfe_kfdb_detect_relocalization_candidates",
+    "orbfe_kfdb_detect_loop_candidates_device",
+    "orbfe_kfdb_detect_relocalization_candidates_device",
     "orbfe_archive_mat_bytes",
     "orbfe_archive_write_keypoints_device", "orbfe_archive_read_keypoints_device",
     "orbfe_archive_write_descriptors_device", "orbfe_archive_read_descriptors_device",
@@ -86,6 +94,30 @@ def lib() -> C.CDLL:
             L.orbfe_vocabulary_load_text.argtypes = [C.c_char_p, C.c_int, C.c_void_p]
             L.orbfe_vocabulary_create.restype = C.c_void_p
             L.orbfe_vocabulary_destroy.argtypes = [C.c_void_p]
+        if hasattr(L, "orbfe_kfdb_create"):
+            vp, i, u64, f = C.c_void_p, C.c_int, C.c_uint64, C.c_float
+            L.orbfe_vocabulary_set_arithmetic.argtypes = [vp, i]
+            L.orbfe_vocabulary_score.argtypes = [vp, vp, vp, i, vp, vp, i, vp]
+            L.orbfe_vocabulary_score_batch_device.argtypes = [vp, i, vp, vp, i, vp, vp, vp, vp]
+            L.orbfe_kfdb_create.restype = vp
+            L.orbfe_kfdb_create.argtypes = [vp, i, i, vp]
+            L.orbfe_kfdb_destroy.restype = None
+            L.orbfe_kfdb_destroy.argtypes = [vp]
+            L.orbfe_kfdb_set_stream.argtypes = [vp, vp]
+            L.orbfe_kfdb_size.argtypes = [vp]
+            L.orbfe_kfdb_add.argtypes = [vp, vp, vp, i, vp]
+            L.orbfe_kfdb_add_device.argtypes = [vp, vp, vp, vp, vp]
+            L.orbfe_kfdb_erase.argtypes = [vp, i]
+            L.orbfe_kfdb_clear.argtypes = [vp]
+            L.orbfe_kfdb_set_covisibility.argtypes = [vp, i, i, vp]
+            L.orbfe_kfdb_set_scores.argtypes = [vp, i, f, f]
+            L.orbfe_kfdb_get_state.argtypes = [vp, i, vp]
+            L.orbfe_kfdb_detect_loop_candidates.argtypes = [vp, u64, vp, vp, i, i, vp, f, vp, i, vp]
+            L.orbfe_kfdb_detect_relocalization_candidates.argtypes = [vp, u64, vp, vp, i, vp, i, vp]
+            L.orbfe_kfdb_detect_loop_candidates_device.argtypes = [vp, u64, vp, vp, vp, i, vp, f,
+                                                                   vp, i, vp]
+            L.orbfe_kfdb_detect_relocalization_candidates_device.argtypes = [vp, u64, vp, vp, vp,
+                                                                             vp, i, vp]
         if hasattr(L, "orbfe_archive_mat_bytes"):
             L.orbfe_archive_mat_bytes.restype = C.c_int64
             sz, vp, i = C.c_size_t, C.c_void_p, C.c_int
@@ -544,6 +576,153 @@ class Vocabulary:
     def set_stream(self, stream_handle: int | None) -> None:
         _check("orbfe_vocabulary_set_stream", lib().orbfe_vocabulary_set_stream(
             self._h, _stream_arg(stream_handle)))
+
+    def set_arithmetic(self, mode: int) -> None:
+        """ORBFE_ARITH_X86_SIMD (1, default): the L2 / dot-product sums contracted to fma as the
+        reference's -march=native build; ORBFE_ARITH_SCALAR (0): uncontracted."""
+        _check("orbfe_vocabulary_set_arithmetic",
+               lib().orbfe_vocabulary_set_arithmetic(self._h, mode))
+
+    def score(self, ids1, vals1, ids2, vals2) -> float:
+        """ORBVocabulary::score(v1, v2) with the vocabulary's scoring (ScoringObject.cpp:23-311)."""
+        i1, v1 = np.ascontiguousarray(ids1, np.int32), np.ascontiguousarray(vals1, np.float64)
+        i2, v2 = np.ascontiguousarray(ids2, np.int32), np.ascontiguousarray(vals2, np.float64)
+        out = C.c_double(0.0)
+        _check("orbfe_vocabulary_score", lib().orbfe_vocabulary_score(
+            self._h, ptr(i1), ptr(v1), len(i1), ptr(i2), ptr(v2), len(i2), C.byref(out)))
+        return out.value
+
+    def score_batch_device(self, n_pairs: int, d_pair_a: int, d_pair_b: int, cap: int,
+                           d_wid: int, d_val: int, d_nw: int, d_score: int) -> None:
+        _check("orbfe_vocabulary_score_batch_device", lib().orbfe_vocabulary_score_batch_device(
+            self._h, n_pairs, C.c_void_p(d_pair_a), C.c_void_p(d_pair_b), cap, C.c_void_p(d_wid),
+            C.c_void_p(d_val), C.c_void_p(d_nw), C.c_void_p(d_score)))
+
+
+class KfdbState(C.Structure):
+    """orbfe_kfdb_state: the six fields of KeyFrame.h:166-171 and which scores were written."""
+    _fields_ = [("loop_query", C.c_uint64), ("reloc_query", C.c_uint64),
+                ("loop_words", C.c_int32), ("reloc_words", C.c_int32),
+                ("loop_score", C.c_float), ("reloc_score", C.c_float),
+                ("scores_set", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KeyFrameDatabase:
+    """KeyFrameDatabase (KeyFrameDatabase.cc:115-389) over device slots.  Keyframes are named by
+    the slot ``add`` returns.  The two queries return ``(candidates, status)``: status is
+    ORBFE_OK, or ORBFE_ERR_UNSUPPORTED when the reference would have read a score it never wrote
+    (the candidates are then computed with 0.0f); other errors raise."""
+
+    def __init__(self, voc: Vocabulary, cap: int = 4096, slots_hint: int = 0):
+        st = C.c_int(0)
+        h = lib().orbfe_kfdb_create(voc._h, cap, slots_hint, C.byref(st))
+        if not h:
+            raise OrbfeError("orbfe_kfdb_create", st.value)
+        self._h = C.c_void_p(h)
+        self._voc = voc  # the vocabulary must outlive the database
+        self.cap = cap
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().orbfe_kfdb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return lib().orbfe_kfdb_size(self._h)
+
+    def set_stream(self, stream_handle: int | None) -> None:
+        _check("orbfe_kfdb_set_stream", lib().orbfe_kfdb_set_stream(
+            self._h, _stream_arg(stream_handle)))
+
+    def add(self, word_ids, values) -> int:
+        ids = np.ascontiguousarray(word_ids, np.int32)
+        val = np.ascontiguousarray(values, np.float64)
+        slot = C.c_int32(-1)
+        _check("orbfe_kfdb_add", lib().orbfe_kfdb_add(self._h, ptr(ids), ptr(val), len(ids),
+                                                      C.byref(slot)))
+        return slot.value
+
+    def add_device(self, d_wid: int, d_val: int, d_nw: int) -> int:
+        slot = C.c_int32(-1)
+        _check("orbfe_kfdb_add_device", lib().orbfe_kfdb_add_device(
+            self._h, C.c_void_p(d_wid), C.c_void_p(d_val), C.c_void_p(d_nw), C.byref(slot)))
+        return slot.value
+
+    def erase(self, slot: int) -> None:
+        _check("orbfe_kfdb_erase", lib().orbfe_kfdb_erase(self._h, slot))
+
+    def clear(self) -> None:
+        _check("orbfe_kfdb_clear", lib().orbfe_kfdb_clear(self._h))
+
+    def set_covisibility(self, slot: int, neigh_slots) -> None:
+        n = np.ascontiguousarray(neigh_slots, np.int32)
+        _check("orbfe_kfdb_set_covisibility", lib().orbfe_kfdb_set_covisibility(
+            self._h, slot, len(n), ptr(n)))
+
+    def set_scores(self, slot: int, loop_score: float, reloc_score: float) -> None:
+        _check("orbfe_kfdb_set_scores", lib().orbfe_kfdb_set_scores(
+            self._h, slot, loop_score, reloc_score))
+
+    def get_state(self, slot: int) -> KfdbState:
+        s = KfdbState()
+        _check("orbfe_kfdb_get_state", lib().orbfe_kfdb_get_state(self._h, slot, C.byref(s)))
+        return s
+
+    @staticmethod
+    def _result(fn: str, st: int, cand: np.ndarray, n: int):
+        if st not in (ORBFE_OK, ORBFE_ERR_UNSUPPORTED):
+            raise OrbfeError(fn, st)
+        return cand[:n].copy(), st
+
+    def DetectLoopCandidates(self, query_id: int, word_ids, values, conn_slots, min_score: float,
+                             cand_cap: int = 4096):
+        ids = np.ascontiguousarray(word_ids, np.int32)
+        val = np.ascontiguousarray(values, np.float64)
+        conn = np.ascontiguousarray(conn_slots, np.int32)
+        cand = np.zeros(max(cand_cap, 1), np.int32)
+        n = C.c_int32(0)
+        st = lib().orbfe_kfdb_detect_loop_candidates(
+            self._h, query_id, ptr(ids), ptr(val), len(ids), len(conn), ptr(conn), min_score,
+            ptr(cand), cand_cap, C.byref(n))
+        return self._result("orbfe_kfdb_detect_loop_candidates", st, cand, n.value)
+
+    def DetectRelocalizationCandidates(self, frame_id: int, word_ids, values,
+                                       cand_cap: int = 4096):
+        ids = np.ascontiguousarray(word_ids, np.int32)
+        val = np.ascontiguousarray(values, np.float64)
+        cand = np.zeros(max(cand_cap, 1), np.int32)
+        n = C.c_int32(0)
+        st = lib().orbfe_kfdb_detect_relocalization_candidates(
+            self._h, frame_id, ptr(ids), ptr(val), len(ids), ptr(cand), cand_cap, C.byref(n))
+        return self._result("orbfe_kfdb_detect_relocalization_candidates", st, cand, n.value)
+
+    def detect_loop_candidates_device(self, query_id: int, d_wid: int, d_val: int, d_nw: int,
+                                      n_conn: int, d_conn: int, min_score: float, d_cand: int,
+                                      cand_cap: int):
+        """-> (n_cand, status); the candidates stay in d_cand."""
+        n = C.c_int32(0)
+        st = lib().orbfe_kfdb_detect_loop_candidates_device(
+            self._h, query_id, C.c_void_p(d_wid), C.c_void_p(d_val), C.c_void_p(d_nw), n_conn,
+            C.c_void_p(d_conn), min_score, C.c_void_p(d_cand), cand_cap, C.byref(n))
+        if st not in (ORBFE_OK, ORBFE_ERR_UNSUPPORTED):
+            raise OrbfeError("orbfe_kfdb_detect_loop_candidates_device", st)
+        return n.value, st
+
+    def detect_relocalization_candidates_device(self, frame_id: int, d_wid: int, d_val: int,
+                                                d_nw: int, d_cand: int, cand_cap: int):
+        n = C.c_int32(0)
+        st = lib().orbfe_kfdb_detect_relocalization_candidates_device(
+            self._h, frame_id, C.c_void_p(d_wid), C.c_void_p(d_val), C.c_void_p(d_nw),
+            C.c_void_p(d_cand), cand_cap, C.byref(n))
+        if st not in (ORBFE_OK, ORBFE_ERR_UNSUPPORTED):
+            raise OrbfeError("orbfe_kfdb_detect_relocalization_candidates_device", st)
+        return n.value, st
 
 
 class ORBmatcher:

@@ -740,11 +740,74 @@ def row_loop():
     ov.close()
 
 
+def row_kfdb(tmpdir):
+    """The keyframe database: one relocalisation query and one loop query (host forms, each with
+    its wait) against 2000 keyframes of 1000 words each in the bench vocabulary (k = 10, L = 6),
+    words drawn from a 20000-word scene pool so that a query shares ~50 words with a keyframe;
+    every keyframe's covisibility list is its 10 predecessors, the loop query's connected set
+    the 10 newest keyframes.  Comparator: tests/cpp/kfdb_test --time, a one-thread std::list
+    inverted-file walk of the same script on this machine's host.  Two repeats of each."""
+    import ctypes as C
+    import subprocess
+    import kfdb_cases as K
+    parent, word, desc, weight = vocab_arrays(10, 6, 0)
+    L = native.lib()
+    st = C.c_int(0)
+    h = L.orbfe_vocabulary_create(10, 6, 0, 0, len(parent), native.ptr(parent), native.ptr(word),
+                                  native.ptr(desc), native.ptr(weight), 0, C.byref(st))
+    assert h, st.value
+    gv = native.Vocabulary.__new__(native.Vocabulary)
+    gv._h = C.c_void_p(h)
+    nkf, nw = 2000, 1000
+    rng = np.random.Generator(np.random.PCG64(11))
+    pool = np.sort(rng.choice(10 ** 6, 20000, replace=False)).astype(np.int32)
+
+    def bow():
+        ids = np.sort(rng.choice(pool, nw, replace=False)).astype(np.int32)
+        v = rng.uniform(0.2, 4.0, nw)
+        return ids, v / v.sum()
+    db = native.KeyFrameDatabase(gv, 1024, nkf)
+    script = []
+    for i in range(nkf):
+        b = bow()
+        script.append(("add", "k%d" % i, *b))
+        assert db.add(*b) == i
+    for i in range(nkf):
+        n = list(range(max(i - 10, 0), i))[::-1]
+        script.append(("covis", "k%d" % i, ["k%d" % j for j in n]))
+        db.set_covisibility(i, n)
+    q = bow()
+    conn = list(range(nkf - 10, nkf))
+    script += [("reloc", 1, *q), ("loop", 2, *q, ["k%d" % j for j in conn], 0.005)]
+    path = os.path.join(tmpdir, "kfdb_script.bin")
+    K.dump_script(path, 0, script)
+    ncand = [0, 0]
+    qid = [10]
+
+    def call():
+        qid[0] += 2
+        c, _ = db.DetectRelocalizationCandidates(qid[0], *q)
+        ncand[0] = len(c)
+        c, _ = db.DetectLoopCandidates(qid[0] + 1, *q, conn, 0.005)
+        ncand[1] = len(c)
+    exe = os.path.join(ROOT, "tests", "cpp", "build", "kfdb_test")
+    for rep in range(2):
+        t = timed(call, 100, warm=3)
+        r = subprocess.run([exe, "--time", path, "20"], capture_output=True, text=True, check=True)
+        t_cpu = float(r.stdout.split("ms_per_pass=")[1].split()[0]) * 1e-3
+        jrow("kfdb", "query pairs/s", 1, t, f"repeat {rep}: reloc + loop query, {nkf} keyframes x {nw} "
+             f"words, candidates {ncand[0]} / {ncand[1]}; comparator: one-thread std::list inverted file",
+             comparator_ms=round(t_cpu * 1e3, 4), device_over_comparator=round(t / t_cpu, 3),
+             comparator_over_device=round(t_cpu / t, 3))
+    db.close()
+    gv.close()
+
+
 if __name__ == "__main__":
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         rows = {"single": row_single, "color": row_color, "stereo": row_stereo, "reloc": row_reloc, "fuse": row_fuse, "triangulation": row_triangulation, "track": row_track,
                 "distinctive": row_distinctive, "bow": lambda: row_bow(td),
-                "loop": row_loop}
+                "loop": row_loop, "kfdb": lambda: row_kfdb(td)}
         for name in (sys.argv[1:] or list(rows)):
             rows[name]()
