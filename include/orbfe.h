@@ -636,8 +636,10 @@ int orbfe_is_in_frustum(orbfe_matcher* m, int n, const float* xyz, const float* 
  * on ORBvoc.txt: header "k L scoring weighting", one line per node "parent isLeaf d0..d31
  * weight".  The tree is kept in HBM of `device`.  Blank lines are skipped. */
 orbfe_vocabulary* orbfe_vocabulary_load_text(const char* path, int device, int* status);
-/* The same from node arrays: node 0 is the root (its entries are ignored); parent[i] < i;
- * is_word flags the leaves that are words (word ids in node order); desc n_nodes x 32. */
+/* The same from node arrays: node 0 is the root (its entries are ignored); parent[i] < i
+ * (anything else returns ORBFE_ERR_ARG); is_word flags the nodes that are words (word ids in
+ * node order); desc n_nodes x 32.  A childless node that is no word sends its features to word
+ * 0 with the node's weight, as the reference's Node() default does. */
 orbfe_vocabulary* orbfe_vocabulary_create(int k, int L, int scoring, int weighting, int n_nodes,
                                           const int32_t* parent, const uint8_t* is_word,
                                           const uint8_t* desc, const double* weight, int device,
@@ -658,7 +660,9 @@ int orbfe_bow_transform(orbfe_vocabulary* v, const uint8_t* desc, int n, int lev
                         int32_t* node_off, int32_t* feat, int32_t* nn);
 /* Batched device form: frame f's descriptors at d_desc + f*cap*32 (d_n[f] rows, cap <= 4096);
  * outputs per frame at f*cap (node_off at f*(cap+1)), counts in d_nw[f] / d_nn[f].
- * Asynchronous on the vocabulary's stream (orbfe_vocabulary_set_stream). */
+ * Requires 0 <= d_n[f] <= cap for every frame: the kernels trust the count they read on the
+ * device, and a larger one reads and writes past the frame's slot.  cap > 4096 returns
+ * ORBFE_ERR_UNSUPPORTED.  Asynchronous on the vocabulary's stream (orbfe_vocabulary_set_stream). */
 int orbfe_bow_transform_batch_device(orbfe_vocabulary* v, int nframes, const uint8_t* d_desc,
                                      const int32_t* d_n, int cap, int levelsup,
                                      int32_t* d_word_ids, double* d_values, int32_t* d_nw,

@@ -113,6 +113,7 @@ __device__ __forceinline__ void bitonic_sort_u64(unsigned long long* k, int n_pa
 __global__ __launch_bounds__(kBowBlock) void bow_assemble_kernel(BowArgs a) {
     __shared__ unsigned long long keys[kBowMaxFeatures];
     __shared__ double vals[kBowMaxFeatures];
+    __shared__ double wts[kBowMaxFeatures];  // each feature's weight (0 = stopped), by feature
     __shared__ int pos[kBowMaxFeatures];
     __shared__ int tmp[kBowBlock / 64 + 1];
     __shared__ double s_norm;
@@ -125,10 +126,11 @@ __global__ __launch_bounds__(kBowBlock) void bow_assemble_kernel(BowArgs a) {
     const bool must = v.scoring != 5;                 // DotProductScoring does not normalise
     const bool tf = v.weighting == 0 || v.weighting == 1;  // addWeight vs addIfNotExist
     // ---- BowVector: sort (word, feature) of the kept features
-    for (int t = threadIdx.x; t < n_pad; t += kBowBlock)
-        keys[t] = (t < n && a.f_w[fo + t] > 0)
-                      ? ((unsigned long long)(unsigned)a.f_word[fo + t] << 32) | (unsigned)t
-                      : ~0ull;
+    for (int t = threadIdx.x; t < n_pad; t += kBowBlock) {
+        const double w = t < n ? a.f_w[fo + t] : 0.0;
+        wts[t] = w;
+        keys[t] = w > 0 ? ((unsigned long long)(unsigned)a.f_word[fo + t] << 32) | (unsigned)t : ~0ull;
+    }
     __syncthreads();
     bitonic_sort_u64(keys, n_pad);
     // run heads -> compact index by a block scan over runs of kBowBlock-strided chunks
@@ -151,10 +153,12 @@ __global__ __launch_bounds__(kBowBlock) void bow_assemble_kernel(BowArgs a) {
         const int t = c + threadIdx.x;
         if (t < n_pad && keys[t] != ~0ull && (t == 0 || (keys[t] >> 32) != (keys[t - 1] >> 32))) {
             const unsigned wd = (unsigned)(keys[t] >> 32);
-            const double w = a.f_w[fo + (unsigned)(keys[t] & 0xffffffffu)];
-            double s = w;
+            // each feature's own weight: word 0 is also where a childless node that is no word
+            // lands (Node() leaves word_id 0), with that node's weight
+            double s = wts[(unsigned)(keys[t] & 0xffffffffu)];
             if (tf)
-                for (int u = t + 1; u < n_pad && keys[u] != ~0ull && (unsigned)(keys[u] >> 32) == wd; ++u) s += w;
+                for (int u = t + 1; u < n_pad && keys[u] != ~0ull && (unsigned)(keys[u] >> 32) == wd; ++u)
+                    s += wts[(unsigned)(keys[u] & 0xffffffffu)];
             vals[pos[t]] = s;
             a.word_ids[fo + pos[t]] = (int)wd;
         }
@@ -187,9 +191,7 @@ __global__ __launch_bounds__(kBowBlock) void bow_assemble_kernel(BowArgs a) {
     __syncthreads();
     // ---- FeatureVector: sort (node, feature) of the kept features
     for (int t = threadIdx.x; t < n_pad; t += kBowBlock)
-        keys[t] = (t < n && a.f_w[fo + t] > 0)
-                      ? ((unsigned long long)(unsigned)a.f_node[fo + t] << 32) | (unsigned)t
-                      : ~0ull;
+        keys[t] = wts[t] > 0 ? ((unsigned long long)(unsigned)a.f_node[fo + t] << 32) | (unsigned)t : ~0ull;
     __syncthreads();
     bitonic_sort_u64(keys, n_pad);
     int* noff = a.node_off + (size_t)f * (a.cap + 1);

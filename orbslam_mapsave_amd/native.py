@@ -532,10 +532,34 @@ class Vocabulary:
         h = lib().orbfe_vocabulary_load_text(path.encode(), device, C.byref(st))
         if not h:
             raise OrbfeError("orbfe_vocabulary_load_text", st.value)
+        self._adopt(h)
+
+    def _adopt(self, h: int) -> None:
         self._h = C.c_void_p(h)
         info = np.zeros(6, np.int32)
         _check("orbfe_vocabulary_info", lib().orbfe_vocabulary_info(self._h, ptr(info)))
         self.k, self.L, self.scoring, self.weighting, self.nodes, self.words = map(int, info)
+
+    @classmethod
+    def from_arrays(cls, k: int, L: int, scoring: int, weighting: int, parent, is_word, desc,
+                    weight, device: int = 0) -> "Vocabulary":
+        """The vocabulary from node arrays in insertion order (orbfe_vocabulary_create): node 0
+        is the root, parent[i] < i, word ids are handed out to the flagged nodes in order."""
+        par = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        n = len(par)
+        word = np.ascontiguousarray(is_word, np.uint8).reshape(-1)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        w = np.ascontiguousarray(weight, np.float64).reshape(-1)
+        if not (len(word) == len(d) == len(w) == n):
+            raise ValueError("from_arrays: parent, is_word, desc and weight must describe the same nodes")
+        st = C.c_int(0)
+        h = lib().orbfe_vocabulary_create(k, L, scoring, weighting, n, ptr(par), ptr(word), ptr(d),
+                                          ptr(w), device, C.byref(st))
+        if not h:
+            raise OrbfeError("orbfe_vocabulary_create", st.value)
+        self = cls.__new__(cls)
+        self._adopt(h)
+        return self
 
     def close(self) -> None:
         if getattr(self, "_h", None):
