@@ -142,6 +142,16 @@ def _stream_arg(stream_handle: int | None):
     return C.c_void_p(HIP_STREAM_LEGACY if stream_handle == 0 else stream_handle)
 
 
+def _check_results(fn: str, st: int, results):
+    """_check for the calls that write valid results next to ORBFE_ERR_UNSUPPORTED (a predicted
+    level outside the pyramid skips that point only): the error carries them as ``.results``."""
+    if st != ORBFE_OK:
+        e = OrbfeError(fn, st)
+        e.results = results() if st == ORBFE_ERR_UNSUPPORTED else None
+        raise e
+    return results()
+
+
 def _check(fn: str, st: int) -> None:
     if st != ORBFE_OK:
         raise OrbfeError(fn, st)
@@ -842,10 +852,10 @@ class ORBmatcher:
         ids = None if mp_ids is None else np.ascontiguousarray(mp_ids, np.int32)
         nm = C.c_int32(0)
         fv, mv = F.view(), mps.view()
-        _check("orbfe_search_by_projection_local", lib().orbfe_search_by_projection_local(
-            self._h, C.c_float(self.mfNNratio), C.byref(fv), ptr(fmp), ptr(fobs), C.byref(mv),
-            ptr(ids), C.c_float(th), C.byref(nm)))
-        return fmp, fobs, nm.value
+        return _check_results(
+            "orbfe_search_by_projection_local", lib().orbfe_search_by_projection_local(
+                self._h, C.c_float(self.mfNNratio), C.byref(fv), ptr(fmp), ptr(fobs), C.byref(mv),
+                ptr(ids), C.c_float(th), C.byref(nm)), lambda: (fmp, fobs, nm.value))
 
     def SearchByProjectionLast(self, cur: Frame, tcw_cur, cam: Camera, last_keys, last_valid,
                                last_outlier, last_xyz, last_desc, last_nobs, tcw_last,
@@ -894,11 +904,11 @@ class ORBmatcher:
         ids = None if kf_ids is None else np.ascontiguousarray(kf_ids, np.int32)
         nm = C.c_int32(0)
         cv = cur.view()
-        _check("orbfe_search_by_projection_keyframe", lib().orbfe_search_by_projection_keyframe(
-            self._h, int(self.mbCheckOrientation), C.byref(cv), ptr(a[0]), C.byref(cam),
-            C.c_float(log_scale), ptr(fmp), len(a[1]), *(ptr(x) for x in a[1:]), ptr(ids),
-            C.c_float(th), int(ORBdist), C.byref(nm)))
-        return fmp, nm.value
+        return _check_results(
+            "orbfe_search_by_projection_keyframe", lib().orbfe_search_by_projection_keyframe(
+                self._h, int(self.mbCheckOrientation), C.byref(cv), ptr(a[0]), C.byref(cam),
+                C.c_float(log_scale), ptr(fmp), len(a[1]), *(ptr(x) for x in a[1:]), ptr(ids),
+                C.c_float(th), int(ORBdist), C.byref(nm)), lambda: (fmp, nm.value))
 
     FUSE_SE3, FUSE_SIM3 = 0, 1  # ORBFE_FUSE_*
 
@@ -990,12 +1000,13 @@ class ORBmatcher:
         t = np.ascontiguousarray(tcw, np.float32).reshape(12)
         counts = np.zeros(2, np.int32)
         vp = lambda p: C.c_void_p(p) if p else None  # noqa: E731
-        _check("orbfe_search_local_points_device", lib().orbfe_search_local_points_device(
-            self._h, C.byref(fv), ptr(t), C.byref(cam), C.c_float(log_scale),
-            C.c_float(cos_limit), n_mp, vp(d_xyz), vp(d_normal), vp(d_min), vp(d_max),
-            vp(d_mdesc), vp(d_nobs), vp(d_bad), vp(d_skip), vp(d_ids), C.c_float(nnratio),
-            C.c_float(th), vp(d_fmp), vp(d_fobs), vp(d_in_view), ptr(counts)))
-        return int(counts[0]), int(counts[1])
+        return _check_results(
+            "orbfe_search_local_points_device", lib().orbfe_search_local_points_device(
+                self._h, C.byref(fv), ptr(t), C.byref(cam), C.c_float(log_scale),
+                C.c_float(cos_limit), n_mp, vp(d_xyz), vp(d_normal), vp(d_min), vp(d_max),
+                vp(d_mdesc), vp(d_nobs), vp(d_bad), vp(d_skip), vp(d_ids), C.c_float(nnratio),
+                C.c_float(th), vp(d_fmp), vp(d_fobs), vp(d_in_view), ptr(counts)),
+            lambda: (int(counts[0]), int(counts[1])))
 
     def search_by_projection_local_device(self, n_kp: int, d_keys: int, d_desc: int,
                                           d_u_right: int | None, width: int, height: int,
@@ -1016,11 +1027,11 @@ class ORBmatcher:
         mv = MapPointView(n_mp, vp(d_in_view), vp(d_bad), vp(d_px), vp(d_py), vp(d_pxr),
                           vp(d_lvl), vp(d_vcos), vp(d_mdesc), vp(d_nobs))
         nm = C.c_int32(0)
-        _check("orbfe_search_by_projection_local_device",
-               lib().orbfe_search_by_projection_local_device(
-                   self._h, C.c_float(nnratio), C.byref(fv), vp(d_fmp), vp(d_fobs), C.byref(mv),
-                   vp(d_ids), C.c_float(th), C.byref(nm)))
-        return nm.value
+        return _check_results(
+            "orbfe_search_by_projection_local_device",
+            lib().orbfe_search_by_projection_local_device(
+                self._h, C.c_float(nnratio), C.byref(fv), vp(d_fmp), vp(d_fobs), C.byref(mv),
+                vp(d_ids), C.c_float(th), C.byref(nm)), lambda: nm.value)
 
     def last_rounds(self) -> int:
         return lib().orbfe_matcher_last_rounds(self._h)
@@ -1256,17 +1267,26 @@ class ORBmatcher:
                    ptr(sg), len(sf), vp(d_matches12), vp(d_nmatches), vp(d_status)))
 
     def is_in_frustum(self, xyz, normal, min_dist, max_dist, tcw, cam: Camera, bounds,
-                      log_scale: float, cos_limit: float = 0.5):
-        """Frame::isInFrustum + MapPoint::PredictScale over all map points (Frame.cc:387)."""
+                      log_scale: float, cos_limit: float = 0.5, out=None):
+        """Frame::isInFrustum + MapPoint::PredictScale over all map points (Frame.cc:387).
+        out: the six output arrays (in_view u8, proj_x, proj_y, proj_xr f32, pred_level i32,
+        view_cos f32) to write into; in_view is written for every point, the other five only
+        for a point in view -- a rejected point keeps what they held, as mTrackProj* do."""
         xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
         n = len(xyz)
         normal = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
         mn = np.ascontiguousarray(min_dist, np.float32)
         mx = np.ascontiguousarray(max_dist, np.float32)
         t = np.ascontiguousarray(tcw, np.float32).reshape(12)
-        inv = np.zeros(n, np.uint8)
-        px, py, pxr, vc = (np.zeros(n, np.float32) for _ in range(4))
-        pl = np.zeros(n, np.int32)
+        if out is not None:
+            inv, px, py, pxr, pl, vc = out
+            for o, dt in zip(out, (np.uint8, np.float32, np.float32, np.float32, np.int32,
+                                   np.float32)):
+                assert o.dtype == dt and o.shape == (n,) and o.flags["C_CONTIGUOUS"]
+        else:
+            inv = np.zeros(n, np.uint8)
+            px, py, pxr, vc = (np.zeros(n, np.float32) for _ in range(4))
+            pl = np.zeros(n, np.int32)
         _check("orbfe_is_in_frustum", lib().orbfe_is_in_frustum(
             self._h, n, ptr(xyz), ptr(normal), ptr(mn), ptr(mx), ptr(t), C.byref(cam),
             *(C.c_float(b) for b in bounds), C.c_float(log_scale), C.c_float(cos_limit),

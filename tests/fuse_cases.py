@@ -78,10 +78,25 @@ def camera_center(T):
                   float(T[2, i]) * float(T[2, 3]))) for i in range(3)]
 
 
-def project(c: dict, i: int, ow=None):
+# Single-decision mutants of the gates (tests/projection_cases.py builds the inputs that show
+# them): the first four change project(), the others search_point().
+GATE_MUTANTS = ("bounds_inclusive_upper", "vcos_float_quotient", "chi2_float_literal",
+                "chi2_mono_uses_78", "stereo_kr_gt0", "sigma_of_predicted_level", "window_plus1",
+                "sim3_has_chi2")
+# `z <= 0` is no mutant: z = +-0 makes invz infinite and u, v NaN or infinite, which
+# KeyFrame::IsInImage refuses (a NaN fails `x >= mnMinX`), so the point is dropped either way.
+# chi2_float_literal shows at 7.8 only ((float)7.8 > 7.8 > its predecessor); (float)5.99 lies
+# below 5.99 and no float lies between them.  The chi-square mutants show in the SE3 mode,
+# sim3_has_chi2 in the Sim3 mode.
+GATE_EQUIVALENT = ("depth_le0",)
+SE3_ONLY = ("chi2_float_literal", "chi2_mono_uses_78", "stereo_kr_gt0", "sigma_of_predicted_level")
+
+
+def project(c: dict, i: int, ow=None, mutant=None):
     """The projection block of both overloads for point i -> dict(pc, u, v, ur, dist, dot,
     reject) with reject in (None, "depth", "image", "distance", "angle") and, when not rejected,
-    lvl (MapPoint::PredictScale, unclamped)."""
+    lvl (MapPoint::PredictScale, unclamped; None where log(ratio) / logScaleFactor is not
+    finite and its conversion to int undefined)."""
     kf, cam = c["kf"], c["cam"]
     T = c["tcw"].astype(F32)
     if ow is None:
@@ -89,7 +104,7 @@ def project(c: dict, i: int, ow=None):
     P = c["xyz"][i]
     pc = [((T[r, 0] * P[0] + T[r, 1] * P[1]) + T[r, 2] * P[2]) + T[r, 3] for r in range(3)]
     out = dict(pc=pc, reject=None)
-    if pc[2] < F32(0.0):
+    if (pc[2] <= F32(0.0)) if mutant == "depth_le0" else (pc[2] < F32(0.0)):
         out["reject"] = "depth"
         return out
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
@@ -99,7 +114,13 @@ def project(c: dict, i: int, ow=None):
         v = F32(cam.fy) * y + F32(cam.cy)
         ur = u - F32(cam.bf) * invz
     out.update(u=u, v=v, ur=ur)
-    if not (u >= F32(kf.min_x) and u < F32(kf.max_x) and v >= F32(kf.min_y) and v < F32(kf.max_y)):
+    if mutant == "bounds_inclusive_upper":
+        inside = u >= F32(kf.min_x) and u <= F32(kf.max_x) and v >= F32(kf.min_y) and \
+            v <= F32(kf.max_y)
+    else:                                           # KeyFrame::IsInImage: a NaN is outside
+        inside = u >= F32(kf.min_x) and u < F32(kf.max_x) and v >= F32(kf.min_y) and \
+            v < F32(kf.max_y)
+    if not inside:
         out["reject"] = "image"
         return out
     po = [P[j] - ow[j] for j in range(3)]
@@ -112,24 +133,35 @@ def project(c: dict, i: int, ow=None):
     nv = c["normal"][i]
     dot = float(po[0]) * float(nv[0]) + float(po[1]) * float(nv[1]) + float(po[2]) * float(nv[2])
     out["dot"] = dot
-    if dot < 0.5 * float(d3):
+    if mutant == "vcos_float_quotient":             # isInFrustum's form of the test
+        with np.errstate(all="ignore"):
+            steep = F32(np.float64(dot) / np.float64(d3)) < F32(0.5)
+    else:
+        steep = dot < 0.5 * float(d3)
+    if steep:
         out["reject"] = "angle"
         return out
-    ratio = c["max_dist"][i] / d3
-    out["lvl"] = int(math.ceil(F32(math.log(float(ratio))) / F32(c["log_scale"])))
+    with np.errstate(all="ignore"):
+        ratio = c["max_dist"][i] / d3
+        lg = math.log(float(ratio)) if 0 < ratio < np.inf else \
+            (np.inf if ratio > 0 else -np.inf if ratio == 0 else np.nan)
+        q = F32(lg) / F32(c["log_scale"])
+    out["lvl"] = int(math.ceil(float(q))) if np.isfinite(q) else None
     return out
 
 
-def search_point(c: dict, i: int, th: float, mode: int, ow=None, stats=None):
+def search_point(c: dict, i: int, th: float, mode: int, ow=None, stats=None, mutant=None):
     """(best_idx, best_dist, unsupported) of point i, the skip byte not looked at."""
     kf = c["kf"]
-    p = project(c, i, ow)
+    p = project(c, i, ow, mutant)
     if p["reject"] is not None:
         if stats is not None:
             stats[p["reject"]] = stats.get(p["reject"], 0) + 1
         return -1, 256, False
     lvl = p["lvl"]
-    if lvl < 0 or lvl >= len(kf.scale_factors):
+    if lvl is None or lvl < 0 or lvl >= len(kf.scale_factors):
+        if stats is not None:
+            stats["level_outside"] = stats.get("level_outside", 0) + 1
         return -1, 256, True
     u, v, ur = p["u"], p["v"], p["ur"]
     r = F32(th) * kf.scale_factors[lvl]
@@ -137,19 +169,30 @@ def search_point(c: dict, i: int, th: float, mode: int, ow=None, stats=None):
     best, bi = 256, -1
     for idx in oracle.features_in_area(kf, float(u), float(v), float(r)):
         octave = int(k["octave"][idx])
-        if octave < lvl - 1 or octave > lvl:
+        if octave < lvl - 1 or octave > (lvl + 1 if mutant == "window_plus1" else lvl):
+            if stats is not None:
+                stats["level_window"] = stats.get("level_window", 0) + 1
             continue
-        if mode == SE3:
+        if mode == SE3 or mutant == "sim3_has_chi2":
             ex, ey = u - k["x"][idx], v - k["y"][idx]
-            inv = c["inv_sigma2"][octave]
+            inv = c["inv_sigma2"][lvl if mutant == "sigma_of_predicted_level" else octave]
             kr = kf.u_right[idx] if kf.u_right is not None else F32(-1)
-            if kr >= 0:
+            # the float product against the double literals 7.8 / 5.99 (928, 939)
+            if (kr > 0) if mutant == "stereo_kr_gt0" else (kr >= 0):
                 er = ur - kr
                 e2 = ex * ex + ey * ey + er * er
-                drop = float(e2 * inv) > 7.8
+                drop = e2 * inv > F32(7.8) if mutant == "chi2_float_literal" else \
+                    float(e2 * inv) > 7.8
+                if stats is not None:
+                    stats["chi2_stereo"] = stats.get("chi2_stereo", 0) + 1
             else:
                 e2 = ex * ex + ey * ey
-                drop = float(e2 * inv) > 5.99
+                if mutant == "chi2_float_literal":
+                    drop = e2 * inv > F32(5.99)
+                else:
+                    drop = float(e2 * inv) > (7.8 if mutant == "chi2_mono_uses_78" else 5.99)
+                if stats is not None:
+                    stats["chi2_mono"] = stats.get("chi2_mono", 0) + 1
             if drop:
                 if stats is not None:
                     stats["chi2"] = stats.get("chi2", 0) + 1
@@ -160,7 +203,7 @@ def search_point(c: dict, i: int, th: float, mode: int, ow=None, stats=None):
     return (bi if best <= TH_LOW else -1), best, False
 
 
-def restated(c: dict, th: float, mode: int, use_skip: bool = True, stats=None):
+def restated(c: dict, th: float, mode: int, use_skip: bool = True, stats=None, mutant=None):
     """-> (best_idx, best_dist, n_found, unsupported) for every point of the case."""
     n = len(c["xyz"])
     ow = camera_center(c["tcw"].astype(F32))
@@ -172,7 +215,7 @@ def restated(c: dict, th: float, mode: int, use_skip: bool = True, stats=None):
             if stats is not None:
                 stats["skip"] = stats.get("skip", 0) + 1
             continue
-        bi[i], bd[i], u = search_point(c, i, th, mode, ow, stats)
+        bi[i], bd[i], u = search_point(c, i, th, mode, ow, stats, mutant)
         bad |= u
     return bi, bd, int((bi >= 0).sum()), bad
 

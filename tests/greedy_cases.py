@@ -41,6 +41,23 @@ SFI_MUTANTS = ("steal_lt", "stolen_not_in_hist", "th_lt", "ratio_le", "round_hal
 LOCAL_MUTANTS = ("ratio_any_level", "ratio_ge", "th_lt", "stereo_ge", "order_by_index")
 LAST_MUTANTS = ("overwritten_not_cleared", "overwritten_not_counted", "th_lt", "stereo_ge",
                 "round_half_even", "maxima_ge", "tenth_double", "order_by_index")
+# The mutants of the projection gates in front of the greedy part (tests/projection_cases.py
+# builds the inputs that show them).  *_EQUIVALENT: decisions written differently that no input
+# separates, asserted as equivalences:
+#   radius_ge              no float equals the double 0.998, so `>=` and `>` agree on every float
+#   th_always_multiplied   r * 1.0f == r: `if(bFactor)` only saves the product
+#   invz_float, stereo_ur_uses_float_invz
+#                          (float)(1.0 / (double)z) == 1.0f / z for every float z (a quotient
+#                          rounded to 53 bits and then to 24 is the quotient rounded to 24)
+LOCAL_GATE_MUTANTS = ("radius_float_0998", "level_window_plus1", "stereo_ge")
+LOCAL_GATE_EQUIVALENT = ("radius_ge", "th_always_multiplied")
+#   depth_z_lt0            z = -0.0f passes `z < 0` and fails `invzc < 0`; but then u and v are
+#                          NaN or infinite: the point leaves at the image test or searches
+#                          around a NaN centre, which finds nothing (DESIGN H21).  The branch
+#                          counter `behind` tells the two apart, the outputs do not.
+LAST_GATE_MUTANTS = ("bounds_strict", "forward_ge", "backward_ge", "forward_ignores_mono",
+                     "window_forward_closed")
+LAST_GATE_EQUIVALENT = ("depth_z_lt0", "invz_float", "stereo_ur_uses_float_invz")
 
 
 def _bump(st, key, n=1):
@@ -76,6 +93,9 @@ class Grid:
 
     def area(self, x, y, r, lo, hi, by_index=False):
         x, y, r = F32(x), F32(y), F32(r)
+        if not (np.isfinite(x) and np.isfinite(y) and np.isfinite(r)):
+            # (int)floor(NaN) is undefined in the reference; pinned (DESIGN H21): no candidates
+            return np.zeros(0, np.int64)
         cx0 = max(0, math.floor((x - self.minx - r) * self.gw))
         if cx0 >= GRID_COLS:
             return np.zeros(0, np.int64)
@@ -226,9 +246,26 @@ def restated_sfi(f1: Frame, f2: Frame, prev, window, nnratio, check_ori=True, st
 
 # ---- SearchByProjection, local map (45-137) -------------------------------------------------------
 
+def radius_by_viewing_cos(view_cos, th, mutant=None):
+    """RadiusByViewingCos (131-137) and `if(bFactor) r*=th` (49, 65-66): the float viewCos and th
+    are compared with the double literals 0.998 and 1.0."""
+    if mutant == "radius_float_0998":            # (float)0.998 > 0.998: the boundary float
+        near = F32(view_cos) > F32(0.998)
+    elif mutant == "radius_ge":
+        near = float(view_cos) >= 0.998
+    else:
+        near = float(view_cos) > 0.998
+    r = F32(2.5) if near else F32(4.0)
+    if float(th) != 1.0 or mutant == "th_always_multiplied":
+        r = r * F32(th)
+    return r
+
+
 def restated_local(f: Frame, mps: MapPoints, th, nnratio, frame_mp=None, frame_mp_obs=None,
-                   mp_ids=None, stats=None, mutant=None):
-    """-> (frame_mp, frame_mp_obs, nmatches)."""
+                   mp_ids=None, stats=None, mutant=None, info=None):
+    """-> (frame_mp, frame_mp_obs, nmatches).  A predicted level outside mvScaleFactors (the
+    reference reads past the vector, ORBmatcher.cc:69) skips the point and sets
+    info["unsupported"]."""
     st = stats
     g = Grid(f)
     fmp = np.full(f.n, -1, np.int32) if frame_mp is None else np.array(frame_mp, np.int32)
@@ -241,11 +278,17 @@ def restated_local(f: Frame, mps: MapPoints, th, nnratio, frame_mp=None, frame_m
         if not mps.track_in_view[i] or mps.is_bad[i]:
             continue
         pl = int(mps.pred_level[i])
-        r = F32(2.5) if float(mps.view_cos[i]) > 0.998 else F32(4.0)    # 131-137
-        if float(th) != 1.0:
-            r = r * th
+        if pl < 0 or pl >= len(f.scale_factors):
+            _bump(st, "level_outside")
+            if info is not None:
+                info["unsupported"] = True
+            continue
+        r = radius_by_viewing_cos(mps.view_cos[i], th, mutant)          # 131-137
+        _bump(st, "radius_2.5" if r == F32(2.5) * (th if float(th) != 1.0 else F32(1.0))
+              else "radius_4.0")
         rs = r * f.scale_factors[pl]
-        c = g.area(mps.proj_x[i], mps.proj_y[i], rs, pl - 1, pl, mutant == "order_by_index")
+        hi = pl + 1 if mutant == "level_window_plus1" else pl
+        c = g.area(mps.proj_x[i], mps.proj_y[i], rs, pl - 1, hi, mutant == "order_by_index")
         if len(c) == 0:
             continue
         best = second = 256
@@ -305,26 +348,40 @@ def rigid(T, P):
     return [((T[r, 0] * P[0] + T[r, 1] * P[1]) + T[r, 2] * P[2]) + T[r, 3] for r in range(3)]
 
 
-def last_motion(c, mono):
+def last_motion(c, mono, mutant=None):
     """(bForward, bBackward) (1341-1352)."""
     Tc = np.asarray(c["tcw_cur"], F32).reshape(3, 4)
     Tl = np.asarray(c["tcw_last"], F32).reshape(3, 4)
     tlc = rigid(Tl, camera_center(Tc))
     b = F32(c["cam"].b)
-    return bool(tlc[2] > b and not mono), bool(-tlc[2] > b and not mono)
+    fwd = tlc[2] >= b if mutant == "forward_ge" else tlc[2] > b
+    bwd = -tlc[2] >= b if mutant == "backward_ge" else -tlc[2] > b
+    return (bool(fwd and (not mono or mutant == "forward_ignores_mono")), bool(bwd and not mono))
 
 
-def last_project(c, i):
-    """(invz, u, v, ur, radius-less) of last-frame point i in the current frame (1363-1374, 1412)."""
+def last_project(c, i, mutant=None):
+    """(invz, u, v, ur) of last-frame point i in the current frame."""
+    return _last_project(c, i, mutant)[:4]
+
+
+def _last_project(c, i, mutant=None):
+    """(invz, u, v, ur, z) of last-frame point i in the current frame (1363-1374, 1412):
+    invzc = 1.0 / z is a double quotient rounded to float, -inf for z = -0.0f."""
     T = np.asarray(c["tcw_cur"], F32).reshape(3, 4)
     cam = c["cam"]
     pc = rigid(T, np.asarray(c["last_xyz"], F32)[i])
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        invz = F32(1.0 / float(pc[2])) if pc[2] != 0 else F32(np.inf)
+    with np.errstate(all="ignore"):
+        if mutant == "invz_float":
+            invz = F32(1.0) / pc[2]
+        else:
+            invz = F32(np.float64(1.0) / np.float64(pc[2]))
         u = F32(cam.fx) * pc[0] * invz + F32(cam.cx)
         v = F32(cam.fy) * pc[1] * invz + F32(cam.cy)
-        ur = u - F32(cam.bf) * invz
-    return invz, u, v, ur
+        if mutant == "stereo_ur_uses_float_invz":
+            ur = u - F32(cam.bf) * (F32(1.0) / pc[2])
+        else:
+            ur = u - F32(cam.bf) * invz
+    return invz, u, v, ur, pc[2]
 
 
 def restated_last(c, th, mono, check_ori=True, frame_mp=None, frame_mp_obs=None, stats=None,
@@ -335,7 +392,7 @@ def restated_last(c, th, mono, check_ori=True, frame_mp=None, frame_mp_obs=None,
     g = Grid(cur)
     fmp = np.full(cur.n, -1, np.int32) if frame_mp is None else np.array(frame_mp, np.int32)
     fobs = np.zeros(cur.n, np.int32) if frame_mp_obs is None else np.array(frame_mp_obs, np.int32)
-    fwd, bwd = last_motion(c, mono)
+    fwd, bwd = last_motion(c, mono, mutant)
     lk = c["last_keys"]
     ids = c.get("last_ids")
     holder = {}                                   # slot -> acceptance that holds it
@@ -344,14 +401,25 @@ def restated_last(c, th, mono, check_ori=True, frame_mp=None, frame_mp_obs=None,
     for i in range(len(lk)):
         if not c["last_valid"][i] or c["last_outlier"][i]:
             continue
-        invz, u, v, ur = last_project(c, i)
-        if invz < 0:
+        invz, u, v, ur, z = _last_project(c, i, mutant)
+        if (z < 0) if mutant == "depth_z_lt0" else (invz < 0):          # 1370: -0.0f is behind
+            _bump(st, "behind")
             continue
-        if u < F32(cur.min_x) or u > F32(cur.max_x) or v < F32(cur.min_y) or v > F32(cur.max_y):
+        if mutant == "bounds_strict":
+            out = (u <= F32(cur.min_x) or u >= F32(cur.max_x) or v <= F32(cur.min_y) or
+                   v >= F32(cur.max_y))
+        else:                                                           # 1376-1379: NaN passes
+            out = (u < F32(cur.min_x) or u > F32(cur.max_x) or v < F32(cur.min_y) or
+                   v > F32(cur.max_y))
+        if out:
+            _bump(st, "outside")
             continue
+        _bump(st, "window_forward" if fwd else "window_backward" if bwd else "window_both")
         o = int(lk["octave"][i])
         radius = F32(th) * cur.scale_factors[o]
-        lo, hi = (o, -1) if fwd else (0, o) if bwd else (o - 1, o + 1)
+        lo, hi = (o, -1) if fwd else (0, o) if bwd else (o - 1, o + 1)  # 1388-1393
+        if fwd and mutant == "window_forward_closed":
+            hi = o + 1
         cand = g.area(u, v, radius, lo, hi, mutant == "order_by_index")
         if len(cand) == 0:
             continue
@@ -785,7 +853,7 @@ def last_ties(seed, motion="mono", th=None, bins=None, b=None):
         for j, p in enumerate(b.kp):
             if p["ur"] is not None:
                 qi, kind = p["ur"]
-                _, _, _, uq = last_project(c, qi)
+                uq = last_project(c, qi)[3]
                 ur[j] = _edge_value(uq, F32(th) * SCALE[b.q[qi]["lvl"]], kind)
             elif j % 3 == 0:
                 ur[j] = F32(p["x"] - 8.0)

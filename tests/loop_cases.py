@@ -79,7 +79,7 @@ def _sbp_point(c, i, ow, th, variant):
         return dict(reject=p["reject"])
     kf = c["kf"]
     lvl = p["lvl"]
-    if lvl < 0 or lvl >= len(kf.scale_factors):
+    if lvl is None or lvl < 0 or lvl >= len(kf.scale_factors):
         return dict(reject="unsupported")
     r = F32(int(th)) * kf.scale_factors[lvl]                       # 363: th is an int
     idx = oracle.features_in_area(kf, float(p["u"]), float(p["v"]), float(r))   # 365

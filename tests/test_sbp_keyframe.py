@@ -18,7 +18,22 @@ import scenarios as S
 F32 = np.float32
 
 
-def restated(c, th, orb_dist, check_ori=True):
+# Single-decision mutants of the projection gates (tests/projection_cases.py builds the inputs
+# that show them).  invz_float is no mutant: (float)(1.0 / (double)z) == 1.0f / z for every float
+# z, asserted as an equivalence.
+GATE_MUTANTS = ("has_depth_test", "window_minus_only", "found_not_skipped", "bounds_strict")
+GATE_EQUIVALENT = ("invz_float",)
+
+
+def _bump(st, key):
+    if st is not None:
+        st[key] = st.get(key, 0) + 1
+
+
+def restated(c, th, orb_dist, check_ori=True, stats=None, mutant=None, info=None):
+    """-> (frame_mp, nmatches).  A predicted level outside mvScaleFactors (the reference reads
+    past the vector, ORBmatcher.cc:1529) skips the point and sets info["unsupported"]."""
+    st = stats
     cur = c["cur"]
     k = cur.keys
     fmp = c["frame_mp"].copy()
@@ -32,22 +47,48 @@ def restated(c, th, orb_dist, check_ori=True):
     hist = [[] for _ in range(30)]
     nm = 0
     for i in range(len(c["kf_valid"])):
-        if not c["kf_valid"][i] or c["kf_bad"][i] or c["found"][i]:
+        if not c["kf_valid"][i] or c["kf_bad"][i] or \
+                (c["found"][i] and mutant != "found_not_skipped"):
+            _bump(st, "not_searched")
             continue
         P = c["kf_xyz"][i]
         pc = [((T[r, 0] * P[0] + T[r, 1] * P[1]) + T[r, 2] * P[2]) + T[r, 3] for r in range(3)]
-        invz = F32(1.0 / float(pc[2]))
-        u = F32(cam.fx) * pc[0] * invz + F32(cam.cx)
-        v = F32(cam.fy) * pc[1] * invz + F32(cam.cy)
-        if u < 0 or u > W or v < 0 or v > H:
+        with np.errstate(all="ignore"):
+            if mutant == "invz_float":
+                invz = F32(1.0) / pc[2]
+            else:                                   # 1505: a double quotient; no depth test
+                invz = F32(np.float64(1.0) / np.float64(pc[2]))
+            u = F32(cam.fx) * pc[0] * invz + F32(cam.cx)
+            v = F32(cam.fy) * pc[1] * invz + F32(cam.cy)
+        if mutant == "has_depth_test" and invz < 0:
+            continue
+        if pc[2] < 0:
+            _bump(st, "behind_projected")
+        if mutant == "bounds_strict":
+            out = u <= 0 or u >= W or v <= 0 or v >= H
+        else:                                       # 1510-1513: a NaN passes
+            out = u < 0 or u > W or v < 0 or v > H
+        if out:
+            _bump(st, "outside")
             continue
         po = [P[j] - ow[j] for j in range(3)]
         d3 = F32(math.sqrt(sum(float(x) * float(x) for x in po)))
         if d3 < F32(0.8) * c["kf_min"][i] or d3 > F32(1.2) * c["kf_max"][i]:
+            _bump(st, "distance")
             continue
-        ratio = c["kf_max"][i] / d3
-        lvl = int(math.ceil(F32(math.log(float(ratio))) / F32(c["log_scale"])))
-        assert 0 <= lvl < 8
+        with np.errstate(all="ignore"):
+            ratio = c["kf_max"][i] / d3
+            q = F32(math.log(float(ratio)) if 0 < ratio < np.inf else
+                    (np.inf if ratio > 0 else -np.inf if ratio == 0 else np.nan)) / \
+                F32(c["log_scale"])
+        lvl = int(math.ceil(float(q))) if np.isfinite(q) else -1
+        if not 0 <= lvl < len(scale):
+            _bump(st, "level_outside")
+            if info is not None:
+                info["unsupported"] = True
+            continue
+        _bump(st, "searched")
+        hi = lvl if mutant == "window_minus_only" else lvl + 1
         r = F32(th) * scale[lvl]
         # GetFeaturesInArea(u, v, r, lvl-1, lvl+1) (Frame.cc:445-498): candidates come in grid
         # order -- cell column ix, then row iy, then insertion (keypoint index) order
@@ -57,7 +98,7 @@ def restated(c, th, orb_dist, check_ori=True):
         for i2 in range(cur.n):
             if not (0 <= gx[i2] < 64 and 0 <= gy[i2] < 48):
                 continue
-            if k["octave"][i2] < lvl - 1 or k["octave"][i2] > lvl + 1:
+            if k["octave"][i2] < lvl - 1 or k["octave"][i2] > hi:
                 continue
             if not (abs(k["x"][i2] - u) < r and abs(k["y"][i2] - v) < r):
                 continue
