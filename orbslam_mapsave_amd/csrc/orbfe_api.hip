@@ -126,6 +126,13 @@ struct Profiler {
         hipExtLaunchKernelGGL(kernel, grid, block, shmem, stream, e0_, e1_, 0, __VA_ARGS__); \
     } while (0)
 
+// ORBFE_LAUNCH of kernel<true> (x86 arithmetic) or kernel<false>.
+#define ORBFE_LAUNCH_X86(x86, prof, stage, kernel, ...)                                    \
+    do {                                                                                   \
+        if (x86) ORBFE_LAUNCH(prof, stage, kernel<true>, __VA_ARGS__);                     \
+        else ORBFE_LAUNCH(prof, stage, kernel<false>, __VA_ARGS__);                        \
+    } while (0)
+
 }  // namespace orbfe
 
 using namespace orbfe;
@@ -200,57 +207,63 @@ struct orbfe_extractor {
     // two forms do not recapture.
     hipGraphExec_t g1[2] = {nullptr, nullptr};
     const void* g1_key[2][11] = {};  // the buffers, plan and staging mode each graph was captured with
-    // K4 fused into K5 per keypoint window (default), or its own pass over every level with
-    // K5 reading the blurred levels (ORBFE_PREBLUR=1: describe 0.30 -> 0.20 ms per 256 frames,
-    // but the pass costs 0.19 ms; profiles/r02/experiments/preblur.json)
-    bool fused_blur = std::getenv("ORBFE_PREBLUR") == nullptr;
-    // ORBFE_PREBLUR with ORBFE_PRE_MASK=<hex>: the describe reads blurred windows only for the
-    // levels in the mask and blurs the others per keypoint (experiments)
-    uint32_t pre_mask_env = std::getenv("ORBFE_PRE_MASK") ? (uint32_t)std::strtoul(std::getenv("ORBFE_PRE_MASK"), nullptr, 16) : 0xffffffffu;
-    // the pyramid in one launch (pyramid_kernel); ORBFE_PYR=0: per-level resize launches + the
-    // one-workgroup tail
-    bool use_pyr = !(std::getenv("ORBFE_PYR") && std::strcmp(std::getenv("ORBFE_PYR"), "0") == 0);
-    // ORBFE_PYR=2: the band kernel even where its plan recomputes many seam rows (tests, A/B)
-    bool force_pyr = std::getenv("ORBFE_PYR") && std::strcmp(std::getenv("ORBFE_PYR"), "2") == 0;
-    // ORBFE_ZERO_COPY=0: the single-frame host call copies its frame in and its outputs out
-    // with DMA copies instead of kernels reading / writing the pinned buffers
-    bool zero_copy = !(std::getenv("ORBFE_ZERO_COPY") && std::strcmp(std::getenv("ORBFE_ZERO_COPY"), "0") == 0);
+    // The environment's switches, read once, when the handle is created.
+    struct Switches {
+        // K4 fused into K5 per keypoint window (default), or its own pass over every level with
+        // K5 reading the blurred levels (ORBFE_PREBLUR=1: describe 0.30 -> 0.20 ms per 256 frames,
+        // but the pass costs 0.19 ms; profiles/r02/experiments/preblur.json)
+        bool fused_blur = !env_is("ORBFE_PREBLUR");
+        // ORBFE_PREBLUR with ORBFE_PRE_MASK=<hex>: the describe reads blurred windows only for the
+        // levels in the mask and blurs the others per keypoint (experiments)
+        uint32_t pre_mask = (uint32_t)env_int("ORBFE_PRE_MASK", 0xffffffffl, 16);
+        // the pyramid in one launch (pyramid_kernel); ORBFE_PYR=0: per-level resize launches + the
+        // one-workgroup tail
+        bool use_pyr = env_on("ORBFE_PYR");
+        // ORBFE_PYR=2: the band kernel even where its plan recomputes many seam rows (tests, A/B)
+        bool force_pyr = env_is("ORBFE_PYR", "2");
+        // ORBFE_PYR_LDS_KB: LDS cap of a band plan's workgroup (plan_pyramid)
+        int pyr_lds_kb = (int)env_int("ORBFE_PYR_LDS_KB", kPyrLdsCapKB);
+        // ORBFE_ZERO_COPY=0: the single-frame host call copies its frame in and its outputs out
+        // with DMA copies instead of kernels reading / writing the pinned buffers
+        bool zero_copy = env_on("ORBFE_ZERO_COPY");
+        // ORBFE_PYR_SMALL_BELOW (A/B): batches below it take the small-batch band plans (thin bands)
+        int pyr_small_below = (int)env_int("ORBFE_PYR_SMALL_BELOW", kTailMinFrames);
+        // Batches of >= pyr_small_below frames take the per-level kernels (resize2 pairs + the
+        // one-workgroup tail) even where the band plan is the faster path alone: under the bench's
+        // two sub-batch streams the band kernel's 1024-thread, 80 KB workgroups find few CUs free
+        // beside the other stream's FAST / describe waves (a 256-frame launch stretched to 0.70 ms
+        // against 0.154 alone), the per-level kernels' 256-thread workgroups co-reside: c3 365.4 K
+        // -> 368.7 K frames/s (profiles/r05/pyramid_overlap/).  ORBFE_PYR_BATCH=band restores it.
+        bool pyr_batch_band = env_is("ORBFE_PYR_BATCH", "band");
+        // ORBFE_RS2=0: one resize launch per level where resize2_kernel would take two (A/B)
+        bool use_rs2 = env_on("ORBFE_RS2");
+        // ORBFE_RESIZE_TABLE=0: resize_kernel's horizontal pass by byte gathers (A/B)
+        bool table_off = env_is("ORBFE_RESIZE_TABLE", "0");
+        // ORBFE_DESC_MFMA=0: describe blurs its raw windows on the VALU instead of the matrix cores
+        bool desc_mfma = env_on("ORBFE_DESC_MFMA");
+        // ORBFE_DESC_STRIDE=0: describe waves take consecutive slots in batches too (A/B)
+        bool desc_stride = env_on("ORBFE_DESC_STRIDE");
+        // ORBFE_DESC_ORDER=0: strided describe waves take the oct-tree output order (A/B); 2: the
+        // band order at every frame size
+        bool desc_order = env_on("ORBFE_DESC_ORDER");
+        bool desc_order_all = env_is("ORBFE_DESC_ORDER", "2");
+        // ORBFE_OCT_SMALL=0: small batches keep the 256-thread oct-tree (A/B)
+        bool oct_small = env_on("ORBFE_OCT_SMALL");
+        // ORBFE_DESC_G16=1 (opt-in): 16 keypoints per describe wave (launch_describe)
+        int desc_g16 = (int)env_int("ORBFE_DESC_G16", 0);
+        bool no_graph = env_is("ORBFE_NO_GRAPH");  // the single-frame call keeps to plain launches
+    } sw;
     // run(): the pyramid kernel reads level 0 from l0_stage and writes it to the slab level 0
     LevelPtr l0_stage{};
     bool l0_from_stage = false;
-    // ORBFE_PYR_SMALL_BELOW (A/B): batches below it take the small-batch band plans (thin bands)
-    int pyr_small_below = std::getenv("ORBFE_PYR_SMALL_BELOW") ? std::atoi(std::getenv("ORBFE_PYR_SMALL_BELOW")) : kTailMinFrames;
-    // Batches of >= pyr_small_below frames take the per-level kernels (resize2 pairs + the
-    // one-workgroup tail) even where the band plan is the faster path alone: under the bench's
-    // two sub-batch streams the band kernel's 1024-thread, 80 KB workgroups find few CUs free
-    // beside the other stream's FAST / describe waves (a 256-frame launch stretched to 0.70 ms
-    // against 0.154 alone), the per-level kernels' 256-thread workgroups co-reside: c3 365.4 K
-    // -> 368.7 K frames/s (profiles/r05/pyramid_overlap/).  ORBFE_PYR_BATCH=band restores it.
-    bool pyr_batch_band = std::getenv("ORBFE_PYR_BATCH") && std::strcmp(std::getenv("ORBFE_PYR_BATCH"), "band") == 0;
     bool band_path(int n) const {  // run() makes the pyramid with pyramid_kernel for n frames
-        const int which = n >= pyr_small_below ? 0 : 1;
-        if (which == 0 && !pyr_batch_band && !force_pyr) return false;
-        return plan.pyr_ok && (plan.pyr_use[which] || force_pyr) && use_pyr && plan.geo.nlevels >= 2;
+        const int which = n >= sw.pyr_small_below ? 0 : 1;
+        if (which == 0 && !sw.pyr_batch_band && !sw.force_pyr) return false;
+        return plan.pyr.ok && (plan.pyr.use[which] || sw.force_pyr) && sw.use_pyr && plan.geo.nlevels >= 2;
     }
-    bool pyr_path(int n) const { return band_path(n); }  // one launch
-    // ORBFE_RS2=0: one resize launch per level where resize2_kernel would take two (A/B)
-    bool use_rs2 = !(std::getenv("ORBFE_RS2") && std::strcmp(std::getenv("ORBFE_RS2"), "0") == 0);
-    // ORBFE_RESIZE_TABLE=0: resize_kernel's horizontal pass by byte gathers (A/B)
-    bool table_off = std::getenv("ORBFE_RESIZE_TABLE") && std::strcmp(std::getenv("ORBFE_RESIZE_TABLE"), "0") == 0;
-    // ORBFE_DESC_MFMA=0: describe blurs its raw windows on the VALU instead of the matrix cores
-    bool desc_mfma = !(std::getenv("ORBFE_DESC_MFMA") && std::strcmp(std::getenv("ORBFE_DESC_MFMA"), "0") == 0);
-    // ORBFE_DESC_STRIDE=0: describe waves take consecutive slots in batches too (A/B)
-    bool desc_stride = !(std::getenv("ORBFE_DESC_STRIDE") && std::strcmp(std::getenv("ORBFE_DESC_STRIDE"), "0") == 0);
-    // ORBFE_DESC_ORDER=0: strided describe waves take the oct-tree output order (A/B); 2: the
-    // band order at every frame size
-    bool desc_order = !(std::getenv("ORBFE_DESC_ORDER") && std::strcmp(std::getenv("ORBFE_DESC_ORDER"), "0") == 0);
-    bool desc_order_all = std::getenv("ORBFE_DESC_ORDER") && std::strcmp(std::getenv("ORBFE_DESC_ORDER"), "2") == 0;
     int num_cus = 256;  // compute units of the device (launch-shape choices)
-    // ORBFE_OCT_SMALL=0: small batches keep the 256-thread oct-tree (A/B)
-    bool oct_small = !(std::getenv("ORBFE_OCT_SMALL") && std::strcmp(std::getenv("ORBFE_OCT_SMALL"), "0") == 0);
-    int desc_g16 = std::getenv("ORBFE_DESC_G16") ? std::atoi(std::getenv("ORBFE_DESC_G16")) : 0;
-    bool graph_broken = std::getenv("ORBFE_NO_GRAPH") != nullptr;  // capture failed once (or
-                                 // disabled for A/B runs): keep to the launch path
+    bool graph_broken = sw.no_graph;  // capture failed once (or disabled for A/B runs): keep to
+                                      // the launch path
 
     void drop_graph() {
         for (hipGraphExec_t& g : g1) {
@@ -283,7 +296,7 @@ struct orbfe_extractor {
                                pin_desc.p, pin_n.p,
                                reinterpret_cast<const void*>((uintptr_t)w << 32 | (uint32_t)h),
                                reinterpret_cast<const void*>((uintptr_t)frames_cap),
-                               reinterpret_cast<const void*>((uintptr_t)zero_copy)};
+                               reinterpret_cast<const void*>((uintptr_t)sw.zero_copy)};
         if (g1[gi] && std::memcmp(key, g1_key[gi], sizeof(key)) != 0) {
             hipGraphExecDestroy(g1[gi]);
             g1[gi] = nullptr;
@@ -299,8 +312,8 @@ struct orbfe_extractor {
             // zero-copy: the pyramid kernel reads the frame from the pinned staging buffer and
             // writes level 0 into the slab as it goes (no H2D copy), describe writes keypoints,
             // descriptors and the count straight into the pinned outputs (no D2H copies)
-            const bool zc_out = zero_copy && pin_kps.d && pin_desc.d && pin_n.d;
-            const bool zc_in = zero_copy && src.d && pyr_path(1);
+            const bool zc_out = sw.zero_copy && pin_kps.d && pin_desc.d && pin_n.d;
+            const bool zc_in = sw.zero_copy && src.d && band_path(1);
             LevelPtr lp0{pyr.as<uint8_t>() + l0.off, g.slab, l0.pitch};
             bool ok = true;
             if (zc_in) {
@@ -353,18 +366,18 @@ struct orbfe_extractor {
     int set_plan(int w, int h) {
         if (planned && plan.w == w && plan.h == h) return ORBFE_OK;
         Plan g;
-        int st = plan_geometry(tab, w, h, g);
+        int st = plan_geometry(tab, w, h, g, sw.pyr_lds_kb);
         if (st != ORBFE_OK) return st;
         if ((st = cells.ensure(std::max<size_t>(1, g.cells.size()) * sizeof(CellDesc)))) return st;
         if ((st = xtab.ensure(std::max<size_t>(1, g.xtab.size()) * sizeof(int)))) return st;
         if ((st = ytab.ensure(std::max<size_t>(1, g.ytab.size()) * sizeof(int)))) return st;
         if ((st = bslot.ensure(kBlurFragBytes + g.bitems.size() * sizeof(uint32_t)))) return st;
-        if ((st = ptab.ensure(std::max<size_t>(16, g.ptab.size() * sizeof(uint32_t))))) return st;
-        if (!g.ptab.empty())
-            ORBFE_HIP(hipMemcpyAsync(ptab.p, g.ptab.data(), g.ptab.size() * sizeof(uint32_t),
+        if ((st = ptab.ensure(std::max<size_t>(16, g.pyr.tab.size() * sizeof(uint32_t))))) return st;
+        if (!g.pyr.tab.empty())
+            ORBFE_HIP(hipMemcpyAsync(ptab.p, g.pyr.tab.data(), g.pyr.tab.size() * sizeof(uint32_t),
                                      hipMemcpyHostToDevice, stream));
-        if (g.pyr_ok) {  // dynamic LDS above 64 KB must be allowed per kernel
-            const int mx = (int)std::max(g.pyr_lds[0], g.pyr_lds[1]);
+        if (g.pyr.ok) {  // dynamic LDS above 64 KB must be allowed per kernel
+            const int mx = (int)std::max(g.pyr.lds[0], g.pyr.lds[1]);
             hipFuncSetAttribute(reinterpret_cast<const void*>(&pyramid_kernel<false>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, mx);
             hipFuncSetAttribute(reinterpret_cast<const void*>(&pyramid_kernel<true>),
@@ -429,254 +442,232 @@ struct orbfe_extractor {
             bp[l] = LevelPtr{blur.as<uint8_t>() + lv.off, g.slab, lv.pitch};
         }
         lp[0] = l0;
-        // K1 cascaded pyramid: one launch per level, 128 x 32 tiles of every frame; the small
-        // top levels (tail_start ..) in one K1b launch, a workgroup per frame
-        // (a batch of a few frames would leave most CUs idle in the tail: per-level launches)
-        const int ts = n >= kTailMinFrames ? std::min(g.tail_start, L) : L;
-        // K1 as one launch (pyramid_kernel): every level of a band of every frame in LDS
-        const int which = n >= pyr_small_below ? 0 : 1;
-        const bool one_pyr = pyr_path(n);
-        if (l0_from_stage && !one_pyr) return ORBFE_ERR_ARG;  // callers check pyr_path first
-        if (one_pyr) {
-            PyrArgs pa;
-            pa.src = l0_from_stage ? l0_stage : lp[0];
-            pa.l0_copy = l0_from_stage ? lp[0] : LevelPtr{nullptr, 0, 0};
-            pa.nlevels = L;
-            for (int l = 0; l < L; ++l) {
-                pa.dst[l] = lp[l];
-                pa.w[l] = g.geo.lv[l].w;
-                pa.lp[l] = g.pyr_lp[l];
-                pa.gtab[l] = ptab.as<uint4>() + g.gtab_off[l];
-                pa.yt[l] = ytab.as<int>() + g.yoff[l];
-                pa.simd_xb[l] = x86() ? sse2_body_resize(pa.w[l]) : 0;
-            }
-            pa.buf_b = g.pyr_bufb[which];
-            pa.ybuf = g.pyr_ybuf[which];
-            pa.ymax = g.pyr_ymax[which];
-            pa.bands = reinterpret_cast<const int4*>(ptab.as<uint4>() + g.band_off[which]);
-            if (x86())
-                ORBFE_LAUNCH(prof, ORBFE_STAGE_RESIZE, pyramid_kernel<true>, dim3(g.nbands[which], n),
-                             dim3(kPyrBlockSize), g.pyr_lds[which], stream, pa);
-            else
-                ORBFE_LAUNCH(prof, ORBFE_STAGE_RESIZE, pyramid_kernel<false>, dim3(g.nbands[which], n),
-                             dim3(kPyrBlockSize), g.pyr_lds[which], stream, pa);
-        }
-        for (int l = 1; l < (one_pyr ? 1 : ts); ++l) {
-            // levels l and l + 1 in one launch (resize2_kernel) where planned; ORBFE_RS2=0: one
-            // launch per level
-            if (use_rs2 && l + 1 < ts && g.rs2_ok[l] && !table_off) {
-                Resize2Args r2;
-                r2.src = lp[l - 1];
-                r2.mid = lp[l];
-                r2.dst = lp[l + 1];
-                r2.sw = g.geo.lv[l - 1].w;
-                r2.mw = g.geo.lv[l].w;
-                r2.dw = g.geo.lv[l + 1].w;
-                r2.dh = g.geo.lv[l + 1].h;
-                r2.tiles_x = g.rs2_tiles_x[l];
-                r2.tiles = reinterpret_cast<const int4*>(ptab.as<uint4>() + g.rs2_off[l]);
-                r2.yt_m = ytab.as<int>() + g.yoff[l];
-                r2.xt_m = xtab.as<int>() + g.xoff[l];
-                r2.yt_d = ytab.as<int>() + g.yoff[l + 1];
-                r2.xt_d = xtab.as<int>() + g.xoff[l + 1];
-                r2.gtab_m = ptab.as<uint4>() + g.gtab_off[l];
-                r2.gtab_d = ptab.as<uint4>() + g.gtab_off[l + 1];
-                r2.pa = g.rs2_pa[l];
-                r2.pb = g.rs2_pb[l];
-                r2.bofs = g.rs2_bofs[l];
-                r2.xb_m = x86() ? sse2_body_resize(r2.mw) : 0;
-                r2.xb_d = x86() ? sse2_body_resize(r2.dw) : 0;
-                if (x86())
-                    ORBFE_LAUNCH(prof, ORBFE_STAGE_RESIZE, resize2_kernel<true>, dim3(g.rs2_tiles[l], n),
-                                 dim3(256), g.rs2_lds[l], stream, r2);
-                else
-                    ORBFE_LAUNCH(prof, ORBFE_STAGE_RESIZE, resize2_kernel<false>, dim3(g.rs2_tiles[l], n),
-                                 dim3(256), g.rs2_lds[l], stream, r2);
-                ++l;
-                continue;
-            }
-            ResizeArgs ra;
-            ra.src = lp[l - 1];
-            ra.dst = lp[l];
-            ra.sw = g.geo.lv[l - 1].w;
-            ra.sh = g.geo.lv[l - 1].h;
-            ra.dw = g.geo.lv[l].w;
-            ra.dh = g.geo.lv[l].h;
-            ra.tiles_x = g.rs_tiles_x[l];
-            ra.lds_pitch = g.rs_pitch[l];
-            ra.xt = xtab.as<int>() + g.xoff[l];
-            ra.yt = ytab.as<int>() + g.yoff[l];
-            ra.simd_xb = x86() ? sse2_body_resize(ra.dw) : 0;
-            ra.gtab = g.pyr_ok && !table_off ? ptab.as<uint4>() + g.gtab_off[l] : nullptr;
-            if (x86()) {
-                ORBFE_LAUNCH(prof, ORBFE_STAGE_RESIZE, resize_kernel<true>, dim3(g.rs_tiles[l], n),
-                             dim3(256), g.rs_lds[l], stream, ra);
-            } else {
-                ORBFE_LAUNCH(prof, ORBFE_STAGE_RESIZE, resize_kernel<false>, dim3(g.rs_tiles[l], n),
-                             dim3(256), g.rs_lds[l], stream, ra);
-            }
-        }
-        if (!one_pyr && ts < L) {
-            ResizeTailArgs ta;
-            ta.src = lp[ts - 1];
-            ta.sh = g.geo.lv[ts - 1].h;
-            ta.nt = L - ts;
-            ta.lp[0] = (g.geo.lv[ts - 1].w + 15) & ~15;  // 16-byte chunk staging
-            ta.buf_b = ta.lp[0] * ta.sh;
-            for (int k = 0; k < ta.nt; ++k) {
-                const int l = ts + k;
-                ta.lp[k + 1] = (g.geo.lv[l].w + 3) & ~3;
-                ta.dw[k] = g.geo.lv[l].w;
-                ta.dh[k] = g.geo.lv[l].h;
-                ta.xt[k] = xtab.as<int>() + g.xoff[l];
-                ta.yt[k] = ytab.as<int>() + g.yoff[l];
-                ta.dst[k] = lp[l];
-                ta.simd_xb[k] = x86() ? sse2_body_resize(ta.dw[k]) : 0;
-            }
-            if (x86())
-                ORBFE_LAUNCH(prof, ORBFE_STAGE_RESIZE, resize_tail_kernel<true>, dim3(n),
-                             dim3(kTailBlock), 0, stream, ta);
-            else
-                ORBFE_LAUNCH(prof, ORBFE_STAGE_RESIZE, resize_tail_kernel<false>, dim3(n),
-                             dim3(kTailBlock), 0, stream, ta);
-        }
-        // K2 FAST per cell
-        const int ncells = (int)g.cells.size();
-        if (ncells > 0) {
-            FastArgs fa;
-            fa.cells = cells.as<CellDesc>();
-            fa.ncells = ncells;
-            fa.cell_cap_total = g.cell_cap_total;
-            fa.ini_th = std::min(std::max(tab.p.ini_th_fast, 0), 255);
-            fa.min_th = std::min(std::max(tab.p.min_th_fast, 0), 255);
-            fa.roi_pitch = g.roi_pitch;
-            fa.roi_rows = g.roi_rows;
-            fa.cand_max = g.cand_max;
-            fa.cell_cnt = cell_cnt.as<int>();
-            fa.cell_keys = cell_keys.as<uint32_t>();
-            fa.level_keys = level_keys.as<int>();
-            for (int l = 0; l < L; ++l) fa.pyr[l] = lp[l];
-            if (g.roi_pitch == kFastPitch)
-                ORBFE_LAUNCH(prof, ORBFE_STAGE_FAST, fast_kernel<kFastPitch>, dim3(ncells, n), dim3(kFastBlockSize), g.fast_lds, stream, fa);
-            else
-                ORBFE_LAUNCH(prof, ORBFE_STAGE_FAST, fast_kernel<0>, dim3(ncells, n), dim3(kFastBlockSize), g.fast_lds, stream, fa);
-        }
-        // K3 oct-tree per (frame, level)
-        OctArgs oa;
-        oa.geo = g.geo;
-        oa.cells = cells.as<CellDesc>();
-        oa.ncells = ncells;
-        oa.cell_cap_total = g.cell_cap_total;
-        oa.cell_cnt = cell_cnt.as<int>();
-        oa.cell_keys = cell_keys.as<uint32_t>();
-        oa.level_keys = level_keys.as<int>();
-        oa.keys = keys.as<uint32_t>();
-        oa.act = act.as<int4>();
-        oa.oct_out = oct_out.as<uint32_t>();
-        oa.oct_cnt = oct_cnt.as<int>();
+        if (l0_from_stage && !band_path(n)) return ORBFE_ERR_ARG;  // callers check band_path first
         // describe's strided waves (batches) sweep each level in 32-row bands where a frame's
         // pyramid overflows half an XCD's L2 (level 0 >= 1 Mpx; 1080p: describe traffic -13 %,
         // 640 x 480: no traffic to save, oct-tree +2.5 %): the oct-tree writes that order beside
         // its output (ORBFE_DESC_ORDER=0: never, =2: at every size)
-        const bool banded = n >= kDescSmallBatch && desc_stride && desc_order &&
-                            (desc_order_all || (long long)g.geo.lv[0].w * g.geo.lv[0].h >= (1 << 20));
+        const bool banded = n >= kDescSmallBatch && sw.desc_stride && sw.desc_order &&
+                            (sw.desc_order_all || (long long)g.geo.lv[0].w * g.geo.lv[0].h >= (1 << 20));
+        launch_pyramid(n, lp);
+        launch_fast(n, lp);
+        launch_octree(n, banded);
+        // K4 blur: fused into K5, where each keypoint's window is blurred in LDS, or (PREBLUR)
+        // every level of every frame, read by the pre-blurred describe
+        if (!sw.fused_blur) launch_blur(n, lp, bp);
+        launch_describe(n, lp, bp, banded, d_kps, kps_cap, d_desc, d_n);
+        ORBFE_HIP(hipGetLastError());
+        last_n = n;
+        for (int l = 0; l < L; ++l) last_pyr[l] = lp[l];
+        return ORBFE_OK;
+    }
+
+    const int* xt(int l) const { return xtab.as<int>() + plan.xoff[l]; }  // level l's resize tables
+    const int* yt(int l) const { return ytab.as<int>() + plan.yoff[l]; }
+    const uint4* gtab(int l) const { return ptab.as<uint4>() + plan.pyr.gtab_off[l]; }
+    int xb_resize(int w) const { return x86() ? sse2_body_resize(w) : 0; }  // x86 SIMD-body bounds
+    int xb_blur(int w) const { return x86() ? sse2_body_blur(w) : 0; }
+
+    // K1 as one launch (pyramid_kernel): every level of a band of every frame in LDS
+    void launch_bands(int n, const LevelPtr* lp) {
+        const Plan::Pyr& p = plan.pyr;
+        const int which = n >= sw.pyr_small_below ? 0 : 1;
+        PyrArgs pa;
+        pa.src = l0_from_stage ? l0_stage : lp[0];
+        pa.l0_copy = l0_from_stage ? lp[0] : LevelPtr{nullptr, 0, 0};
+        pa.nlevels = plan.geo.nlevels;
+        for (int l = 0; l < pa.nlevels; ++l) {
+            pa.dst[l] = lp[l];
+            pa.w[l] = plan.geo.lv[l].w;
+            pa.lp[l] = p.lp[l];
+            pa.gtab[l] = gtab(l);
+            pa.yt[l] = yt(l);
+            pa.simd_xb[l] = xb_resize(pa.w[l]);
+        }
+        pa.buf_b = p.bufb[which], pa.ybuf = p.ybuf[which], pa.ymax = p.ymax[which];
+        pa.bands = reinterpret_cast<const int4*>(ptab.as<uint4>() + p.band_off[which]);
+        ORBFE_LAUNCH_X86(x86(), prof, ORBFE_STAGE_RESIZE, pyramid_kernel, dim3(p.nbands[which], n),
+                         dim3(kPyrBlock), p.lds[which], stream, pa);
+    }
+
+    // levels l and l + 1 from level l - 1 in one launch (resize2_kernel)
+    void launch_resize2(int n, const LevelPtr* lp, int l) {
+        const Plan::Pyr::Resize2& p = plan.pyr.rs2;
+        Resize2Args r2;
+        r2.src = lp[l - 1], r2.mid = lp[l], r2.dst = lp[l + 1];
+        r2.sw = plan.geo.lv[l - 1].w, r2.mw = plan.geo.lv[l].w;
+        r2.dw = plan.geo.lv[l + 1].w, r2.dh = plan.geo.lv[l + 1].h;
+        r2.tiles_x = p.tiles_x[l];
+        r2.tiles = reinterpret_cast<const int4*>(ptab.as<uint4>() + p.off[l]);
+        r2.yt_m = yt(l), r2.xt_m = xt(l), r2.gtab_m = gtab(l), r2.xb_m = xb_resize(r2.mw);
+        r2.yt_d = yt(l + 1), r2.xt_d = xt(l + 1), r2.gtab_d = gtab(l + 1), r2.xb_d = xb_resize(r2.dw);
+        r2.pa = p.pa[l], r2.pb = p.pb[l], r2.bofs = p.bofs[l];
+        ORBFE_LAUNCH_X86(x86(), prof, ORBFE_STAGE_RESIZE, resize2_kernel, dim3(p.tiles[l], n), dim3(256),
+                         p.lds[l], stream, r2);
+    }
+
+    // level l from level l - 1 (resize_kernel)
+    void launch_resize(int n, const LevelPtr* lp, int l) {
+        const Plan::Pyr::Resize& p = plan.pyr.rs;
+        ResizeArgs ra;
+        ra.src = lp[l - 1], ra.dst = lp[l];
+        ra.sw = plan.geo.lv[l - 1].w, ra.sh = plan.geo.lv[l - 1].h;
+        ra.dw = plan.geo.lv[l].w, ra.dh = plan.geo.lv[l].h;
+        ra.tiles_x = p.tiles_x[l], ra.lds_pitch = p.pitch[l];
+        ra.xt = xt(l), ra.yt = yt(l), ra.simd_xb = xb_resize(ra.dw);
+        ra.gtab = plan.pyr.ok && !sw.table_off ? gtab(l) : nullptr;
+        ORBFE_LAUNCH_X86(x86(), prof, ORBFE_STAGE_RESIZE, resize_kernel, dim3(p.tiles[l], n), dim3(256),
+                         p.lds[l], stream, ra);
+    }
+
+    // K1b: levels ts .. L - 1 from level ts - 1, a workgroup per frame (resize_tail_kernel)
+    void launch_tail(int n, const LevelPtr* lp, int ts) {
+        const Geo& geo = plan.geo;
+        ResizeTailArgs ta;
+        ta.src = lp[ts - 1], ta.sh = geo.lv[ts - 1].h, ta.nt = geo.nlevels - ts;
+        ta.lp[0] = (geo.lv[ts - 1].w + 15) & ~15;  // 16-byte chunk staging
+        ta.buf_b = ta.lp[0] * ta.sh;
+        for (int k = 0; k < ta.nt; ++k) {
+            const int l = ts + k;
+            ta.lp[k + 1] = (geo.lv[l].w + 3) & ~3;
+            ta.dw[k] = geo.lv[l].w, ta.dh[k] = geo.lv[l].h;
+            ta.xt[k] = xt(l), ta.yt[k] = yt(l), ta.simd_xb[k] = xb_resize(ta.dw[k]);
+            ta.dst[k] = lp[l];
+        }
+        ORBFE_LAUNCH_X86(x86(), prof, ORBFE_STAGE_RESIZE, resize_tail_kernel, dim3(n), dim3(kTailBlock), 0,
+                         stream, ta);
+    }
+
+    // K1 cascaded pyramid: one launch (launch_bands), or one launch per level or level pair, 128 x
+    // 32 tiles of every frame, and the small top levels (tail_start ..) in one K1b launch, a
+    // workgroup per frame (a batch of a few frames would leave most CUs idle in the tail:
+    // per-level launches)
+    void launch_pyramid(int n, const LevelPtr* lp) {
+        if (band_path(n)) return launch_bands(n, lp);
+        const int L = plan.geo.nlevels;
+        const int ts = n >= kTailMinFrames ? std::min(plan.pyr.tail_start, L) : L;
+        for (int l = 1; l < ts; ++l) {
+            // levels l and l + 1 in one launch where planned; ORBFE_RS2=0: one launch per level
+            if (sw.use_rs2 && l + 1 < ts && plan.pyr.rs2.ok[l] && !sw.table_off)
+                launch_resize2(n, lp, l++);
+            else
+                launch_resize(n, lp, l);
+        }
+        if (ts < L) launch_tail(n, lp, ts);
+    }
+
+    // K2 FAST per cell
+    void launch_fast(int n, const LevelPtr* lp) {
+        const int ncells = (int)plan.cells.size();
+        if (ncells == 0) return;
+        const Plan::Fast& p = plan.fast;
+        FastArgs fa;
+        fa.cells = cells.as<CellDesc>(), fa.ncells = ncells, fa.cell_cap_total = plan.cell_cap_total;
+        fa.ini_th = std::min(std::max(tab.p.ini_th_fast, 0), 255);
+        fa.min_th = std::min(std::max(tab.p.min_th_fast, 0), 255);
+        fa.roi_pitch = p.roi_pitch, fa.roi_rows = p.roi_rows, fa.cand_max = p.cand_max;
+        fa.cell_cnt = cell_cnt.as<int>(), fa.cell_keys = cell_keys.as<uint32_t>();
+        fa.level_keys = level_keys.as<int>();
+        for (int l = 0; l < plan.geo.nlevels; ++l) fa.pyr[l] = lp[l];
+        if (p.roi_pitch == kFastPitch)
+            ORBFE_LAUNCH(prof, ORBFE_STAGE_FAST, fast_kernel<kFastPitch>, dim3(ncells, n), dim3(kFastBlock), p.lds, stream, fa);
+        else
+            ORBFE_LAUNCH(prof, ORBFE_STAGE_FAST, fast_kernel<0>, dim3(ncells, n), dim3(kFastBlock), p.lds, stream, fa);
+    }
+
+    // K3 oct-tree per (frame, level); banded: it also writes describe's band order (run())
+    void launch_octree(int n, bool banded) {
+        const Plan::Oct& p = plan.oct;
+        const int L = plan.geo.nlevels;
+        OctArgs oa;
+        oa.geo = plan.geo;
+        oa.cells = cells.as<CellDesc>(), oa.ncells = (int)plan.cells.size();
+        oa.cell_cap_total = plan.cell_cap_total;
+        oa.cell_cnt = cell_cnt.as<int>(), oa.cell_keys = cell_keys.as<uint32_t>();
+        oa.level_keys = level_keys.as<int>();
+        oa.keys = keys.as<uint32_t>(), oa.act = act.as<int4>();
+        oa.oct_out = oct_out.as<uint32_t>(), oa.oct_cnt = oct_cnt.as<int>();
         oa.oct_ord = banded ? oct_ord.as<uint16_t>() : nullptr;
-        oa.ncap_max = g.ncap_max;
-        oa.sort_cap = g.sort_cap;
-        oa.lds_keys = g.oct_keys;
+        oa.ncap_max = p.ncap_max, oa.sort_cap = p.sort_cap, oa.lds_keys = p.keys;
         // 1024-thread trees while the launch has at most one tree per CU (the single-frame call,
         // config 4 at 32 frames per rank: each level-0 tree is the launch's long pole); 256-thread
         // trees, six per CU, for larger batches (throughput)
-        if (n * L <= num_cus && oct_small)
-            ORBFE_LAUNCH(prof, ORBFE_STAGE_OCTREE, octree_kernel<1024>, dim3(n, L), dim3(1024), g.oct_lds, stream, oa);
+        if (n * L <= num_cus && sw.oct_small)
+            ORBFE_LAUNCH(prof, ORBFE_STAGE_OCTREE, octree_kernel<1024>, dim3(n, L), dim3(1024), p.lds, stream, oa);
         else
-            ORBFE_LAUNCH(prof, ORBFE_STAGE_OCTREE, octree_kernel<kOctBlockSize>, dim3(n, L), dim3(kOctBlockSize), g.oct_lds, stream, oa);
-        // K4 blur: fused into K5, where each keypoint's window is blurred in LDS, or (PREBLUR)
-        // every level of every frame, read by the pre-blurred describe
-        if (!fused_blur) {
-            BlurArgs ba;
-            ba.nlevels = L;
-            for (int l = 0; l < L; ++l) {
-                ba.w[l] = g.geo.lv[l].w;
-                ba.h[l] = g.geo.lv[l].h;
-                ba.src[l] = lp[l];
-                ba.dst[l] = bp[l];
-                ba.simd_xb[l] = x86() ? sse2_body_blur(g.geo.lv[l].w) : 0;
-            }
-            ba.frags = bslot.as<uint4>();
-            ba.items = reinterpret_cast<const uint32_t*>(bslot.as<uint8_t>() + kBlurFragBytes);
-            ba.nitems = (int)g.bitems.size();
-            for (int i = 0; i < 4; ++i) ba.taps[i] = tab.taps[i];
-            if (x86())
-                ORBFE_LAUNCH(prof, ORBFE_STAGE_BLUR, blur_mfma_kernel<true>, dim3(ba.nitems, n), dim3(256), 0, stream, ba);
-            else
-                ORBFE_LAUNCH(prof, ORBFE_STAGE_BLUR, blur_mfma_kernel<false>, dim3(ba.nitems, n), dim3(256), 0, stream, ba);
+            ORBFE_LAUNCH(prof, ORBFE_STAGE_OCTREE, octree_kernel<kOctBlock>, dim3(n, L), dim3(kOctBlock), p.lds, stream, oa);
+    }
+
+    // K4's arguments: every level of src blurred into dst
+    BlurArgs blur_args(const LevelPtr* src, const LevelPtr* dst) const {
+        BlurArgs ba;
+        ba.nlevels = plan.geo.nlevels;
+        for (int l = 0; l < ba.nlevels; ++l) {
+            ba.w[l] = plan.geo.lv[l].w, ba.h[l] = plan.geo.lv[l].h, ba.simd_xb[l] = xb_blur(ba.w[l]);
+            ba.src[l] = src[l], ba.dst[l] = dst[l];
         }
-        // K5 describe
+        ba.frags = bslot.as<uint4>();
+        ba.items = reinterpret_cast<const uint32_t*>(bslot.as<uint8_t>() + kBlurFragBytes);
+        ba.nitems = (int)plan.bitems.size();
+        for (int i = 0; i < 4; ++i) ba.taps[i] = tab.taps[i];
+        return ba;
+    }
+    void launch_blur(int n, const LevelPtr* lp, const LevelPtr* bp) {
+        const BlurArgs ba = blur_args(lp, bp);
+        ORBFE_LAUNCH_X86(x86(), prof, ORBFE_STAGE_BLUR, blur_mfma_kernel, dim3(ba.nitems, n), dim3(256), 0,
+                         stream, ba);
+    }
+
+    // K5 describe
+    void launch_describe(int n, const LevelPtr* lp, const LevelPtr* bp, bool banded,
+                         orbfe_keypoint* d_kps, int kps_cap, uint8_t* d_desc, int32_t* d_n) {
+        const Geo& geo = plan.geo;
         DescArgs da;
-        da.nlevels = L;
-        da.out_total = g.geo.out_total;
-        da.kps_cap = kps_cap;
-        for (int l = 0; l < L; ++l) {
-            da.out_off[l] = g.geo.lv[l].out_off;
-            da.scale[l] = g.geo.lv[l].scale;
-            da.size[l] = g.geo.lv[l].size;
-            da.pyr[l] = lp[l];
-            da.blur[l] = bp[l];
-            da.w[l] = g.geo.lv[l].w;
-            da.h[l] = g.geo.lv[l].h;
-            da.simd_xb[l] = x86() ? sse2_body_blur(da.w[l]) : 0;
+        da.nlevels = geo.nlevels, da.out_total = geo.out_total, da.kps_cap = kps_cap;
+        for (int l = 0; l < geo.nlevels; ++l) {
+            da.out_off[l] = geo.lv[l].out_off, da.scale[l] = geo.lv[l].scale, da.size[l] = geo.lv[l].size;
+            da.pyr[l] = lp[l], da.blur[l] = bp[l];
+            da.w[l] = geo.lv[l].w, da.h[l] = geo.lv[l].h, da.simd_xb[l] = xb_blur(da.w[l]);
         }
         for (int i = 0; i < 4; ++i) da.taps[i] = tab.taps[i];
-        da.oct_out = oct_out.as<uint32_t>();
-        da.oct_cnt = oct_cnt.as<int>();
+        da.oct_out = oct_out.as<uint32_t>(), da.oct_cnt = oct_cnt.as<int>();
         da.oct_ord = banded ? oct_ord.as<uint16_t>() : nullptr;
-        da.kps = d_kps;
-        da.desc = d_desc;
-        da.n_out = d_n;
-        const bool all_pre = !fused_blur && pre_mask_env == 0xffffffffu;
-        da.pre_mask = fused_blur ? 0u : pre_mask_env;
+        da.kps = d_kps, da.desc = d_desc, da.n_out = d_n;
+        const bool all_pre = !sw.fused_blur && sw.pre_mask == 0xffffffffu;
+        da.pre_mask = sw.fused_blur ? 0u : sw.pre_mask;
         // a wave takes kDescGroupSize keypoints (the trig and pattern loads amortised over the
         // group); small batches take kDescGroupSmall, for four times the waves in flight
         // (x86 arithmetic: the rotation FMA-contracted, kFma)
         // window source: every level pre-blurred, some levels pre-blurred (VALU blur for the
         // rest), or none (the matrix-core blur unless ORBFE_DESC_MFMA=0)
-        const int win = all_pre ? kWinPre : (da.pre_mask == 0u && desc_mfma ? kWinMfma : kWinValu);
+        const int win = all_pre ? kWinPre : (da.pre_mask == 0u && sw.desc_mfma ? kWinMfma : kWinValu);
         // ORBFE_DESC_G16=1 (opt-in): 16 keypoints per wave in strided x86 matrix-core batches.
         // At 640 x 480 describe runs 2 % faster (c3 +1.3 % frames/s) but moves 1.30 GB per
         // 512-frame launch instead of 0.70 (1.65x its algorithmic bytes: the frames in flight
         // per XCD double); at 1080p it is 9 % slower (profiles/r04/experiments/describe_g16/)
-        const bool g16 = desc_g16 == 1 && n >= kDescSmallBatch && desc_stride && x86() && win == kWinMfma;
+        const bool g16 = sw.desc_g16 == 1 && n >= kDescSmallBatch && sw.desc_stride && x86() && win == kWinMfma;
         const int group = g16 ? 16 : n >= kDescSmallBatch ? kDescGroupSize : kDescGroupSmall;
-        const int per_block = (kDescBlockSize / 64) * group;  // slots per workgroup
-        const dim3 dgrid((g.geo.out_total + per_block - 1) / per_block, n);
+        const int per_block = (kDescBlock / 64) * group;  // slots per workgroup
+        const dim3 dgrid((geo.out_total + per_block - 1) / per_block, n);
         // batches: strided slots (a frame's waves sweep its oct-tree output in runs of W
         // consecutive slots, sharing window lines in L2); ORBFE_DESC_STRIDE=0: grouped slots
-        da.wave_stride = (group == kDescGroupSize || g16) && desc_stride ? (int)dgrid.x * (kDescBlockSize / 64) : 0;
+        da.wave_stride = (group == kDescGroupSize || g16) && sw.desc_stride ? (int)dgrid.x * (kDescBlock / 64) : 0;
         da.frags = bslot.as<uint4>() + kDescFragOff;
-        const int variant = g16 ? 12 : (group == kDescGroupSize ? 6 : 0) + (x86() ? 3 : 0) + win;
-        switch (variant) {
-#define ORBFE_DESC_CASE(V, G, X, W) \
-            case V: ORBFE_LAUNCH(prof, ORBFE_STAGE_DESCRIBE, (describe_kernel<G, X, W>), dgrid, dim3(kDescBlockSize), 0, stream, da); break;
-            ORBFE_DESC_CASE(0, kDescGroupSmall, false, kWinValu)
-            ORBFE_DESC_CASE(1, kDescGroupSmall, false, kWinPre)
-            ORBFE_DESC_CASE(2, kDescGroupSmall, false, kWinMfma)
-            ORBFE_DESC_CASE(3, kDescGroupSmall, true, kWinValu)
-            ORBFE_DESC_CASE(4, kDescGroupSmall, true, kWinPre)
-            ORBFE_DESC_CASE(5, kDescGroupSmall, true, kWinMfma)
-            ORBFE_DESC_CASE(6, kDescGroupSize, false, kWinValu)
-            ORBFE_DESC_CASE(7, kDescGroupSize, false, kWinPre)
-            ORBFE_DESC_CASE(8, kDescGroupSize, false, kWinMfma)
-            ORBFE_DESC_CASE(9, kDescGroupSize, true, kWinValu)
-            ORBFE_DESC_CASE(10, kDescGroupSize, true, kWinPre)
-            ORBFE_DESC_CASE(11, kDescGroupSize, true, kWinMfma)
-            ORBFE_DESC_CASE(12, 16, true, kWinMfma)
-#undef ORBFE_DESC_CASE
+#define ORBFE_DESC_LAUNCH(G, X, W) \
+        ORBFE_LAUNCH(prof, ORBFE_STAGE_DESCRIBE, (describe_kernel<G, X, W>), dgrid, dim3(kDescBlock), 0, stream, da)
+#define ORBFE_DESC_CASE(V, G, W) \
+            case V: if (x86()) ORBFE_DESC_LAUNCH(G, true, W); else ORBFE_DESC_LAUNCH(G, false, W); break;
+        switch (g16 ? 6 : (group == kDescGroupSize ? 3 : 0) + win) {
+            ORBFE_DESC_CASE(0, kDescGroupSmall, kWinValu)
+            ORBFE_DESC_CASE(1, kDescGroupSmall, kWinPre)
+            ORBFE_DESC_CASE(2, kDescGroupSmall, kWinMfma)
+            ORBFE_DESC_CASE(3, kDescGroupSize, kWinValu)
+            ORBFE_DESC_CASE(4, kDescGroupSize, kWinPre)
+            ORBFE_DESC_CASE(5, kDescGroupSize, kWinMfma)
+            case 6: ORBFE_DESC_LAUNCH(16, true, kWinMfma); break;  // g16 is x86 only
         }
-        ORBFE_HIP(hipGetLastError());
-        last_n = n;
-        for (int l = 0; l < L; ++l) last_pyr[l] = lp[l];
-        return ORBFE_OK;
+#undef ORBFE_DESC_CASE
+#undef ORBFE_DESC_LAUNCH
     }
 
     // K0: level 0 of every frame from the caller's frames (gray or colour), full masks laid out
@@ -808,15 +799,36 @@ struct DeviceGuard {
         if (prev >= 0 && cur != prev) hipSetDevice(prev);
     }
 };
+
+// Every entry point that allocates or touches the device runs through here: std::bad_alloc ->
+// ORBFE_ERR_NOMEM, any other exception -> ORBFE_ERR_HIP; with a handle, its device made current
+// for the call (without: creation and the host-only queries).  Argument checks stay in front.
+template <class F>
+int guarded(F&& f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        return ORBFE_ERR_NOMEM;
+    } catch (...) {
+        return ORBFE_ERR_HIP;
+    }
+}
+template <class F>
+int guarded(const orbfe_extractor* h, F&& f) {
+    return guarded([&]() {
+        DeviceGuard dg(h->device);
+        return f();
+    });
+}
 }  // namespace
 
 extern "C" {
 
 orbfe_extractor* orbfe_create(const orbfe_params* params, int device, int max_width,
                               int max_height, int max_batch, int* status) {
-    int st = ORBFE_OK;
     orbfe_extractor* h = nullptr;
-    try {
+    int st = guarded([&]() {
+        int st = ORBFE_OK;
         if (!params) {
             st = ORBFE_ERR_ARG;
         } else if ((st = check_device(device)) == ORBFE_OK) {
@@ -836,11 +848,8 @@ orbfe_extractor* orbfe_create(const orbfe_params* params, int device, int max_wi
             if (st == ORBFE_OK) st = h->set_plan(w, hh);
             if (st == ORBFE_OK) st = h->ensure_frames(std::max(1, max_batch));
         }
-    } catch (const std::bad_alloc&) {
-        st = ORBFE_ERR_NOMEM;
-    } catch (...) {
-        st = ORBFE_ERR_HIP;
-    }
+        return st;
+    });
     if (st != ORBFE_OK && h) {
         delete h;
         h = nullptr;
@@ -909,37 +918,32 @@ int orbfe_keypoint_capacity(const orbfe_extractor* h) {
     return c;
 }
 
+// out_total of the plan for a w x hgt input (a host-only query: no plan is kept)
+static int planned_capacity(const HostTables& t, int w, int hgt, int pyr_lds_kb = kPyrLdsCapKB) {
+    return guarded([&]() {
+        Plan g;
+        const int st = plan_geometry(t, w, hgt, g, pyr_lds_kb);
+        return st != ORBFE_OK ? st : g.geo.out_total;
+    });
+}
+
 int orbfe_keypoint_capacity_for(const orbfe_extractor* h, int w, int hgt) {
     if (!h || w <= 0 || hgt <= 0) return ORBFE_ERR_ARG;
     if (h->planned && h->plan.w == w && h->plan.h == hgt) return h->plan.geo.out_total;
-    try {
-        Plan g;
-        const int st = plan_geometry(h->tab, w, hgt, g);
-        return st != ORBFE_OK ? st : g.geo.out_total;
-    } catch (const std::bad_alloc&) {
-        return ORBFE_ERR_NOMEM;
-    }
+    return planned_capacity(h->tab, w, hgt, h->sw.pyr_lds_kb);
 }
 
 int orbfe_keypoint_capacity_params(const orbfe_params* p, int w, int hgt) {
     if (!p || w <= 0 || hgt <= 0) return ORBFE_ERR_ARG;
-    try {
-        HostTables t{};
-        int st = make_tables(*p, t);
-        if (st != ORBFE_OK) return st;
-        Plan g;
-        st = plan_geometry(t, w, hgt, g);
-        return st != ORBFE_OK ? st : g.geo.out_total;
-    } catch (const std::bad_alloc&) {
-        return ORBFE_ERR_NOMEM;
-    }
+    HostTables t{};
+    const int st = make_tables(*p, t);
+    return st != ORBFE_OK ? st : planned_capacity(t, w, hgt);
 }
 
 static int extract_host_common(orbfe_extractor* h, const uint8_t* const* imgs, int n, int w,
                                int hgt, size_t stride, int pix, const uint8_t* const* masks,
                                size_t mask_stride, const orbfe_rect* rects, orbfe_keypoint* kps,
                                int kps_cap, uint8_t* desc, int32_t* n_out) {
-    DeviceGuard dg(h->device);
     h->staged_kps = nullptr;
     h->staged_desc = nullptr;
     h->staged_n = 0;
@@ -1009,53 +1013,40 @@ int orbfe_extract_color(orbfe_extractor* h, const uint8_t* img, int pix, int w, 
         (mask && mask_stride < (size_t)w))
         return ORBFE_ERR_ARG;
     if (!rect_ok(rect)) return ORBFE_ERR_UNSUPPORTED;
-    try {
+    return guarded(h, [&]() {
         const uint8_t* m[1] = {mask};
         int32_t cnt = 0;
         const int st = extract_host_common(h, &img, 1, w, hgt, stride, pix, mask ? m : nullptr,
                                            mask_stride, rect, kps, kps_cap, desc, &cnt);
         *n_out = cnt;
         return st;
-    } catch (const std::bad_alloc&) {
-        return ORBFE_ERR_NOMEM;
-    } catch (...) {
-        return ORBFE_ERR_HIP;
-    }
+    });
 }
 
 int orbfe_input_buffer(orbfe_extractor* h, int w, int hgt, uint8_t** buf, size_t* stride) {
     if (!h || w <= 0 || hgt <= 0 || !buf || !stride) return ORBFE_ERR_ARG;
-    try {
-        DeviceGuard dg(h->device);
+    return guarded(h, [&]() {
         int st;
         if ((st = h->set_plan(w, hgt))) return st;  // the size must be one the plan supports
         if ((st = h->pin_user.ensure((size_t)w * hgt))) return st;
         *buf = h->pin_user.p;
         *stride = (size_t)w;
         return ORBFE_OK;
-    } catch (const std::bad_alloc&) {
-        return ORBFE_ERR_NOMEM;
-    } catch (...) {
-        return ORBFE_ERR_HIP;
-    }
+    });
 }
 
 int orbfe_extract_staged(orbfe_extractor* h, int w, int hgt, orbfe_keypoint* kps, int kps_cap,
                          uint8_t* desc, int* n_out) {
     if (!h || w <= 0 || hgt <= 0 || !n_out || kps_cap < 0 || (kps_cap > 0 && !kps)) return ORBFE_ERR_ARG;
     if (!h->pin_user.p || h->pin_user.bytes < (size_t)w * hgt) return ORBFE_ERR_ARG;  // no buffer handed out
-    try {
+    return guarded(h, [&]() {
         const uint8_t* img = h->pin_user.p;
         int32_t cnt = 0;
         const int st = extract_host_common(h, &img, 1, w, hgt, (size_t)w, ORBFE_PIX_GRAY, nullptr, 0,
                                            nullptr, kps_cap ? kps : nullptr, kps_cap, desc, &cnt);
         *n_out = cnt;
         return st;
-    } catch (const std::bad_alloc&) {
-        return ORBFE_ERR_NOMEM;
-    } catch (...) {
-        return ORBFE_ERR_HIP;
-    }
+    });
 }
 
 int orbfe_staged_outputs(const orbfe_extractor* h, const orbfe_keypoint** kps, const uint8_t** desc,
@@ -1075,14 +1066,10 @@ int orbfe_extract_batch(orbfe_extractor* h, const uint8_t* const* imgs, int n, i
     if (stride < (size_t)w || (masks && mask_stride < (size_t)w)) return ORBFE_ERR_ARG;
     for (int f = 0; f < n; ++f)
         if (!imgs[f]) return ORBFE_ERR_ARG;
-    try {
+    return guarded(h, [&]() {
         return extract_host_common(h, imgs, n, w, hgt, stride, ORBFE_PIX_GRAY, masks, mask_stride,
                                    nullptr, kps, kps_cap, desc, n_out);
-    } catch (const std::bad_alloc&) {
-        return ORBFE_ERR_NOMEM;
-    } catch (...) {
-        return ORBFE_ERR_HIP;
-    }
+    });
 }
 
 int orbfe_extract_batch_device(orbfe_extractor* h, const uint8_t* d_imgs, int n, int w, int hgt,
@@ -1106,8 +1093,7 @@ int orbfe_extract_color_batch_device(orbfe_extractor* h, const uint8_t* d_imgs, 
     if (stride < (size_t)w * cn || (n > 1 && frame_pitch < stride * hgt)) return ORBFE_ERR_ARG;
     if (d_masks && (mask_stride < (size_t)w || (n > 1 && mask_frame_pitch < mask_stride * hgt)))
         return ORBFE_ERR_ARG;
-    try {
-        DeviceGuard dg(h->device);
+    return guarded(h, [&]() {
         int st;
         if ((st = h->set_plan(w, hgt))) return st;
         if (kps_cap < h->kp_capacity()) return ORBFE_ERR_CAPACITY;
@@ -1125,9 +1111,7 @@ int orbfe_extract_color_batch_device(orbfe_extractor* h, const uint8_t* d_imgs, 
             lp0 = LevelPtr{h->pyr.as<uint8_t>() + l0.off, g.slab, l0.pitch};
         }
         return h->run(n, lp0, d_kps, kps_cap, d_desc, d_n_out);
-    } catch (...) {
-        return ORBFE_ERR_HIP;
-    }
+    });
 }
 
 // ---- stereo (Frame::ComputeStereoMatches, Frame.cc:584-756) ----------------------------------
@@ -1213,8 +1197,7 @@ int orbfe_compute_stereo_matches(orbfe_extractor* left, orbfe_extractor* right, 
     if (st) return st;
     if (nl == 0) return ORBFE_OK;
     if (nr >= 65536) return ORBFE_ERR_UNSUPPORTED;  // candidate keys pack iR in 16 bits
-    try {
-        DeviceGuard dg(left->device);
+    return guarded(left, [&]() {
         orbfe_extractor* L = left;
         const int cap = std::max(nl, nr);
         hipStream_t s = L->stream;
@@ -1254,11 +1237,7 @@ int orbfe_compute_stereo_matches(orbfe_extractor* left, orbfe_extractor* right, 
         int status = 0;
         std::memcpy(&status, q + o_st, sizeof(int));
         return status;
-    } catch (const std::bad_alloc&) {
-        return ORBFE_ERR_NOMEM;
-    } catch (...) {
-        return ORBFE_ERR_HIP;
-    }
+    });
 }
 
 int orbfe_compute_stereo_matches_device(orbfe_extractor* left, orbfe_extractor* right, int n,
@@ -1272,13 +1251,10 @@ int orbfe_compute_stereo_matches_device(orbfe_extractor* left, orbfe_extractor* 
     int st = stereo_pair_ok(left, right, n);
     if (st || n == 0) return st;
     if (kps_cap >= 65536) return ORBFE_ERR_UNSUPPORTED;
-    try {
-        DeviceGuard dg(left->device);
+    return guarded(left, [&]() {
         return stereo_launch(left, right, 0, n, d_kl, d_dl, d_nl, d_kr, d_dr, d_nr, kps_cap, bf,
                              b, d_u_right, d_depth);
-    } catch (...) {
-        return ORBFE_ERR_HIP;
-    }
+    });
 }
 
 int orbfe_stereo_status(orbfe_extractor* left) {
@@ -1348,32 +1324,33 @@ int orbfe_profile_read(orbfe_extractor* h, double* total_ms, int32_t* launches) 
 // different stages running concurrently on two handles.
 int orbfe_debug_replay(orbfe_extractor* h, unsigned stage_mask, int reps) {
     if (!h || !h->planned || h->last_run.n < 1 || reps < 0 || !h->last_run.kps) return ORBFE_ERR_ARG;
-    DeviceGuard dg(h->device);
-    const auto r = h->last_run;
-    // FAST adds its per-level key totals into level_keys and the oct-tree reads and clears them
-    // (0 between calls).  A FAST replay without the oct-tree starts from zero each time; an
-    // oct-tree replay without FAST restores one FAST's totals (recomputed once) before each
-    // launch; both leave the totals at zero, as a full extraction does.
-    const bool fast = (stage_mask >> ORBFE_STAGE_FAST) & 1u, oct = (stage_mask >> ORBFE_STAGE_OCTREE) & 1u;
-    const size_t lk = (size_t)r.n * kMaxLevels * sizeof(int);
-    int st = ORBFE_OK;
-    auto hip = [&](hipError_t e) { if (e != hipSuccess && st == ORBFE_OK) st = ORBFE_ERR_HIP; };
-    if (oct && !fast) {
-        if ((st = h->lk_snap.ensure(lk))) return st;
-        h->prof.run_mask = 1u << ORBFE_STAGE_FAST;
-        hip(hipMemsetAsync(h->level_keys.p, 0, lk, h->stream));
-        if (st == ORBFE_OK) st = h->run(r.n, r.l0, r.kps, r.cap, r.desc, r.nout);
-        hip(hipMemcpyAsync(h->lk_snap.p, h->level_keys.p, lk, hipMemcpyDeviceToDevice, h->stream));
-    }
-    h->prof.run_mask = stage_mask;
-    for (int i = 0; i < reps && st == ORBFE_OK; ++i) {
-        if (fast && !oct) hip(hipMemsetAsync(h->level_keys.p, 0, lk, h->stream));
-        if (oct && !fast) hip(hipMemcpyAsync(h->level_keys.p, h->lk_snap.p, lk, hipMemcpyDeviceToDevice, h->stream));
-        if (st == ORBFE_OK) st = h->run(r.n, r.l0, r.kps, r.cap, r.desc, r.nout);
-    }
-    if (fast != oct) hip(hipMemsetAsync(h->level_keys.p, 0, lk, h->stream));
-    h->prof.run_mask = h->stage_mask;
-    return st;
+    return guarded(h, [&]() {
+        const auto r = h->last_run;
+        // FAST adds its per-level key totals into level_keys and the oct-tree reads and clears them
+        // (0 between calls).  A FAST replay without the oct-tree starts from zero each time; an
+        // oct-tree replay without FAST restores one FAST's totals (recomputed once) before each
+        // launch; both leave the totals at zero, as a full extraction does.
+        const bool fast = (stage_mask >> ORBFE_STAGE_FAST) & 1u, oct = (stage_mask >> ORBFE_STAGE_OCTREE) & 1u;
+        const size_t lk = (size_t)r.n * kMaxLevels * sizeof(int);
+        int st = ORBFE_OK;
+        auto hip = [&](hipError_t e) { if (e != hipSuccess && st == ORBFE_OK) st = ORBFE_ERR_HIP; };
+        if (oct && !fast) {
+            if ((st = h->lk_snap.ensure(lk))) return st;
+            h->prof.run_mask = 1u << ORBFE_STAGE_FAST;
+            hip(hipMemsetAsync(h->level_keys.p, 0, lk, h->stream));
+            if (st == ORBFE_OK) st = h->run(r.n, r.l0, r.kps, r.cap, r.desc, r.nout);
+            hip(hipMemcpyAsync(h->lk_snap.p, h->level_keys.p, lk, hipMemcpyDeviceToDevice, h->stream));
+        }
+        h->prof.run_mask = stage_mask;
+        for (int i = 0; i < reps && st == ORBFE_OK; ++i) {
+            if (fast && !oct) hip(hipMemsetAsync(h->level_keys.p, 0, lk, h->stream));
+            if (oct && !fast) hip(hipMemcpyAsync(h->level_keys.p, h->lk_snap.p, lk, hipMemcpyDeviceToDevice, h->stream));
+            if (st == ORBFE_OK) st = h->run(r.n, r.l0, r.kps, r.cap, r.desc, r.nout);
+        }
+        if (fast != oct) hip(hipMemsetAsync(h->level_keys.p, 0, lk, h->stream));
+        h->prof.run_mask = h->stage_mask;
+        return st;
+    });
 }
 
 int orbfe_set_stage_mask(orbfe_extractor* h, unsigned stage_mask) {
@@ -1431,21 +1408,13 @@ int orbfe_get_blurred_level(orbfe_extractor* h, int frame, int level, uint8_t* o
     // K4 on demand (the default extraction path blurs level 0 and the tail levels inside K5);
     // ORBFE_PROBE_AS_EXTRACTED=1 copies the slab as the extraction left it (the levels
     // ORBFE_PREBLUR's pass made)
-    if (out && !std::getenv("ORBFE_PROBE_AS_EXTRACTED")) {
+    // (read per call: tests set it after creating the handle)
+    if (out && !env_is("ORBFE_PROBE_AS_EXTRACTED")) {
         DeviceGuard dg(h->device);
-        BlurArgs ba;
-        ba.nlevels = g.geo.nlevels;
-        for (int l = 0; l < ba.nlevels; ++l) {
-            ba.w[l] = g.geo.lv[l].w;
-            ba.h[l] = g.geo.lv[l].h;
-            ba.src[l] = h->last_pyr[l];
-            ba.dst[l] = LevelPtr{h->blur.as<uint8_t>() + g.geo.lv[l].off, g.slab, g.geo.lv[l].pitch};
-            ba.simd_xb[l] = h->x86() ? sse2_body_blur(g.geo.lv[l].w) : 0;
-        }
-        ba.frags = h->bslot.as<uint4>();
-        ba.items = reinterpret_cast<const uint32_t*>(h->bslot.as<uint8_t>() + kBlurFragBytes);
-        ba.nitems = (int)g.bitems.size();
-        for (int i = 0; i < 4; ++i) ba.taps[i] = h->tab.taps[i];
+        LevelPtr dst[kMaxLevels];
+        for (int l = 0; l < g.geo.nlevels; ++l)
+            dst[l] = LevelPtr{h->blur.as<uint8_t>() + g.geo.lv[l].off, g.slab, g.geo.lv[l].pitch};
+        const BlurArgs ba = h->blur_args(h->last_pyr, dst);
         if (h->x86())
             hipLaunchKernelGGL(blur_mfma_kernel<true>, dim3(ba.nitems, h->last_n), dim3(256), 0, h->stream, ba);
         else

@@ -980,17 +980,11 @@ static bool fv_ok(int nn, const int32_t* off, const int32_t* feat, int n) {
 }
 
 // ORBFE_ZERO_COPY=0: the vocabulary's host transform copies through device buffers (DMA)
-static bool zero_copy_off() {
-    const char* e = std::getenv("ORBFE_ZERO_COPY");
-    return e && std::strcmp(e, "0") == 0;
-}
+static bool zero_copy_off() { return env_is("ORBFE_ZERO_COPY", "0"); }
 
 // ORBFE_BOW1=0: the host form takes the general two-launch path (bow_search_kernel) instead of
 // the gathered one
-static bool bow1_off() {
-    const char* e = std::getenv("ORBFE_BOW1");
-    return e && std::strcmp(e, "0") == 0;
-}
+static bool bow1_off() { return env_is("ORBFE_BOW1", "0"); }
 
 // The host form's gathered path (bow_search1_kernel, then the orientation filter on the host;
 // inputs validated by the caller).  *done = false: the pair does not fit it (more than kBow1Nodes common nodes or a

@@ -32,6 +32,20 @@
 
 namespace orbfe {
 
+struct Level0Args {
+    const uint8_t* src;    // caller frames (cn bytes per pixel)
+    long long src_fpitch;
+    int src_pitch, cn, c0, c2;   // channels; gray weights of channel 0 and 2 (RGB2Gray<uchar>)
+    bool aligned;          // src rows 4-byte aligned: vector loads
+    const uint8_t* mask;   // NULL or u8 plane per frame
+    long long mask_fpitch;
+    int mask_pitch;
+    const int4* rects;     // NULL or per frame (x0, y0, x1, y1) zeroed rectangle
+    uint8_t* dst;          // pyramid level 0
+    long long dst_fpitch;
+    int dst_pitch, w, h;
+};
+
 // ---------------------------------------------------------------------------------------------
 // constant tables
 __constant__ int8_t c_pattern[1024] = {
@@ -191,6 +205,72 @@ __global__ __launch_bounds__(256) void level0_kernel(Level0Args a) {
         default: level0_row<4>(a, f, y, x); break;
     }
 }
+
+struct ResizeArgs {
+    LevelPtr src, dst;
+    int sw, sh, dw, dh;
+    int tiles_x, lds_pitch;
+    const int* xt;
+    const int* yt;
+    int simd_xb;           // x86 arithmetic: columns [0, simd_xb) use the SSE2 rounding (H5)
+    const uint4* gtab;     // resize_kernel: the level's pyramid_kernel column-group table, or null
+};
+
+// resize2_kernel: levels l and l + 1 in one launch, tiles of level l + 1 (see the kernel)
+struct Resize2Args {
+    LevelPtr src, mid, dst;             // levels l - 1, l, l + 1
+    int sw, mw, dw, dh;                 // widths of l - 1, l, l + 1; rows of l + 1
+    int tiles_x;
+    // per tile: {computed rows first, last, computed columns first, last (4-aligned start)} and
+    // {own rows [y0, y1), own columns [x0, x1)} of level l
+    const int4* tiles;
+    const int* yt_m;                    // level l's y / x tables (rows / columns of l - 1)
+    const int* xt_m;
+    const int* yt_d;                    // level l + 1's (of level l)
+    const int* xt_d;
+    const uint4* gtab_m;                // column-group tables of levels l, l + 1
+    const uint4* gtab_d;
+    int pa, pb, bofs;                   // LDS: level l - 1 rows at 0 (pitch pa), level l at bofs (pb)
+    int xb_m, xb_d;                     // x86 SIMD-body bounds of levels l, l + 1
+};
+
+struct PyrArgs {
+    LevelPtr src;                  // level 0
+    LevelPtr l0_copy;              // base != null: each band also writes its level-0 rows here
+                                   // (src is then the caller's staging copy of the frame)
+    LevelPtr dst[kMaxLevels];      // pyramid levels (index = level; 0 unused)
+    int nlevels;
+    int w[kMaxLevels];             // level widths
+    int lp[kMaxLevels];            // LDS row pitch per level
+    int buf_b, ybuf, ymax;         // LDS offsets: second level buffer, y-table rows (2 x ymax)
+    const int4* bands;             // [band][level] {c0, c1, w0, w1}: rows computed / written
+    const uint4* gtab[kMaxLevels]; // per level >= 1: 3 uint4 per column group
+    const int* yt[kMaxLevels];     // per level >= 1: the resize y table
+    int simd_xb[kMaxLevels];
+};
+
+struct ResizeTailArgs {
+    LevelPtr src;                 // level ts-1
+    int sh;                       // its rows
+    int nt;                       // tail levels ts .. ts+nt-1
+    int buf_b;                    // LDS offset of the second buffer
+    int lp[kMaxLevels + 1];       // LDS row pitch of level ts-1+k (k = 0 .. nt)
+    int dw[kMaxLevels], dh[kMaxLevels];
+    const int* xt[kMaxLevels];
+    const int* yt[kMaxLevels];
+    LevelPtr dst[kMaxLevels];
+    int simd_xb[kMaxLevels];      // per tail level, as ResizeArgs::simd_xb
+};
+
+// pyramid_kernel band plans: LDS per workgroup for large batches (80 KB: two 1024-thread
+// workgroups per CU; ORBFE_PYR_LDS_KB overrides), level-0 rows per band for small ones
+constexpr int kPyrLdsCapKB = 80;
+constexpr int kPyrBlock = 1024;
+constexpr int kPyrSmallRows = 12;
+// band plans whose rows computed exceed the pyramid's by more than this use the per-level
+// kernels instead (large batches: throughput; small ones: latency)
+constexpr double kPyrMaxWork = 1.25, kPyrMaxWorkSmall = 3.0;
+constexpr int kTailMinFrames = 8;   // batches below this skip the one-workgroup-per-frame tail
 
 // ---------------------------------------------------------------------------------------------
 // K1 — one pyramid level from the previous one (App. A.1, scalar FixedPtCast<int,uchar,22>),
@@ -550,7 +630,6 @@ __device__ __forceinline__ int reflect101_1(int p, int len) {  // |overshoot| < 
 // dword LDS reads per source row, two v_alignbyte make the 8-byte window, one v_perm per pixel
 // pairs its two source bytes as u16 and v_dot2 applies (a0, a1) — instead of 4 byte gathers,
 // 2 multiplies and an add per pixel.  Vertical pass and rounding: resize_px, as resize_kernel.
-constexpr int kPyrBlock = kPyrBlockSize;
 #ifndef ORBFE_PYR_ROWS
 #define ORBFE_PYR_ROWS 1  // 2 and 4 measured no faster (profiles/r03/experiments/pyramid.json)
 #endif
@@ -673,8 +752,6 @@ __global__ __launch_bounds__(kPyrBlock) void pyramid_kernel(PyrArgs a) {
         for (; r <= bl.y; r += rps) row_out(r);
     }
 }
-template __global__ void pyramid_kernel<false>(PyrArgs);
-template __global__ void pyramid_kernel<true>(PyrArgs);
 
 
 // Host: pyramid_kernel's per-level column-group tables (3 uint4 per group of 4 output columns:
@@ -821,6 +898,27 @@ __global__ __launch_bounds__(kTailBlock) void resize_tail_kernel(ResizeTailArgs 
         __syncthreads();
     }
 }
+
+struct FastArgs {
+    const CellDesc* cells;
+    int ncells;
+    long long cell_cap_total;
+    int ini_th, min_th;
+    int roi_pitch, roi_rows, cand_max;  // dynamic-LDS carve of fast_kernel
+    int* cell_cnt;         // [frame][cell]
+    uint32_t* cell_keys;   // [frame][cell_cap_total]
+    int* level_keys;       // [frame][kMaxLevels] keys per level (atomic sums; 0 on entry)
+    LevelPtr pyr[kMaxLevels];
+};
+constexpr int kFastPitch = 48;  // fast_kernel<kFastPitch>: ROI pitch known at compile time
+// FAST survivor-list entries per cell (>= 322: a pre-test sweep adds <= 256 entries and a
+// flush keeps <= 66).  512 covers the ~22 % pre-test pass rate of textured cells without a
+// flush and brings the kernel's LDS to ~4.8 KB per wave (32 waves per CU, from ~25)
+#ifndef ORBFE_FAST_LIST
+#define ORBFE_FAST_LIST 512
+#endif
+constexpr int kFastListCap = ORBFE_FAST_LIST;
+static_assert(kFastListCap >= 322, "a FAST list flush must make progress");
 
 // ---------------------------------------------------------------------------------------------
 // K2 — FAST per cell.  S(p) = max(q0, -q1) - 1 where q0 (q1) is the max (min) over the 16
@@ -1249,8 +1347,29 @@ __global__ __launch_bounds__(kFastBlock) void fast_kernel(FastArgs a) {
 #endif
 }
 
-template __global__ void fast_kernel<0>(FastArgs);
-template __global__ void fast_kernel<kFastPitch>(FastArgs);
+
+struct OctArgs {
+    Geo geo;
+    const CellDesc* cells;
+    int ncells;
+    long long cell_cap_total;
+    const int* cell_cnt;
+    const uint32_t* cell_keys;
+    int* level_keys;       // [frame][kMaxLevels] from fast_kernel; reset to 0 after reading
+    uint32_t* keys;        // [frame][key_total] compacted per level
+    int4* act;             // [frame][2 * key_total]: node positions of levels whose keys
+                           // exceed kOctLdsKeys (int per key)
+    uint32_t* oct_out;     // [frame][out_total]
+    int* oct_cnt;          // [frame][nlevels]
+    uint16_t* oct_ord;     // [frame][out_total] or null: each level's keypoints in 32-row bands
+                           // (level-local indices; describe's processing order, not the output's)
+    int ncap_max, sort_cap;
+    int lds_keys;          // keys of a level held in LDS (Plan::Oct::keys)
+};
+#ifndef ORBFE_OCT_BLOCK
+#define ORBFE_OCT_BLOCK 256  // 128: 248K, 256: 254K, 512: 243K, 1024: 220K frames/s (c3)
+#endif
+constexpr int kOctLdsKeys = 4096;  // max oct-tree keys of one level held in LDS (else global)
 
 // ---------------------------------------------------------------------------------------------
 // K3 — DistributeOctTree as a data-parallel emulation of the reference's std::list.
@@ -1267,7 +1386,7 @@ template __global__ void fast_kernel<kFastPitch>(FastArgs);
 // FAST lists stay below ~3,300 keys), so every pass is a sweep of LDS reads and LDS atomics;
 // a level with more keys runs the same code on global arrays.  Final: per node the max
 // response, first (lowest original index) on ties (741-759).
-constexpr int kOctBlock = kOctBlockSize;
+constexpr int kOctBlock = ORBFE_OCT_BLOCK;
 // small batches (the single-frame call): one tree per CU at most, so the level-0 tree's sweeps
 // spread over 16 waves instead of 4
 constexpr int kOctBlockSmall = 1024;
@@ -2003,9 +2122,59 @@ __global__ __launch_bounds__(BLK) void octree_kernel(OctArgs a) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-template __global__ void octree_kernel<kOctBlock>(OctArgs);
-template __global__ void octree_kernel<kOctBlockSmall>(OctArgs);
+struct BlurArgs {
+    int nlevels;
+    int w[kMaxLevels], h[kMaxLevels];
+    int taps[4];
+    LevelPtr src[kMaxLevels];
+    LevelPtr dst[kMaxLevels];
+    int simd_xb[kMaxLevels];  // x86 arithmetic: columns [0, simd_xb) round half to even (H6)
+    const uint32_t* items;     // blur_mfma_kernel: the plan's work list (blur_items)
+    int nitems;
+    const uint4* frags;        // blur_mfma_kernel: constant B fragments (blur_frags)
+};
+
+struct DescArgs {
+    int nlevels, out_total, kps_cap;
+    int wave_stride;  // 0: a wave takes G consecutive slots; W > 0: slots wv, wv + W, ... (W = waves per frame)
+    int out_off[kMaxLevels];
+    float scale[kMaxLevels], size[kMaxLevels];
+    int w[kMaxLevels], h[kMaxLevels];
+    int taps[4];
+    LevelPtr pyr[kMaxLevels];
+    const uint32_t* oct_out;
+    const int* oct_cnt;
+    const uint16_t* oct_ord;  // strided waves: slot -> level-local keypoint (OctArgs::oct_ord), or null
+    orbfe_keypoint* kps;
+    uint8_t* desc;
+    int32_t* n_out;
+    int simd_xb[kMaxLevels];  // as BlurArgs::simd_xb, for the fused per-keypoint blur
+    LevelPtr blur[kMaxLevels];  // blurred levels (K4 output), read by the pre-blurred variant
+    uint32_t pre_mask;          // levels whose blurred plane exists (bit l): windows read from it
+    const uint4* frags;         // the matrix-core window blur: H / V fragments (blur_frags, 128..)
+};
+// constant MFMA fragments: [0, 128) blur_mfma_kernel's, [128, 512) describe's window blur
+constexpr size_t kBlurFragBytes = 512 * 16;
+constexpr int kDescFragOff = 128;  // uint4 index of describe's fragments
+// describe window source: raw window blurred on the VALU (pre_mask levels read blurred
+// windows), every level pre-blurred, or the raw window blurred on the matrix cores
+enum { kWinValu = 0, kWinPre = 1, kWinMfma = 2 };
+#ifndef ORBFE_DESC_BLOCK
+#define ORBFE_DESC_BLOCK 256
+#endif
+// 4 keypoints per describe wave: a frame spreads over twice the waves, so ~3.5 frames are in
+// flight per XCD instead of ~7 and each frame's level windows stay in that XCD's 4 MB L2 —
+// describe traffic 1.70x -> 0.69x of its algorithmic bytes for +2 % kernel time
+// (profiles/r02/experiments/describe_group.json).  With the matrix-core window blur the
+// per-wave setup (slot lookup, IC batches, trig, fragment loads) weighs more: 8 per wave measured
+// best (describe 0.2408 / 0.2357 / 0.246 / 0.253 ms at 4 / 8 / 10 / 12-16;
+// profiles/r03/experiments/describe_mfma.json)
+#ifndef ORBFE_DESC_GROUP
+#define ORBFE_DESC_GROUP 8
+#endif
+constexpr int kDescBlock = ORBFE_DESC_BLOCK;
+constexpr int kDescSmallBatch = 8;  // batches below this use kDescGroupSmall keypoints per wave
+constexpr int kDescGroupSize = ORBFE_DESC_GROUP;  // oct-tree output slots per describe wave
 
 // ---------------------------------------------------------------------------------------------
 // K4 — GaussianBlur(7x7, sigma 2, REFLECT_101), integer path (App. A.2): row pass R = sum k_i I
@@ -2176,8 +2345,6 @@ __global__ __launch_bounds__(256) void blur_mfma_kernel(BlurArgs a) {
         }
     }
 }
-template __global__ void blur_mfma_kernel<false>(BlurArgs);
-template __global__ void blur_mfma_kernel<true>(BlurArgs);
 
 // Host: blur_mfma_kernel's work list — per level, per 96-column group of four 24-px tiles,
 // runs of up to kBlurChunk 26-row bands.  Item bits: 0-3 level, 4-12 column group, 13-21 first
@@ -2238,7 +2405,6 @@ void blur_frags(const int taps[4], uint8_t out[512 * 16]) {
 //      trig costs one wave instruction stream per group instead of one per keypoint;
 //   3. per keypoint, lane k evaluates the rotated pattern pairs k + 64 r (pattern held packed
 //      in 4 registers across the group) and 4 ballots make the 256-bit descriptor.
-constexpr int kDescBlock = kDescBlockSize;
 #ifndef ORBFE_DESC_SKIP
 #define ORBFE_DESC_SKIP 0  // attribution experiments only (wrong descriptors): 1 blur passes,
 #endif                     // 2 IC, 4 samples, 8 window loads, 16 trig
@@ -3108,14 +3274,15 @@ int make_tables(const orbfe_params& p, HostTables& t) {
     return ORBFE_OK;
 }
 
-// Plans every size-dependent table for a w x h input (cached per extractor).
-int plan_geometry(const HostTables& t, int w, int h, Plan& g) {
+// The geometry every stage shares, for a w x h input: level sizes and slab offsets, the FAST
+// cell list, the oct-tree capacities and output offsets, the resize x / y tables.
+static int plan_levels(const HostTables& t, int w, int h, Plan& g) {
     const int L = t.p.nlevels;
     g.w = w;
     g.h = h;
     g.geo.nlevels = L;
     long long slab = 0, keys = 0;
-    int out = 0, ncap_max = 0;
+    int out = 0;
     g.cells.clear();
     g.xtab.clear();
     g.ytab.clear();
@@ -3182,7 +3349,6 @@ int plan_geometry(const HostTables& t, int w, int h, Plan& g) {
         lv.ncap = std::max({lv.nfeat + 4, 4 * lv.nini, 20});
         lv.out_off = out;
         out += lv.ncap;
-        ncap_max = std::max(ncap_max, lv.ncap);
         // resize tables for level l from level l-1 (App. A.1)
         if (l > 0) {
             const LevelGeo& sv = g.geo.lv[l - 1];
@@ -3200,28 +3366,6 @@ int plan_geometry(const HostTables& t, int w, int h, Plan& g) {
                 g.xtab.push_back(std::min(sx + 1, sw - 1));
                 g.xtab.push_back((a0 & 0xffff) | (a1 << 16));
             }
-            {   // LDS footprint of a 128 x 32 resize tile of this level
-                int need_rows = 0, need_w = 0;
-                for (int oy = 0; oy < dh; oy += kRsTH) {
-                    const int ey = std::min(oy + kRsTH, dh) - 1;
-                    auto sy = [&](int dy) { return (int)std::floor((float)((dy + 0.5) * scale_y - 0.5)); };
-                    const int r0 = std::min(std::max(sy(oy), 0), sh - 1), r1 = std::min(std::max(sy(ey) + 1, 0), sh - 1);
-                    need_rows = std::max(need_rows, r1 - r0 + 1);
-                }
-                const size_t xb = g.xtab.size() - 3 * (size_t)dw;
-                for (int ox = 0; ox < dw; ox += kRsTW) {
-                    const int ex = std::min(ox + kRsTW, dw) - 1;
-                    const int a0 = g.xtab[xb + 3 * ox] & ~3, a1 = g.xtab[xb + 3 * ex + 1];
-                    // + 2 dwords: the table path reads 3 dwords from a group's first source dword
-                    need_w = std::max(need_w, ((a1 - a0) >> 2) + 1 + 2);
-                }
-                g.rs_tiles_x[l] = (dw + kRsTW - 1) / kRsTW;
-                g.rs_tiles[l] = g.rs_tiles_x[l] * ((dh + kRsTH - 1) / kRsTH);
-                // 16-byte chunks: the widest tile's dwords rounded up to whole chunks
-                g.rs_pitch[l] = 16 * ((need_w + 3) / 4);
-                g.rs_lds[l] = (size_t)need_rows * g.rs_pitch[l];
-                if (g.rs_lds[l] > 64 * 1024) return ORBFE_ERR_UNSUPPORTED;  // scale factors > ~3
-            }
             g.yoff[l] = (int)g.ytab.size();
             for (int dy = 0; dy < dh; ++dy) {
                 float fy = (float)((dy + 0.5) * scale_y - 0.5);
@@ -3234,29 +3378,63 @@ int plan_geometry(const HostTables& t, int w, int h, Plan& g) {
             }
         }
     }
+    g.geo.key_total = keys;
+    g.geo.out_total = out;
+    g.slab = slab;
     if (w > 4096 || h > 4096) return ORBFE_ERR_UNSUPPORTED;
+    return ORBFE_OK;
+}
+
+// The pyramid's part of the plan, from the level geometry and the x / y tables: resize_kernel's
+// tiles, the tail start, pyramid_kernel's group tables and its two band plans under an LDS cap
+// of lds_cap_kb per workgroup, resize2_kernel's tile plans.
+static int plan_pyramid(Plan& g, int lds_cap_kb) {
+    Plan::Pyr& p = g.pyr;
+    const int L = g.geo.nlevels;
+    for (int l = 1; l < L; ++l) {  // LDS footprint of a 128 x 32 resize tile of this level
+        const int sh = g.geo.lv[l - 1].h, dw = g.geo.lv[l].w, dh = g.geo.lv[l].h;
+        const double scale_y = 1. / ((double)dh / sh);  // as the y table's (plan_levels)
+        int need_rows = 0, need_w = 0;
+        for (int oy = 0; oy < dh; oy += kRsTH) {
+            const int ey = std::min(oy + kRsTH, dh) - 1;
+            auto sy = [&](int dy) { return (int)std::floor((float)((dy + 0.5) * scale_y - 0.5)); };
+            const int r0 = std::min(std::max(sy(oy), 0), sh - 1), r1 = std::min(std::max(sy(ey) + 1, 0), sh - 1);
+            need_rows = std::max(need_rows, r1 - r0 + 1);
+        }
+        const size_t xb = (size_t)g.xoff[l];
+        for (int ox = 0; ox < dw; ox += kRsTW) {
+            const int ex = std::min(ox + kRsTW, dw) - 1;
+            const int a0 = g.xtab[xb + 3 * ox] & ~3, a1 = g.xtab[xb + 3 * ex + 1];
+            // + 2 dwords: the table path reads 3 dwords from a group's first source dword
+            need_w = std::max(need_w, ((a1 - a0) >> 2) + 1 + 2);
+        }
+        p.rs.tiles_x[l] = (dw + kRsTW - 1) / kRsTW;
+        p.rs.tiles[l] = p.rs.tiles_x[l] * ((dh + kRsTH - 1) / kRsTH);
+        // 16-byte chunks: the widest tile's dwords rounded up to whole chunks
+        p.rs.pitch[l] = 16 * ((need_w + 3) / 4);
+        p.rs.lds[l] = (size_t)need_rows * p.rs.pitch[l];
+        if (p.rs.lds[l] > 64 * 1024) return ORBFE_ERR_UNSUPPORTED;  // scale factors > ~3
+    }
     {   // K1b: the longest run of top levels ts..L-1 (ts >= 2) whose two largest LDS images,
         // levels ts-1 and ts (rows padded to dwords), fit the tail kernel's LDS
-        const int L = g.geo.nlevels;
         auto bytes = [&](int l) { return (size_t)g.geo.lv[l].h * (((size_t)g.geo.lv[l].w + 15) & ~(size_t)15); };
-        g.tail_start = L;
+        p.tail_start = L;
         for (int ts = L - 1; ts >= 2; --ts) {
             if (bytes(ts - 1) + bytes(ts) > (size_t)kTailLds || g.geo.lv[ts].h > kTailRows) break;
-            g.tail_start = ts;
+            p.tail_start = ts;
         }
-        if (L - g.tail_start < 2) g.tail_start = L;  // a single level gains nothing
+        if (L - p.tail_start < 2) p.tail_start = L;  // a single level gains nothing
     }
     {   // pyramid_kernel: column-group tables, then two band plans (batches >= kTailMinFrames:
-        // the fewest bands whose LDS fits kPyrLdsCap; single frames / small batches: bands of
+        // the fewest bands whose LDS fits lds_cap_kb; single frames / small batches: bands of
         // ~kPyrSmallRows level-0 rows, for more workgroups)
-        const int L = g.geo.nlevels;
-        g.ptab.clear();
-        g.pyr_ok = L >= 2;
-        for (int l = 1; l < L && g.pyr_ok; ++l) {
-            g.gtab_off[l] = (int)(g.ptab.size() / 4);
-            g.pyr_ok = pyramid_group_table(g.xtab, g.xoff[l], g.geo.lv[l].w, g.ptab);
+        p.tab.clear();
+        p.ok = L >= 2;
+        for (int l = 1; l < L && p.ok; ++l) {
+            p.gtab_off[l] = (int)(p.tab.size() / 4);
+            p.ok = pyramid_group_table(g.xtab, g.xoff[l], g.geo.lv[l].w, p.tab);
         }
-        for (int l = 0; l < L; ++l) g.pyr_lp[l] = ((g.geo.lv[l].w + 15) & ~15) + 16;
+        for (int l = 0; l < L; ++l) p.lp[l] = ((g.geo.lv[l].w + 15) & ~15) + 16;
         double work = 0, own = 0;  // pixels computed by the bands vs the pyramid's
         for (int l = 1; l < L; ++l) own += (double)g.geo.lv[l].w * g.geo.lv[l].h;
         auto plan_bands = [&](int nb, std::vector<int>& bt, size_t& lds, int& bufb, int& ybuf, int& ymax) {
@@ -3287,7 +3465,7 @@ int plan_geometry(const HostTables& t, int w, int h, Plan& g) {
                     e[2] = R(l, b);
                     e[3] = R(l, b + 1);
                     const size_t n = (size_t)std::max(0, c1[l] - c0[l] + 1);
-                    (l & 1 ? B : A) = std::max(l & 1 ? B : A, n * g.pyr_lp[l]);
+                    (l & 1 ? B : A) = std::max(l & 1 ? B : A, n * p.lp[l]);
                     if (l) ymax = std::max(ymax, (int)n);
                     if (l) work += (double)n * g.geo.lv[l].w;
                 }
@@ -3296,35 +3474,34 @@ int plan_geometry(const HostTables& t, int w, int h, Plan& g) {
             ybuf = bufb + (int)((B + 15) & ~(size_t)15);
             lds = (size_t)ybuf + 2 * 3 * (size_t)ymax * sizeof(int);
         };
-        const char* cap_env = std::getenv("ORBFE_PYR_LDS_KB");
-        const size_t cap = (cap_env ? (size_t)std::atoi(cap_env) : (size_t)kPyrLdsCapKB) * 1024;
+        const size_t cap = (size_t)lds_cap_kb * 1024;
         std::vector<int> bt[2];
         const int h0 = g.geo.lv[0].h, htop = g.geo.lv[L - 1].h;
         int nb = 1;
-        for (int which = 0; which < 2 && g.pyr_ok; ++which) {
+        for (int which = 0; which < 2 && p.ok; ++which) {
             nb = which == 0 ? 1 : std::max(1, std::min(std::min(64, htop), h0 / kPyrSmallRows));
             for (;; ++nb) {
-                plan_bands(nb, bt[which], g.pyr_lds[which], g.pyr_bufb[which], g.pyr_ybuf[which], g.pyr_ymax[which]);
-                if (g.pyr_lds[which] <= cap) break;
-                if (nb >= htop) { g.pyr_ok = false; break; }  // no band fits: per-level kernels
+                plan_bands(nb, bt[which], p.lds[which], p.bufb[which], p.ybuf[which], p.ymax[which]);
+                if (p.lds[which] <= cap) break;
+                if (nb >= htop) { p.ok = false; break; }  // no band fits: per-level kernels
             }
-            g.nbands[which] = nb;
+            p.nbands[which] = nb;
             // thin bands recompute too many seam rows: at 1920x1080 the per-level kernels win
             // (c4: 1.11 vs 1.25-1.45 ms per step), at 640x480 the band kernel (0.135 vs 0.17)
-            g.pyr_use[which] = g.pyr_ok && work <= own * (which == 0 ? kPyrMaxWork : kPyrMaxWorkSmall);
+            p.use[which] = p.ok && work <= own * (which == 0 ? kPyrMaxWork : kPyrMaxWorkSmall);
         }
-        if (g.pyr_ok) {
+        if (p.ok) {
             for (int which = 0; which < 2; ++which) {
-                while (g.ptab.size() % 4) g.ptab.push_back(0u);
-                g.band_off[which] = (int)(g.ptab.size() / 4);  // int4 units
-                for (int v : bt[which]) g.ptab.push_back((uint32_t)v);
+                while (p.tab.size() % 4) p.tab.push_back(0u);
+                p.band_off[which] = (int)(p.tab.size() / 4);  // int4 units
+                for (int v : bt[which]) p.tab.push_back((uint32_t)v);
             }
         }
         // resize2_kernel plans: levels (l, l + 1) per launch, tiles of level l + 1.  Level l is
         // partitioned among the tiles by each tile's first source row / column (columns rounded
         // down to whole 4-column groups); a tile computes its own part plus what its level l + 1
         // rows and columns read.
-        for (int l = 1; l + 1 < L && g.pyr_ok; ++l) {
+        for (int l = 1; l + 1 < L && p.ok; ++l) {
             const int mw = g.geo.lv[l].w, mh = g.geo.lv[l].h;
             const int dw = g.geo.lv[l + 1].w, dh = g.geo.lv[l + 1].h;
             const int* xm = &g.xtab[g.xoff[l]];
@@ -3357,49 +3534,72 @@ int plan_geometry(const HostTables& t, int w, int h, Plan& g) {
             const int pa = ((awid + 15) & ~15) + 16, pb = ((bwid + 15) & ~15) + 16;
             const size_t bofs = ((size_t)arows * pa + 15) & ~(size_t)15;
             const size_t lds = bofs + (size_t)brows * pb;
-            g.rs2_ok[l] = lds <= 64 * 1024 && gmax <= 256 && brows <= kR2Rows;
-            if (!g.rs2_ok[l]) continue;
-            g.rs2_tiles_x[l] = ntx;
-            g.rs2_tiles[l] = ntx * nty;
-            g.rs2_pa[l] = pa;
-            g.rs2_pb[l] = pb;
-            g.rs2_bofs[l] = (int)bofs;
-            g.rs2_lds[l] = lds;
-            while (g.ptab.size() % 4) g.ptab.push_back(0u);
-            g.rs2_off[l] = (int)(g.ptab.size() / 4);
-            for (int v : tt) g.ptab.push_back((uint32_t)v);
+            p.rs2.ok[l] = lds <= 64 * 1024 && gmax <= 256 && brows <= kR2Rows;
+            if (!p.rs2.ok[l]) continue;
+            p.rs2.tiles_x[l] = ntx;
+            p.rs2.tiles[l] = ntx * nty;
+            p.rs2.pa[l] = pa;
+            p.rs2.pb[l] = pb;
+            p.rs2.bofs[l] = (int)bofs;
+            p.rs2.lds[l] = lds;
+            while (p.tab.size() % 4) p.tab.push_back(0u);
+            p.rs2.off[l] = (int)(p.tab.size() / 4);
+            for (int v : tt) p.tab.push_back((uint32_t)v);
         }
     }
+    return ORBFE_OK;
+}
+
+// fast_kernel's dynamic LDS for the largest cell ROI of the plan's cell list.
+static int plan_fast(Plan& g) {
+    Plan::Fast& p = g.fast;
     int rmax = 7, cmax = 7;
     for (const CellDesc& c : g.cells) {
         rmax = std::max(rmax, c.y1 - c.y0);
         cmax = std::max(cmax, c.x1 - c.x0);
     }
-    g.roi_rows = rmax;
-    g.roi_pitch = (cmax + 3 + 15) & ~15;  // + alignment shift, 16-byte rows for b128 LDS writes
+    p.roi_rows = rmax;
+    p.roi_pitch = (cmax + 3 + 15) & ~15;  // + alignment shift, 16-byte rows for b128 LDS writes
     // FAST survivor list: every candidate pixel up to kFastListCap, else flushed (fast_kernel)
-    g.cand_max = std::min((rmax - 6) * (cmax - 6), kFastListCap);
+    p.cand_max = std::min((rmax - 6) * (cmax - 6), kFastListCap);
     // ROI + zero-bordered score plane at the ROI pitch + candidate list of u16 ROI offsets
-    if ((long long)rmax * g.roi_pitch >= 65536) return ORBFE_ERR_UNSUPPORTED;
-    g.fast_lds = (size_t)rmax * g.roi_pitch + (((rmax - 4) * g.roi_pitch + 15) & ~15) +
-                 2 * (size_t)g.cand_max + 16 + 128;  // + a trash slot per lane
-    g.geo.key_total = keys;
-    blur_items(g.geo, g.bitems);
-    g.geo.out_total = out;
-    g.slab = slab;
-    g.ncap_max = ncap_max;
+    if ((long long)rmax * p.roi_pitch >= 65536) return ORBFE_ERR_UNSUPPORTED;
+    p.lds = (size_t)rmax * p.roi_pitch + (((rmax - 4) * p.roi_pitch + 15) & ~15) +
+            2 * (size_t)p.cand_max + 16 + 128;  // + a trash slot per lane
+    return ORBFE_OK;
+}
+
+// The oct-tree's part of the plan, from the levels' list capacities.
+static void plan_octree(Plan& g) {
+    Plan::Oct& p = g.oct;
+    const int L = g.geo.nlevels;
+    int nf_max = 0;
+    p.ncap_max = 0;
+    for (int l = 0; l < L; ++l) {
+        p.ncap_max = std::max(p.ncap_max, g.geo.lv[l].ncap);
+        nf_max = std::max(nf_max, g.geo.lv[l].nfeat);
+    }
     // phase-2 sort keys: <= one per node (rank sort), 64 for the one-wave bitonic sort
-    g.sort_cap = std::max(ncap_max, 64);
+    p.sort_cap = std::max(p.ncap_max, 64);
     // LDS-resident keys per level: ~9x the largest level budget covers the FAST lists of
     // textured frames (640x480 @1000: <= 1,900 keys per level of 2,048; 1080p @2000: <= 3,300
     // of 4,096), at most kOctLdsKeys; a level with more runs on global arrays.  At 640x480
     // @1000 the carve is 26.8 KB (six trees per CU; 33.9 KB and four before the u16 node
     // fields and the 10x key capacity)
-    int nf_max = 0;
-    for (int l = 0; l < L; ++l) nf_max = std::max(nf_max, g.geo.lv[l].nfeat);
-    g.oct_keys = std::min(kOctLdsKeys, std::max(1024, (9 * nf_max + 63) & ~63));
-    g.oct_lds = std::max(oct_lds_bytes(true, ncap_max, g.sort_cap, g.oct_keys),
-                         oct_lds_bytes(false, ncap_max, g.sort_cap, g.oct_keys));
+    p.keys = std::min(kOctLdsKeys, std::max(1024, (9 * nf_max + 63) & ~63));
+    p.lds = std::max(oct_lds_bytes(true, p.ncap_max, p.sort_cap, p.keys),
+                     oct_lds_bytes(false, p.ncap_max, p.sort_cap, p.keys));
+}
+
+// Plans every size-dependent table for a w x h input (cached per extractor).  pyr_lds_kb: the
+// LDS cap of pyramid_kernel's band plans (the extractor passes its ORBFE_PYR_LDS_KB).
+int plan_geometry(const HostTables& t, int w, int h, Plan& g, int pyr_lds_kb = kPyrLdsCapKB) {
+    int st;
+    if ((st = plan_levels(t, w, h, g))) return st;
+    if ((st = plan_pyramid(g, pyr_lds_kb))) return st;
+    if ((st = plan_fast(g))) return st;
+    plan_octree(g);
+    blur_items(g.geo, g.bitems);
     return ORBFE_OK;
 }
 

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void upload_scatter_kernel(UpScatter a) {
 // staging memory is reused from call to call.
 struct Staging {
     // ORBFE_ZERO_COPY=0: uploads and downloads as DMA copies (the staging buffer unmapped)
-    bool zero_copy_off = std::getenv("ORBFE_ZERO_COPY") && std::strcmp(std::getenv("ORBFE_ZERO_COPY"), "0") == 0;
+    bool zero_copy_off = env_is("ORBFE_ZERO_COPY", "0");
     hipStream_t stream = nullptr;  // the call's stream
     bool may_wait = false;         // the call may wait on the done word (no profiler events)
     uint8_t* pin = nullptr;
@@ -295,7 +295,7 @@ struct orbfe_matcher {
     // a reference set shared by the whole batch is expanded to FP4 fragments once per call
     // (bf_expand_kernel) instead of by every workgroup: c3 bf_match 0.159 -> 0.148 ms per 512
     // frames (profiles/r04/experiments/bf_pre/); ORBFE_BF_PRE=0: every workgroup expands it
-    bool bf_pre = !(std::getenv("ORBFE_BF_PRE") && std::strcmp(std::getenv("ORBFE_BF_PRE"), "0") == 0);
+    bool bf_pre = env_on("ORBFE_BF_PRE");
     // the shared reference set as FP4 fragments (bf_expand_kernel), one buffer per stream the
     // batch form was called on (calls on different streams may overlap), at most kBfStreams of
     // them.  Each buffer carries an event recorded behind the last launch that reads it; a call
@@ -818,8 +818,7 @@ orbfe_matcher* orbfe_matcher_create(int device, int* status) {
             DeviceGuard dg(device);
             m = new orbfe_matcher();
             m->device = device;
-            const char* i8 = std::getenv("ORBFE_BF_I8");
-            if (i8 && i8[0] == '1') m->bf_kernel = bf_match_kernel;
+            if (env_is("ORBFE_BF_I8", "1")) m->bf_kernel = bf_match_kernel;
             if (hipStreamCreateWithFlags(&m->own, hipStreamNonBlocking) != hipSuccess) st = ORBFE_ERR_HIP;
             m->stream = m->own;
         } catch (...) {
@@ -1362,7 +1361,7 @@ int orbfe_search_by_projection_local_device(orbfe_matcher* m, float nnratio,
         // fast path (sbp_local_fast on the resident isInFrustum outputs; the scale factors go
         // as kernel arguments), else / on its rerun the CSR path
         if (frame->n <= kSbpFixKp && frame->nlevels <= kMaxLevels && M > 0 && !m->rerun.no_fixed &&
-            !std::getenv("ORBFE_SBP_DEVICE_CSR"))
+            !env_is("ORBFE_SBP_DEVICE_CSR"))
             st = sbp_local_fast<true>(m, frame, FrustumArgs{}, mp, nnratio, th, d_mps->n_obs,
                                       d_mp_ids, d_frame_mp, d_frame_mp_obs, res);
         else
