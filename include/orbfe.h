@@ -304,6 +304,50 @@ int orbfe_compute_stereo_matches_device(orbfe_extractor* left, orbfe_extractor* 
 /* Synchronizes left's stream; ORBFE_OK or ORBFE_ERR_UNSUPPORTED for the last stereo call. */
 int orbfe_stereo_status(orbfe_extractor* left);
 
+/* ---- RGB-D ------------------------------------------------------------------------------- */
+
+/* The two depth image types Tracking::GrabImageRGBD is fed (Tracking.cc:345-368). */
+#define ORBFE_DEPTH_U16 0   /* CV_16UC1                                                        */
+#define ORBFE_DEPTH_F32 1   /* CV_32FC1                                                        */
+
+/* Frame::ComputeStereoFromRGBD (Frame.cc:759-780) with the depth conversion in front of it
+ * (imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor), Tracking.cc:367-368) fused: `depth` is
+ * the raw w x hgt plane (rows `stride` bytes apart), depth_factor = mDepthMapFactor after
+ * Tracking.cc:236-240.  Only the n pixels under the keypoints are read and scaled; the converted
+ * plane is never made.  keys = mvKeys (distorted, as extracted: the lookup position, truncated
+ * toward zero, row = y, column = x); keys_un = mvKeysUn (its x gives mvuRight = x - bf / d), or
+ * NULL for mvKeysUn = mvKeys (the k1 == 0 branch of Frame::UndistortKeyPoints).  bf = mbf.
+ * Writes mvuRight / mvDepth (n floats each; -1 where d > 0 fails).  A keypoint whose row or
+ * column lies outside the image (or is NaN) reads out of bounds in the reference: it gets
+ * -1 / -1, every other keypoint its values, and the call returns ORBFE_ERR_UNSUPPORTED.
+ * When `depth` is the buffer of the depth-buffer call below, the kernel gathers from it in
+ * place; any other pointer is copied in first.  Synchronous on h's stream. */
+int orbfe_compute_stereo_from_rgbd(orbfe_extractor* h, const void* depth, int depth_type, int w,
+                                   int hgt, size_t stride, float depth_factor,
+                                   const orbfe_keypoint* keys, const orbfe_keypoint* keys_un,
+                                   int n, float bf, float* u_right, float* depth_out);
+
+/* The depth twin of the input buffer: device-mapped pinned memory of hgt rows, *stride bytes
+ * apart, that the caller's grabber writes the raw depth plane into.  It stays valid until a
+ * larger one is asked for or the handle is destroyed. */
+int orbfe_depth_buffer(orbfe_extractor* h, int w, int hgt, int depth_type, void** buf,
+                       size_t* stride);
+
+/* Device-resident batch form over the keypoint / count slabs the batch extractions write
+ * (kps_cap keypoints per frame, d_n[f] of them valid): d_depth holds n_frames raw planes
+ * frame_pitch bytes apart; d_keys_un may be NULL; d_u_right / d_depth_out are n_frames x kps_cap
+ * floats, slots at and past d_n[f] are left alone.  Asynchronous on h's stream; the status call
+ * below reports out-of-image keypoints afterwards. */
+int orbfe_compute_stereo_from_rgbd_device(orbfe_extractor* h, int n_frames, const void* d_depth,
+                                          int depth_type, int w, int hgt, size_t stride,
+                                          size_t frame_pitch, float depth_factor,
+                                          const orbfe_keypoint* d_keys,
+                                          const orbfe_keypoint* d_keys_un, const int32_t* d_n,
+                                          int kps_cap, float bf, float* d_u_right,
+                                          float* d_depth_out);
+/* Synchronizes h's stream; ORBFE_OK or ORBFE_ERR_UNSUPPORTED for the last RGB-D call. */
+int orbfe_rgbd_status(orbfe_extractor* h);
+
 /* ---- matchers ------------------------------------------------------------------------------- */
 
 /* Frame data the matchers read.  Mirrors the Frame members the reference matchers touch:
@@ -629,6 +673,55 @@ int orbfe_is_in_frustum(orbfe_matcher* m, int n, const float* xyz, const float* 
                         float max_y, float log_scale_factor, float viewing_cos_limit,
                         uint8_t* in_view, float* proj_x, float* proj_y, float* proj_xr,
                         int32_t* pred_level, float* view_cos);
+
+/* The close-point rule of an RGB-D / stereo frame and Frame::UnprojectStereo (Frame.cc:782-796).
+ * ORBFE_CLOSE_SORTED is the loop Tracking::UpdateLastFrame (Tracking.cc:1059-1111) and
+ * Tracking::CreateNewKeyFrame (Tracking.cc:1333-1392) share: the features with depth > 0 sorted
+ * by (depth, index), visited until one lies beyond th_depth and more than min_points (the
+ * reference's 100) have been visited.  ORBFE_CLOSE_ALL is Tracking::StereoInitialization
+ * (Tracking.cc:764-779): every feature with depth > 0 in index order, all created, has_point
+ * not read. */
+#define ORBFE_CLOSE_SORTED 0
+#define ORBFE_CLOSE_ALL    1
+/* Most features with depth > 0 one frame may hold. */
+#define ORBFE_CLOSE_MAX_KEPT 8192
+
+/* keys_un = mvKeysUn, depth = mvDepth, has_point[i] = mvpMapPoints[i] && Observations() >= 1
+ * (the fact bCreateNew, Tracking.cc:1086-1092 / 1362-1369, and nMap, 1261-1263, read; may be
+ * NULL with ORBFE_CLOSE_ALL), n features.  cam: fx, fy, cx, cy.  rwc_ow: mRwc row-major (9) then
+ * mOw (3), the products of Frame::UpdatePoseMatrices.  scale_factors = mvScaleFactors (nlevels,
+ * at most 16).
+ * Writes order[0..*n_visited): the feature indices the loop visits, in visiting order;
+ * create[j]: visit j makes a new MapPoint; xyz[3j..]: UnprojectStereo(order[j]) where create[j]
+ * (zeros elsewhere); max_dist[j] / min_dist[j]: mfMaxDistance / mfMinDistance of the Frame-form
+ * MapPoint constructor (MapPoint.cc:298-305) where create[j] (zeros elsewhere; both may be
+ * NULL).  Entries at and past *n_visited are left alone; the arrays hold n entries.
+ * *n_total / *n_map: nTotal / nMap of Tracking::NeedNewKeyFrame (Tracking.cc:1256-1265) over the
+ * whole frame, in either mode.  More than ORBFE_CLOSE_MAX_KEPT features with depth > 0 return
+ * ORBFE_ERR_CAPACITY with nothing written.  A created visit whose octave lies outside
+ * [0, nlevels) indexes mvScaleFactors out of range: its max_dist / min_dist are -1, the other
+ * visits are intact, and the call returns ORBFE_ERR_UNSUPPORTED. */
+int orbfe_close_points(orbfe_matcher* m, int mode, const orbfe_keypoint* keys_un,
+                       const float* depth, const uint8_t* has_point, int n,
+                       const orbfe_camera* cam, const float* rwc_ow, float th_depth,
+                       int min_points, const float* scale_factors, int nlevels, int32_t* order,
+                       int32_t* n_visited, uint8_t* create, float* xyz, float* max_dist,
+                       float* min_dist, int32_t* n_total, int32_t* n_map);
+
+/* Device-resident batch form: n_frames frames in slabs of kps_cap entries (d_n[f] valid), a pose
+ * d_rwc_ow[12 f ..] per frame; the outputs are pitched alike (d_xyz: 3 kps_cap floats per frame)
+ * and stay on the device, d_n_visited / d_n_total / d_n_map / d_status hold one int per frame
+ * (d_status[f]: ORBFE_OK, ORBFE_ERR_CAPACITY or ORBFE_ERR_UNSUPPORTED).  scale_factors is a host
+ * array.  Asynchronous on m's stream. */
+int orbfe_close_points_batch_device(orbfe_matcher* m, int mode, int n_frames,
+                                    const orbfe_keypoint* d_keys_un, const float* d_depth,
+                                    const uint8_t* d_has_point, const int32_t* d_n, int kps_cap,
+                                    const orbfe_camera* cam, const float* d_rwc_ow,
+                                    float th_depth, int min_points, const float* scale_factors,
+                                    int nlevels, int32_t* d_order, int32_t* d_n_visited,
+                                    uint8_t* d_create, float* d_xyz, float* d_max_dist,
+                                    float* d_min_dist, int32_t* d_n_total, int32_t* d_n_map,
+                                    int32_t* d_status);
 
 /* ---- bag of words (DBoW2, vendored in the reference as Thirdparty/DBoW2) ----------------- */
 

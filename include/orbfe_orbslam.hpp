@@ -83,6 +83,33 @@ public:
         descriptors.assign(d, d + (size_t)n * 32);
     }
 
+    // Frame::ComputeStereoFromRGBD (Frame.cc:759-780) on the raw depth image as the grabber
+    // delivers it (depth_type ORBFE_DEPTH_U16 / ORBFE_DEPTH_F32) with the conversion
+    // imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor) (Tracking.cc:367-368) fused: fills
+    // mvuRight / mvDepth.  mvKeysUn empty: mvKeysUn = mvKeys (Frame::UndistortKeyPoints with
+    // k1 == 0).  A keypoint outside the depth image gets -1 / -1 and the call throws
+    // ORBFE_ERR_UNSUPPORTED after filling the others.
+    void ComputeStereoFromRGBD(const void* imDepth, int depth_type, int cols, int rows, size_t step,
+                               float depthMapFactor, const std::vector<orbfe_keypoint>& mvKeys,
+                               const std::vector<orbfe_keypoint>& mvKeysUn, float mbf,
+                               std::vector<float>& mvuRight, std::vector<float>& mvDepth) {
+        if (!mvKeysUn.empty() && mvKeysUn.size() != mvKeys.size())
+            throw Error("ORBextractor::ComputeStereoFromRGBD", ORBFE_ERR_ARG);
+        mvuRight.assign(mvKeys.size(), -1.f);  // 761-762
+        mvDepth.assign(mvKeys.size(), -1.f);
+        check("orbfe_compute_stereo_from_rgbd",
+              orbfe_compute_stereo_from_rgbd(h_, imDepth, depth_type, cols, rows, step, depthMapFactor,
+                                             mvKeys.data(), mvKeysUn.empty() ? nullptr : mvKeysUn.data(),
+                                             (int)mvKeys.size(), mbf, mvuRight.data(), mvDepth.data()));
+    }
+    // The depth twin of InputBuffer: the grabber writes the raw depth image into it and
+    // ComputeStereoFromRGBD, given this pointer, gathers from it in place.
+    void* DepthBuffer(int cols, int rows, int depth_type, size_t* step) {
+        void* buf = nullptr;
+        check("orbfe_depth_buffer", orbfe_depth_buffer(h_, cols, rows, depth_type, &buf, step));
+        return buf;
+    }
+
     int GetLevels() { return orbfe_get_levels(h_); }
     float GetScaleFactor() { return orbfe_get_scale_factor(h_); }
     std::vector<float> GetScaleFactors() { return table(0); }
@@ -195,6 +222,17 @@ struct KeyFramePoints {
 // Rows 0-2 of the 4x4 Sim3 matrix Scw = [s R | t] (row-major 3x4), LoopClosing's corrected pose.
 struct Sim3 {
     float m[12];
+};
+
+// What the close-point loops of Tracking visit (ORBmatcher::ClosePoints): visit j is feature
+// order[j]; where create[j], a new MapPoint goes to xyz[3 j ..] with mfMaxDistance / mfMinDistance
+// max_dist[j] / min_dist[j].  n_total / n_map: nTotal / nMap of Tracking::NeedNewKeyFrame.
+struct ClosePointsResult {
+    std::vector<int> order;
+    std::vector<uint8_t> create;
+    std::vector<float> xyz, max_dist, min_dist;
+    int n_total = 0, n_map = 0;
+    bool octave_out_of_pyramid = false;  // a created visit indexed mvScaleFactors out of range
 };
 
 // ORB_SLAM2::ORBmatcher hot subset (ORBmatcher.h:38-110) on a gfx950 GPU.
@@ -484,6 +522,47 @@ public:
         for (int i = 0; i < N1; ++i)
             if (sim3_m12_[i] >= 0) vpMatches12[i] = P2.ids[sim3_m12_[i]];
         return n;
+    }
+
+    // The close-point loop of Tracking::UpdateLastFrame (Tracking.cc:1059-1111) and
+    // CreateNewKeyFrame (1333-1392) with mode ORBFE_CLOSE_SORTED, StereoInitialization's
+    // (764-779) with ORBFE_CLOSE_ALL, over F.keys_un / mvDepth, creating with
+    // Frame::UnprojectStereo (Frame.cc:782-796).  F.map_points / F.map_point_obs give
+    // "mvpMapPoints[i] && Observations() >= 1" (both empty: no MapPoints).  Rwc (3 x 3 row-major)
+    // and Ow are the products of Frame::UpdatePoseMatrices.  The caller walks the result and does
+    // the `new MapPoint` bookkeeping.
+    ClosePointsResult ClosePoints(int mode, const FrameData& F, const std::vector<float>& mvDepth,
+                                  const orbfe_camera& cam, const float* Rwc, const float* Ow,
+                                  float thDepth, int minPoints = 100) {
+        const size_t N = F.keys_un.size();
+        if (mvDepth.size() != N || !Rwc || !Ow || (!F.map_points.empty() && F.map_points.size() != N) ||
+            (!F.map_points.empty() && F.map_point_obs.size() != N))
+            throw Error("ORBmatcher::ClosePoints", ORBFE_ERR_ARG);
+        std::vector<uint8_t> has_point(N, 0);
+        for (size_t i = 0; i < N && !F.map_points.empty(); ++i)
+            has_point[i] = F.map_points[i] >= 0 && F.map_point_obs[i] >= 1;
+        float pose[12];
+        std::copy(Rwc, Rwc + 9, pose);
+        std::copy(Ow, Ow + 3, pose + 9);
+        ClosePointsResult r;
+        r.order.resize(N);
+        r.create.resize(N);
+        r.xyz.resize(3 * N);
+        r.max_dist.resize(N);
+        r.min_dist.resize(N);
+        int visited = 0;
+        const int st = orbfe_close_points(
+            m_, mode, F.keys_un.data(), mvDepth.data(), has_point.data(), (int)N, &cam, pose, thDepth,
+            minPoints, F.scale_factors.data(), (int)F.scale_factors.size(), r.order.data(), &visited,
+            r.create.data(), r.xyz.data(), r.max_dist.data(), r.min_dist.data(), &r.n_total, &r.n_map);
+        if (st != ORBFE_OK && st != ORBFE_ERR_UNSUPPORTED) throw Error("orbfe_close_points", st);
+        r.octave_out_of_pyramid = st == ORBFE_ERR_UNSUPPORTED;
+        r.order.resize(visited);
+        r.create.resize(visited);
+        r.xyz.resize(3 * (size_t)visited);
+        r.max_dist.resize(visited);
+        r.min_dist.resize(visited);
+        return r;
     }
 
     orbfe_matcher* handle() { return m_; }

@@ -201,6 +201,11 @@ struct orbfe_extractor {
     // block (one H2D copy into st_in), the outputs back into it (st_pin)
     Pinned st_pin;
     DevBuf st_in;
+    // RGB-D (orbfe_rgbd.hip): pin_depth is the buffer orbfe_depth_buffer hands out (reallocated
+    // only by a larger request); rg_pin stages a foreign depth plane, the keypoints and the
+    // outputs of the host form; rg_depth / rg_in / rg_out are their device sides
+    Pinned pin_depth, rg_pin;
+    DevBuf rg_depth, rg_in, rg_out, rg_status;
     // Every buffer the capture embeds is either in g1_key (outputs, pinned staging) or is a
     // plan / workspace buffer: set_plan and a growing ensure_frames drop the graphs.  One graph
     // per input source ([0] copy staging, [1] the handed-out buffer), so callers alternating the
@@ -776,10 +781,10 @@ struct orbfe_extractor {
     ~orbfe_extractor() {
         for (DevBuf* b : {&cells, &xtab, &ytab, &bslot, &ptab, &pyr, &blur, &cell_cnt, &cell_keys, &keys, &act,
                           &oct_out, &oct_cnt, &oct_ord, &level_keys, &lk_snap, &out_kps, &out_desc, &out_n, &stage, &rects, &st_off, &st_items,
-                          &st_sad, &st_status, &st_ur})
+                          &st_sad, &st_status, &st_ur, &rg_depth, &rg_in, &rg_out, &rg_status})
             b->release();
         drop_graph();
-        for (Pinned* q : {&pin_in, &pin_user, &pin_kps, &pin_desc, &pin_n, &st_pin}) q->release();
+        for (Pinned* q : {&pin_in, &pin_user, &pin_kps, &pin_desc, &pin_n, &st_pin, &pin_depth, &rg_pin}) q->release();
         st_in.release();
         prof.release();
         if (own) hipStreamDestroy(own);

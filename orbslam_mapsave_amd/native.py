@@ -2,14 +2,17 @@
 reference interface for the hot path:
 
 * :class:`ORBextractor` mirrors ``ORB_SLAM2::ORBextractor`` (include/ORBextractor.h:50-119):
-  same ctor arguments, ``__call__(image, mask)`` for ``operator()`` and the six getters;
+  same ctor arguments, ``__call__(image, mask)`` for ``operator()`` and the six getters; the
+  frame-side steps that read its outputs hang off it too (``ComputeStereoMatches``,
+  ``ComputeStereoFromRGBD`` with ``depth_buffer``);
 * :class:`ORBmatcher` mirrors the hot subset of ``ORB_SLAM2::ORBmatcher``
   (include/ORBmatcher.h:38-110): ``DescriptorDistance``, ``SearchForInitialization`` and the two
   tracking ``SearchByProjection`` overloads, the search of ``Fuse`` (``FuseSearch``,
   ``fuse_search_batch_device``), ``SearchForTriangulation`` (and
   ``search_for_triangulation_batch_device``), the loop-closing matchers
   (``SearchByBoWKeyFrames``, ``SearchBySim3``, ``SearchByProjectionSim3``), plus the brute-force
-  match of config 3.
+  match of config 3 and the close-point rule of the RGB-D / stereo tracking loops
+  (``ClosePoints``).
 
 There is no CPU fallback: importing works anywhere, but constructing an extractor or matcher
 needs the built library and a gfx950 device, and raises otherwise.
@@ -66,7 +69,22 @@ EXPORTED = [
     "orbfe_archive_mat_bytes",
     "orbfe_archive_write_keypoints_device", "orbfe_archive_read_keypoints_device",
     "orbfe_archive_write_descriptors_device", "orbfe_archive_read_descriptors_device",
+    "orbfe_compute_stereo_from_rgbd", "orbfe_depth_buffer",
+    "orbfe_compute_stereo_from_rgbd_device", "orbfe_rgbd_status",
+    "orbfe_close_points", "orbfe_close_points_batch_device",
 ]
+
+DEPTH_U16, DEPTH_F32 = 0, 1            # ORBFE_DEPTH_*
+CLOSE_SORTED, CLOSE_ALL = 0, 1         # ORBFE_CLOSE_*
+CLOSE_MAX_KEPT = 8192                  # ORBFE_CLOSE_MAX_KEPT
+_DEPTH_DTYPES = {DEPTH_U16: np.dtype(np.uint16), DEPTH_F32: np.dtype(np.float32)}
+
+
+def _depth_type(dtype) -> int:
+    for t, d in _DEPTH_DTYPES.items():
+        if np.dtype(dtype) == d:
+            return t
+    raise ValueError(f"depth images are uint16 or float32, not {dtype}")
 
 
 def lib() -> C.CDLL:
@@ -125,6 +143,17 @@ def lib() -> C.CDLL:
             L.orbfe_archive_read_keypoints_device.argtypes = [i, vp, sz, vp, i, vp, sz, vp]
             L.orbfe_archive_write_descriptors_device.argtypes = [i, vp, sz, vp, i, i, vp, sz, vp, vp]
             L.orbfe_archive_read_descriptors_device.argtypes = [i, vp, sz, i, vp, sz, vp, vp, vp]
+        if hasattr(L, "orbfe_close_points"):
+            sz, vp, i, f = C.c_size_t, C.c_void_p, C.c_int, C.c_float
+            L.orbfe_compute_stereo_from_rgbd.argtypes = [vp, vp, i, i, i, sz, f, vp, vp, i, f, vp, vp]
+            L.orbfe_depth_buffer.argtypes = [vp, i, i, i, vp, vp]
+            L.orbfe_compute_stereo_from_rgbd_device.argtypes = [vp, i, vp, i, i, i, sz, sz, f, vp,
+                                                                vp, vp, i, f, vp, vp]
+            L.orbfe_rgbd_status.argtypes = [vp]
+            L.orbfe_close_points.argtypes = [vp, i, vp, vp, vp, i, vp, vp, f, i, vp, i, vp, vp, vp,
+                                             vp, vp, vp, vp, vp]
+            L.orbfe_close_points_batch_device.argtypes = [vp, i, i, vp, vp, vp, vp, i, vp, vp, f, i,
+                                                          vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -391,6 +420,54 @@ class ORBextractor:
 
     def stereo_status(self) -> None:
         _check("orbfe_stereo_status", lib().orbfe_stereo_status(self._h))
+
+    def depth_buffer(self, w: int, h: int, dtype=np.uint16) -> np.ndarray:
+        """The handle's pinned depth buffer as a writable (h, w) view of `dtype` (uint16 or
+        float32; orbfe_depth_buffer): the grabber writes the raw depth image into it and
+        :meth:`ComputeStereoFromRGBD`, given this array, gathers from it in place."""
+        t = _depth_type(dtype)
+        buf = C.c_void_p()
+        stride = C.c_size_t(0)
+        _check("orbfe_depth_buffer", lib().orbfe_depth_buffer(self._h, w, h, t, C.byref(buf),
+                                                              C.byref(stride)))
+        raw = (C.c_uint8 * (h * stride.value)).from_address(buf.value)
+        return np.frombuffer(raw, _DEPTH_DTYPES[t]).reshape(h, -1)[:, :w]
+
+    def ComputeStereoFromRGBD(self, imDepth: np.ndarray, depth_factor: float, keys: np.ndarray,
+                              bf: float, keys_un: np.ndarray | None = None, results: bool = False):
+        """Frame::ComputeStereoFromRGBD (Frame.cc:759-780) on the raw depth image (uint16 or
+        float32, rows may be padded) with ``convertTo(CV_32F, depth_factor)`` (Tracking.cc:368)
+        fused.  keys = mvKeys, keys_un = mvKeysUn (None: the same).  Returns (mvuRight, mvDepth);
+        with results=True an out-of-image keypoint does not raise and the status comes third."""
+        t = _depth_type(imDepth.dtype)
+        assert imDepth.ndim == 2 and imDepth.strides[1] == imDepth.itemsize and imDepth.strides[0] > 0
+        h, w = imDepth.shape
+        keys = np.ascontiguousarray(keys, KEYPOINT_DTYPE)
+        ku = None if keys_un is None else np.ascontiguousarray(keys_un, KEYPOINT_DTYPE)
+        assert ku is None or len(ku) == len(keys)
+        ur = np.full(len(keys), -1, np.float32)
+        dp = np.full(len(keys), -1, np.float32)
+        st = lib().orbfe_compute_stereo_from_rgbd(
+            self._h, imDepth.ctypes.data, t, w, h, imDepth.strides[0], depth_factor, ptr(keys),
+            ptr(ku), len(keys), bf, ptr(ur), ptr(dp))
+        if results and st in (ORBFE_OK, ORBFE_ERR_UNSUPPORTED):
+            return ur, dp, st
+        _check("orbfe_compute_stereo_from_rgbd", st)
+        return ur, dp
+
+    def compute_stereo_from_rgbd_device(self, n_frames: int, d_depth: int, depth_type: int, w: int,
+                                        h: int, stride: int, frame_pitch: int,
+                                        depth_factor: float, d_keys: int, d_n: int, kps_cap: int,
+                                        bf: float, d_ur: int, d_dp: int,
+                                        d_keys_un: int | None = None) -> None:
+        """Batched device form (orbfe_compute_stereo_from_rgbd_device) over the slabs
+        :meth:`extract_batch_device` writes; async, :meth:`rgbd_status` reports afterwards."""
+        _check("orbfe_compute_stereo_from_rgbd_device", lib().orbfe_compute_stereo_from_rgbd_device(
+            self._h, n_frames, d_depth, depth_type, w, h, stride, frame_pitch, depth_factor,
+            d_keys, d_keys_un, d_n, kps_cap, bf, d_ur, d_dp))
+
+    def rgbd_status(self) -> None:
+        _check("orbfe_rgbd_status", lib().orbfe_rgbd_status(self._h))
 
     def extract_batch(self, images: np.ndarray, masks: np.ndarray | None = None):
         """Host batch: (n, h, w) uint8 -> (kps (n, cap), desc (n, cap, 32), counts (n,))."""
@@ -1292,3 +1369,58 @@ class ORBmatcher:
             *(C.c_float(b) for b in bounds), C.c_float(log_scale), C.c_float(cos_limit),
             ptr(inv), ptr(px), ptr(py), ptr(pxr), ptr(pl), ptr(vc)))
         return inv, px, py, pxr, pl, vc
+
+    def ClosePoints(self, mode: int, keys_un, depth, has_point, cam: Camera, rwc_ow,
+                    th_depth: float, scale_factors=None, min_points: int = 100, out=None,
+                    results: bool = False):
+        """The close-point rule over mvDepth with Frame::UnprojectStereo (orbfe_close_points):
+        mode CLOSE_SORTED is the loop of Tracking::UpdateLastFrame / CreateNewKeyFrame
+        (Tracking.cc:1059-1111, 1333-1392), CLOSE_ALL is StereoInitialization (764-779).
+        has_point[i] = mvpMapPoints[i] && Observations() >= 1; rwc_ow = mRwc (row-major) then
+        mOw.  scale_factors None leaves the MapPoint distances out.  Returns a dict: order,
+        create, xyz (n_visited rows), max_dist / min_dist (or None), n_visited, n_total, n_map,
+        status.  out: the five arrays (order i32, create u8, xyz f32 (n, 3), max_dist, min_dist
+        f32) to write into; the call touches only their first n_visited entries."""
+        keys_un = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE)
+        n = len(keys_un)
+        depth = np.ascontiguousarray(depth, np.float32)
+        hp = None if has_point is None else np.ascontiguousarray(has_point, np.uint8)
+        assert len(depth) == n and (hp is None or len(hp) == n)
+        pose = np.ascontiguousarray(rwc_ow, np.float32).reshape(12)
+        sf = None if scale_factors is None else np.ascontiguousarray(scale_factors, np.float32)
+        if out is not None:
+            order, create, xyz, mx, mn = out
+        else:
+            order = np.zeros(n, np.int32)
+            create = np.zeros(n, np.uint8)
+            xyz = np.zeros((n, 3), np.float32)
+            mx = None if sf is None else np.zeros(n, np.float32)
+            mn = None if sf is None else np.zeros(n, np.float32)
+        cnt = np.zeros(3, np.int32)
+        st = lib().orbfe_close_points(
+            self._h, mode, ptr(keys_un), ptr(depth), ptr(hp), n, C.addressof(cam), ptr(pose),
+            th_depth, min_points, ptr(sf), 0 if sf is None else len(sf), ptr(order),
+            cnt[0:].ctypes.data, ptr(create), ptr(xyz), ptr(mx), ptr(mn), cnt[1:].ctypes.data,
+            cnt[2:].ctypes.data)
+        if not (results and st in (ORBFE_ERR_UNSUPPORTED, ORBFE_ERR_CAPACITY)):
+            _check("orbfe_close_points", st)
+        v = int(cnt[0])
+        return {"order": order[:v], "create": create[:v], "xyz": xyz[:v],
+                "max_dist": None if mx is None else mx[:v],
+                "min_dist": None if mn is None else mn[:v], "n_visited": v,
+                "n_total": int(cnt[1]), "n_map": int(cnt[2]), "status": st}
+
+    def close_points_batch_device(self, mode: int, n_frames: int, d_keys_un: int, d_depth: int,
+                                  d_has_point: int | None, d_n: int, kps_cap: int, cam: Camera,
+                                  d_rwc_ow: int, th_depth: float, min_points: int, scale_factors,
+                                  d_order: int, d_n_visited: int, d_create: int, d_xyz: int,
+                                  d_max_dist: int | None, d_min_dist: int | None, d_n_total: int,
+                                  d_n_map: int, d_status: int) -> None:
+        """Batched device form (orbfe_close_points_batch_device): slabs of kps_cap entries per
+        frame, a pose per frame, outputs left on the device; async."""
+        sf = None if scale_factors is None else np.ascontiguousarray(scale_factors, np.float32)
+        _check("orbfe_close_points_batch_device", lib().orbfe_close_points_batch_device(
+            self._h, mode, n_frames, d_keys_un, d_depth, d_has_point, d_n, kps_cap,
+            C.addressof(cam), d_rwc_ow, th_depth, min_points, ptr(sf),
+            0 if sf is None else len(sf), d_order, d_n_visited, d_create, d_xyz, d_max_dist,
+            d_min_dist, d_n_total, d_n_map, d_status))

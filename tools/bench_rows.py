@@ -803,11 +803,116 @@ def row_kfdb(tmpdir):
     gv.close()
 
 
+def row_rgbd():
+    """Frame::ComputeStereoFromRGBD at 640 x 480, ~1000 keypoints per frame: the device batch over
+    the slabs the batch extraction wrote, the single-frame host form from the staged depth buffer
+    and from a foreign pointer, and the host round trip they replace (D2H of the keypoint slab,
+    the lookup in numpy, H2D of mvuRight / mvDepth), which needs nothing of this library but the
+    extraction and so runs the same on a build without the RGB-D calls; then the close points."""
+    W, H, B = 640, 480, 64
+    ex = native.ORBextractor(1000, 1.2, 8, 20, 7, device=0, max_width=W, max_height=H, max_batch=B)
+    cap = ex.capacity(W, H)
+    imgs = np.stack([synthetic_frame(70 + f % 8, W, H) for f in range(B)])
+    r = np.random.default_rng(1)
+    depth = r.integers(300, 30000, (B, H, W)).astype(np.uint16)
+    depth[r.random(depth.shape) < 0.1] = 0
+    factor, bf = np.float32(1.0) / np.float32(5000.0), np.float32(40.0)
+    d_img = torch.from_numpy(imgs).to(DEV)
+    d_depth = torch.from_numpy(depth.view(np.uint8)).to(DEV)
+    d_k = torch.zeros((B, cap * 28), dtype=torch.uint8, device=DEV)
+    d_d = torch.zeros((B, cap, 32), dtype=torch.uint8, device=DEV)
+    d_n = torch.zeros(B, dtype=torch.int32, device=DEV)
+    d_ur = torch.zeros((B, cap), dtype=torch.float32, device=DEV)
+    d_dp = torch.zeros((B, cap), dtype=torch.float32, device=DEV)
+    torch.cuda.synchronize()
+    ex.extract_batch_device(d_img.data_ptr(), B, W, H, W, W * H, d_k.data_ptr(), cap, d_d.data_ptr(),
+                            d_n.data_ptr())
+    ex.synchronize()
+    cnt = d_n.cpu().numpy()
+    nkp = float(cnt.mean())
+
+    def roundtrip(nf):
+        k = d_k[:nf].cpu().numpy().view(native.KEYPOINT_DTYPE).reshape(nf, cap)
+        c = d_n[:nf].cpu().numpy()
+        ur = np.full((nf, cap), -1, np.float32)
+        dp = np.full((nf, cap), -1, np.float32)
+        for f in range(nf):
+            m = int(c[f])
+            d = depth[f][k[f, :m]["y"].astype(np.int32), k[f, :m]["x"].astype(np.int32)].astype(np.float32) * factor
+            ok = d > 0
+            dp[f, :m][ok] = d[ok]
+            ur[f, :m][ok] = k[f, :m]["x"][ok] - bf / d[ok]
+        d_ur[:nf].copy_(torch.from_numpy(ur))
+        d_dp[:nf].copy_(torch.from_numpy(dp))
+
+    shape = f"{W}x{H}, {nkp:.0f} keypoints per frame"
+    t = timed(lambda: roundtrip(B), 10)
+    jrow("rgbd_roundtrip_batch", "frames/s", B, t,
+         f"host round trip, {B} frames ({shape}): D2H keypoint slabs + counts, numpy lookup, H2D mvuRight + mvDepth")
+    t = timed(lambda: roundtrip(1), 200)
+    jrow("rgbd_roundtrip_single", "frames/s", 1, t, f"host round trip, one frame ({shape})")
+    if not hasattr(ex, "compute_stereo_from_rgbd_device"):
+        ex.close()
+        return
+    ref = (d_ur.cpu().numpy().copy(), d_dp.cpu().numpy().copy())
+
+    def dev():
+        ex.compute_stereo_from_rgbd_device(B, d_depth.data_ptr(), native.DEPTH_U16, W, H, 2 * W, 2 * W * H,
+                                           float(factor), d_k.data_ptr(), d_n.data_ptr(), cap, float(bf),
+                                           d_ur.data_ptr(), d_dp.data_ptr())
+    t = timed(dev, 200)
+    ex.rgbd_status()
+    got = (d_ur.cpu().numpy(), d_dp.cpu().numpy())
+    same = all(np.array_equal(g[f, :cnt[f]], w[f, :cnt[f]]) for g, w in zip(got, ref) for f in range(B))
+    jrow("rgbd_device_batch", "frames/s", B, t,
+         f"orbfe_compute_stereo_from_rgbd_device, {B} frames ({shape}), slabs as the extraction wrote them",
+         equals_roundtrip=bool(same))
+    keys = d_k[0].cpu().numpy().view(native.KEYPOINT_DTYPE)[:cnt[0]].copy()
+    buf = ex.depth_buffer(W, H, np.uint16)
+    buf[:] = depth[0]
+    t = timed(lambda: ex.ComputeStereoFromRGBD(buf, float(factor), keys, float(bf)), 500)
+    jrow("rgbd_host_staged", "frames/s", 1, t, f"host form, depth in the handle's buffer, gathered in place ({shape})")
+    t = timed(lambda: ex.ComputeStereoFromRGBD(depth[0], float(factor), keys, float(bf)), 200)
+    jrow("rgbd_host_foreign", "frames/s", 1, t, f"host form, foreign depth pointer staged first ({shape})")
+    # the close points of UpdateLastFrame over the same frames
+    mt = native.ORBmatcher(0.9, True, device=0)
+    cam = native.Camera(517.3, 516.5, 318.6, 255.3, float(bf), float(bf) / 517.3)
+    pose = torch.from_numpy(np.tile(np.asarray([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], np.float32), (B, 1))).to(DEV)
+    d_hp = torch.from_numpy((r.random((B, cap)) < 0.4).astype(np.uint8)).to(DEV)
+    o_i = torch.zeros((B, cap), dtype=torch.int32, device=DEV)
+    o_c = torch.zeros((B, cap), dtype=torch.uint8, device=DEV)
+    o_x = torch.zeros((B, cap, 3), dtype=torch.float32, device=DEV)
+    o_f = torch.zeros((2, B, cap), dtype=torch.float32, device=DEV)
+    o_n = torch.zeros((4, B), dtype=torch.int32, device=DEV)
+    sf = ex.GetScaleFactors()
+    torch.cuda.synchronize()
+
+    def close():
+        mt.close_points_batch_device(native.CLOSE_SORTED, B, d_k.data_ptr(), d_dp.data_ptr(), d_hp.data_ptr(),
+                                     d_n.data_ptr(), cap, cam, pose.data_ptr(), 3.09, 100, sf,
+                                     o_i.data_ptr(), o_n[0].data_ptr(), o_c.data_ptr(), o_x.data_ptr(),
+                                     o_f[0].data_ptr(), o_f[1].data_ptr(), o_n[1].data_ptr(),
+                                     o_n[2].data_ptr(), o_n[3].data_ptr())
+    t = timed(close, 200)
+    res = o_n.cpu().numpy()
+    jrow("close_points_device_batch", "frames/s", B, t,
+         f"orbfe_close_points_batch_device, sorted mode, {B} frames ({shape})",
+         visited_mean=float(res[0].mean()), status_ok=bool((res[3] == 0).all()))
+    hk = keys
+    hz = d_dp[0].cpu().numpy()[:cnt[0]].copy()
+    hh = d_hp[0].cpu().numpy()[:cnt[0]].copy()
+    hp = pose[0].cpu().numpy()
+    t = timed(lambda: mt.ClosePoints(native.CLOSE_SORTED, hk, hz, hh, cam, hp, 3.09, sf), 200)
+    jrow("close_points_host", "frames/s", 1, t, f"orbfe_close_points host form, sorted mode ({shape})")
+    mt.close()
+    ex.close()
+
+
 if __name__ == "__main__":
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         rows = {"single": row_single, "color": row_color, "stereo": row_stereo, "reloc": row_reloc, "fuse": row_fuse, "triangulation": row_triangulation, "track": row_track,
                 "distinctive": row_distinctive, "bow": lambda: row_bow(td),
-                "loop": row_loop, "kfdb": lambda: row_kfdb(td)}
+                "loop": row_loop, "kfdb": lambda: row_kfdb(td), "rgbd": row_rgbd}
         for name in (sys.argv[1:] or list(rows)):
             rows[name]()
