@@ -1036,6 +1036,134 @@ int orbfe_kfdb_detect_relocalization_candidates_device(orbfe_kfdb* db, uint64_t 
                                                        const int32_t* d_nw, int32_t* d_cand,
                                                        int cand_cap, int32_t* n_cand);
 
+/* ---- the local map: Tracking::UpdateLocalMap (Tracking.cc:1455-1599) ----------------------
+ * A handle holds a device-resident mirror of the part of the map graph that
+ * UpdateLocalKeyFrames (:1491-1599) and UpdateLocalPoints (:1465-1488) read.  Keyframes and map
+ * points are dense slots handed out by the handle, in add order from 0.  There is no erase: the
+ * reference never frees a KeyFrame or a MapPoint, it marks them bad; orbfe_map_clear mirrors
+ * Tracking::Reset.  Device storage grows by doubling inside the mutators, never inside a query.
+ * Per keyframe: the order key, the bad flag, mnTrackReferenceForFrame (the stamp), mvpMapPoints
+ * as point slots or -1, GetBestCovisibilityKeyFrames(10), the children (kept sorted by order
+ * key) and the parent.  Per point: the bad flag, mnTrackReferenceForFrame and the set of
+ * observing keyframes.  The handle: mvpLocalKeyFrames and mpReferenceKF (-1 initially).
+ *
+ * Pointer order: the reference iterates map<KeyFrame*, int> and set<KeyFrame*>,
+ * i.e. in the order of heap addresses.  Every keyframe carries a caller-supplied order_key and
+ * "pointer order" is ascending key; with order_key = (uintptr_t)pKF the parity is exact for the
+ * addresses the caller has.  Keys are distinct.
+ * A handle is not reentrant.  The mutators are synchronous. */
+typedef struct orbfe_map orbfe_map;
+
+#define ORBFE_MAP_MAX_VOTED     4096   /* keyframes one call's frame points may vote for        */
+#define ORBFE_MAP_MAX_KF_SLOTS  8192   /* mvpMapPoints of one keyframe                          */
+#define ORBFE_MAP_KEYFRAMES     0      /* `kind` of orbfe_map_set_stamps / get_stamps           */
+#define ORBFE_MAP_POINTS        1
+
+orbfe_map* orbfe_map_create(int device, int keyframes_hint, int points_hint, int* status);
+void orbfe_map_destroy(orbfe_map* m);
+int  orbfe_map_set_stream(orbfe_map* m, void* hip_stream);
+/* Tracking::Reset: no keyframes, no points, an empty list, reference keyframe -1.  Slots start
+ * again from 0; the device storage is kept. */
+int  orbfe_map_clear(orbfe_map* m);
+int  orbfe_map_size(const orbfe_map* m, int32_t* n_keyframes, int32_t* n_points);
+
+/* A new keyframe of n_slots <= 8192 keypoints: mp_slots[i] = the point held by keypoint i or -1
+ * (NULL: all -1).  Not bad, stamp 0, no neighbours, children or parent.  A key already in the
+ * map, n_slots out of range or a point slot that does not exist return ORBFE_ERR_ARG, as every
+ * out-of-range slot does in every call below. */
+int orbfe_map_add_keyframe(orbfe_map* m, uint64_t order_key, int n_slots, const int32_t* mp_slots,
+                           int32_t* slot);
+/* KeyFrame::AddMapPoint / EraseMapPointMatch / ReplaceMapPointMatch: entries [first, first + n)
+ * of the keyframe's mvpMapPoints. */
+int orbfe_map_set_keyframe_points(orbfe_map* m, int slot, int first, int n, const int32_t* mp_slots);
+/* KeyFrame::SetBadFlag (mbBad). */
+int orbfe_map_set_keyframe_bad(orbfe_map* m, int slot, int bad);
+/* GetBestCovisibilityKeyFrames(10) of the keyframe, in its order: n <= 10 slots; -1 entries keep
+ * their place and are skipped (the contract of orbfe_kfdb_set_covisibility). */
+int orbfe_map_set_covisibility(orbfe_map* m, int slot, int n, const int32_t* neigh_slots);
+/* mspChildrens: the whole set, in any order; the handle sorts it by order key. */
+int orbfe_map_set_children(orbfe_map* m, int slot, int n, const int32_t* child_slots);
+/* mpParent, or -1. */
+int orbfe_map_set_parent(orbfe_map* m, int slot, int parent);
+/* n new points, slots *first_slot .. *first_slot + n - 1: not bad, stamp 0, no observations.
+ * The pointer orbfe_map_local_points_device returned is invalid after this call. */
+int orbfe_map_add_points(orbfe_map* m, int n, int32_t* first_slot);
+/* MapPoint::SetBadFlag / mbBad of n points. */
+int orbfe_map_set_points_bad(orbfe_map* m, int n, const int32_t* mp_slots, int bad);
+/* MapPoint::AddObservation / EraseObservation, batched: point mp_slots[i] is (no longer) observed
+ * by keyframe kf_slots[i].  Set semantics: a pair that is already (not) there is a no-op
+ * (MapPoint.cc:170-171). */
+int orbfe_map_add_observations(orbfe_map* m, int n, const int32_t* mp_slots, const int32_t* kf_slots);
+int orbfe_map_erase_observations(orbfe_map* m, int n, const int32_t* mp_slots, const int32_t* kf_slots);
+/* mnTrackReferenceForFrame of n keyframes (kind ORBFE_MAP_KEYFRAMES) or points (ORBFE_MAP_POINTS):
+ * unsigned long, 0 for a new object, stored in the map archive (KeyFrame.cc:106, MapPoint.cc:80),
+ * hence state with a getter and a setter.  The slots of one set call are distinct. */
+int orbfe_map_set_stamps(orbfe_map* m, int kind, int n, const int32_t* slots, const uint64_t* stamps);
+int orbfe_map_get_stamps(orbfe_map* m, int kind, int n, const int32_t* slots, uint64_t* stamps);
+/* mvpLocalKeyFrames and mpReferenceKF assigned directly (Tracking.cc:789, :969-970): n <= 4104. */
+int orbfe_map_set_local_keyframes(orbfe_map* m, int n, const int32_t* kf_slots, int ref_kf);
+/* The list and the reference keyframe as the last query (or set) left them; host state.  *n > cap:
+ * ORBFE_ERR_CAPACITY. */
+int orbfe_map_get_local_keyframes(const orbfe_map* m, int32_t* kf_slots, int cap, int32_t* n,
+                                  int32_t* ref_kf);
+
+/* Tracking::UpdateLocalMap without the viewer call (:1458): UpdateLocalKeyFrames, then
+ * UpdateLocalPoints, with mCurrentFrame.mnId = frame_id.  frame_mp: inout, n entries, the point
+ * slot held by each frame keypoint or -1 (mCurrentFrame.mvpMapPoints); bad points are set to -1
+ * (:1508).  local_kf receives mvpLocalKeyFrames in order (*n_local_kf entries), *ref_kf
+ * mpReferenceKF, local_mp mvpLocalMapPoints in order (*n_local_mp entries).  Literal details:
+ * bad keyframes are voted for but neither listed, stamped nor eligible as reference; an empty
+ * vote returns early and the previous list and reference keyframe stay, UpdateLocalPoints still
+ * runs over them (:1513); the neighbour loop stops while the list holds more than 80; the
+ * parent is pushed without an isBad test and its break leaves the whole loop (:1588); a second
+ * call with the same frame_id finds the stamps of the first.
+ * A buffer that is too small returns ORBFE_ERR_CAPACITY with the true counts and copies nothing
+ * into that buffer; the handle's state (stamps, list, reference keyframe, device point list) has
+ * advanced as after a successful call, so a retry must not repeat the query: read the list with
+ * orbfe_map_get_local_keyframes / orbfe_map_local_points_device.  More than 4096 voted keyframes
+ * return ORBFE_ERR_CAPACITY with *n_local_kf = their number before any stamp, list or reference
+ * keyframe is written; only the NULLing of bad points in frame_mp (idempotent) has happened.
+ * Five kernel launches; the host waits once, on a done word in pinned memory. */
+int orbfe_map_update_local(orbfe_map* m, uint64_t frame_id, int n, int32_t* frame_mp,
+                           int32_t* local_kf, int kf_cap, int32_t* n_local_kf, int32_t* ref_kf,
+                           int32_t* local_mp, int mp_cap, int32_t* n_local_mp);
+/* The device form: d_frame_mp is the device array orbfe_search_by_projection_* /
+ * orbfe_search_local_points_device update.  The point list stays in device memory
+ * (orbfe_map_local_points_device); the keyframe list (host), *ref_kf and the counts come back
+ * through pinned memory.  An entry of d_frame_mp outside [-1, points) is caught on the device:
+ * ORBFE_ERR_ARG, nothing written but NULLed bad points. */
+int orbfe_map_update_local_device(orbfe_map* m, uint64_t frame_id, int n, int32_t* d_frame_mp,
+                                  int32_t* local_kf, int kf_cap, int32_t* n_local_kf,
+                                  int32_t* ref_kf, int32_t* n_local_mp);
+/* mvpLocalMapPoints of the last successful query as a device array of *n point slots, valid until
+ * the next query or orbfe_map_add_points. */
+int orbfe_map_local_points_device(const orbfe_map* m, const int32_t** d_list, int32_t* n);
+/* The same list copied to the host (*n > cap: ORBFE_ERR_CAPACITY, nothing copied). */
+int orbfe_map_get_local_points(orbfe_map* m, int32_t* mp_slots, int cap, int32_t* n);
+
+/* Device arrays of map-point data: as `src` map-wide, indexed by point slot (mp_ids and bad are
+ * not read: the handle has them); as `dst` contiguous, indexed by list position.  desc is 32
+ * bytes per point and 16-byte aligned.  skip[i] != 0 <=> mnLastFrameSeen == the frame's id and
+ * n_obs = Observations() are the caller's. */
+typedef struct orbfe_map_point_arrays {
+    float*   xyz;        /* n x 3 */
+    float*   normal;     /* n x 3 */
+    float*   min_dist;
+    float*   max_dist;
+    uint8_t* desc;       /* n x 32 */
+    int32_t* n_obs;
+    uint8_t* skip;
+    int32_t* mp_ids;
+    uint8_t* bad;
+} orbfe_map_point_arrays;
+/* The n points of d_list (device; e.g. orbfe_map_local_points_device) gathered in list order:
+ * dst->mp_ids = the list, dst->bad = the handle's bad flags, the rest from src.  These are the
+ * map-point inputs of orbfe_search_local_points_device.  An entry outside the map is written as
+ * a bad point with id -1.  Asynchronous on the handle's stream. */
+int orbfe_map_gather_points_device(orbfe_map* m, int n, const int32_t* d_list,
+                                   const orbfe_map_point_arrays* src,
+                                   const orbfe_map_point_arrays* dst);
+
 /* ---- map-archive records of the extractor outputs (device side) ---------------------------
  * The bodies the reference's Boost map archive stores for the extractor's outputs, written
  * from / read into HBM (MapPoint.h:196-247; KeyFrame::serialize KeyFrame.cc:133-134 / 354-355

@@ -754,4 +754,163 @@ private:
     std::unordered_map<uint64_t, int> slot_;   // mnId -> slot, the keyframes in the database
 };
 
+// Tracking::UpdateLocalMap (Tracking.cc:1455-1599) over the device mirror of the map graph
+// (orbfe_map), keyed by the caller's KeyFrame::mnId and MapPoint::mnId.  The mutators carry the
+// names of the reference methods whose effect they mirror; call them from those methods
+// (INTEGRATION.md §3h).  Every keyframe is added with order_key = (uintptr_t)pKF: the reference
+// iterates map<KeyFrame*, int> and set<KeyFrame*> in address order.
+class LocalMap {
+public:
+    static constexpr uint64_t kNone = ~0ull;  // a NULL MapPoint* / KeyFrame*
+
+    struct Result {
+        std::vector<uint64_t> mvpLocalKeyFrames;   // mnIds, in the reference's order
+        std::vector<uint64_t> mvpLocalMapPoints;
+        uint64_t mpReferenceKF = kNone;
+    };
+
+    explicit LocalMap(int device = 0, int keyframes_hint = 0, int points_hint = 0) {
+        int st = ORBFE_OK;
+        m_ = orbfe_map_create(device, keyframes_hint, points_hint, &st);
+        if (!m_) throw Error("orbfe_map_create", st);
+    }
+    ~LocalMap() { orbfe_map_destroy(m_); }
+    LocalMap(const LocalMap&) = delete;
+    LocalMap& operator=(const LocalMap&) = delete;
+
+    void clear() {  // Tracking::Reset
+        check("orbfe_map_clear", orbfe_map_clear(m_));
+        kf_id_.clear();
+        mp_id_.clear();
+        kf_slot_.clear();
+        mp_slot_.clear();
+        children_.clear();
+    }
+    // new MapPoint(...)
+    void NewMapPoint(uint64_t mpId) {
+        if (mp_slot_.count(mpId)) throw Error("LocalMap::NewMapPoint", ORBFE_ERR_ARG);
+        int32_t s = -1;
+        check("orbfe_map_add_points", orbfe_map_add_points(m_, 1, &s));
+        mp_id_.push_back(mpId);
+        mp_slot_[mpId] = s;
+    }
+    // new KeyFrame(F, ...): pKF's address as the order key, mvpMapPoints as point ids or kNone
+    void NewKeyFrame(uint64_t kfId, uint64_t order_key, const std::vector<uint64_t>& mvpMapPoints) {
+        if (kf_slot_.count(kfId)) throw Error("LocalMap::NewKeyFrame", ORBFE_ERR_ARG);
+        std::vector<int32_t> mps(mvpMapPoints.size());
+        for (size_t i = 0; i < mps.size(); ++i) mps[i] = mp(mvpMapPoints[i], true);
+        int32_t s = -1;
+        check("orbfe_map_add_keyframe",
+              orbfe_map_add_keyframe(m_, order_key, (int)mps.size(), mps.data(), &s));
+        kf_id_.push_back(kfId);
+        kf_slot_[kfId] = s;
+    }
+    // KeyFrame::AddMapPoint(pMP, idx); mpId = kNone: EraseMapPointMatch(idx)
+    void AddMapPoint(uint64_t kfId, size_t idx, uint64_t mpId) {
+        const int32_t p = mp(mpId, true);
+        check("orbfe_map_set_keyframe_points", orbfe_map_set_keyframe_points(m_, kf(kfId), (int)idx, 1, &p));
+    }
+    // MapPoint::AddObservation(pKF, idx) / EraseObservation(pKF)
+    void AddObservation(uint64_t mpId, uint64_t kfId) {
+        const int32_t p = mp(mpId), k = kf(kfId);
+        check("orbfe_map_add_observations", orbfe_map_add_observations(m_, 1, &p, &k));
+    }
+    void EraseObservation(uint64_t mpId, uint64_t kfId) {
+        const int32_t p = mp(mpId), k = kf(kfId);
+        check("orbfe_map_erase_observations", orbfe_map_erase_observations(m_, 1, &p, &k));
+    }
+    // MapPoint::SetBadFlag / KeyFrame::SetBadFlag (mbBad alone: the observations and the
+    // connections change through their own hooks)
+    void SetBadFlag(uint64_t mpId) {
+        const int32_t p = mp(mpId);
+        check("orbfe_map_set_points_bad", orbfe_map_set_points_bad(m_, 1, &p, 1));
+    }
+    void SetKeyFrameBadFlag(uint64_t kfId) {
+        check("orbfe_map_set_keyframe_bad", orbfe_map_set_keyframe_bad(m_, kf(kfId), 1));
+    }
+    // KeyFrame::UpdateBestCovisibles: the first 10 of mvpOrderedConnectedKeyFrames; an id the
+    // mirror does not hold keeps its place and is skipped
+    void UpdateBestCovisibles(uint64_t kfId, const std::vector<uint64_t>& ordered) {
+        int32_t n[10];
+        const int cnt = (int)std::min<size_t>(ordered.size(), 10);
+        for (int i = 0; i < cnt; ++i) {
+            const auto it = kf_slot_.find(ordered[i]);
+            n[i] = it == kf_slot_.end() ? -1 : it->second;
+        }
+        check("orbfe_map_set_covisibility", orbfe_map_set_covisibility(m_, kf(kfId), cnt, n));
+    }
+    // KeyFrame::AddChild / EraseChild / ChangeParent (KeyFrame.cc:441-458)
+    void AddChild(uint64_t kfId, uint64_t childId) {
+        std::vector<int32_t>& c = children_[kf(kfId)];
+        const int32_t s = kf(childId);
+        if (std::find(c.begin(), c.end(), s) == c.end()) c.push_back(s);
+        check("orbfe_map_set_children", orbfe_map_set_children(m_, kf(kfId), (int)c.size(), c.data()));
+    }
+    void EraseChild(uint64_t kfId, uint64_t childId) {
+        std::vector<int32_t>& c = children_[kf(kfId)];
+        c.erase(std::remove(c.begin(), c.end(), kf(childId)), c.end());
+        check("orbfe_map_set_children", orbfe_map_set_children(m_, kf(kfId), (int)c.size(), c.data()));
+    }
+    void ChangeParent(uint64_t kfId, uint64_t parentId) {
+        check("orbfe_map_set_parent", orbfe_map_set_parent(m_, kf(kfId), kf(parentId)));
+        AddChild(parentId, kfId);
+    }
+    // mpParent alone (a keyframe loaded from a map archive; kNone: no parent)
+    void SetParent(uint64_t kfId, uint64_t parentId) {
+        check("orbfe_map_set_parent",
+              orbfe_map_set_parent(m_, kf(kfId), parentId == kNone ? -1 : kf(parentId)));
+    }
+    // mvpLocalKeyFrames / mpReferenceKF assigned directly (Tracking.cc:789, :969-970)
+    void SetLocalKeyFrames(const std::vector<uint64_t>& kfIds, uint64_t refId) {
+        std::vector<int32_t> s;
+        for (uint64_t id : kfIds) s.push_back(kf(id));
+        check("orbfe_map_set_local_keyframes",
+              orbfe_map_set_local_keyframes(m_, (int)s.size(), s.data(), refId == kNone ? -1 : kf(refId)));
+    }
+    // UpdateLocalMap() with mCurrentFrame.mnId = frameId; mvpMapPoints holds point ids or kNone
+    // and gets the bad ones set to kNone (:1508)
+    Result UpdateLocalMap(uint64_t frameId, std::vector<uint64_t>& mvpMapPoints) {
+        std::vector<int32_t> f(mvpMapPoints.size());
+        for (size_t i = 0; i < f.size(); ++i) f[i] = mp(mvpMapPoints[i], true);
+        std::vector<int32_t> kfs(ORBFE_MAP_MAX_VOTED + 8), pts(std::max<size_t>(mp_id_.size(), 1));
+        int32_t nk = 0, ref = -1, np = 0;
+        check("orbfe_map_update_local",
+              orbfe_map_update_local(m_, frameId, (int)f.size(), f.data(), kfs.data(), (int)kfs.size(),
+                                     &nk, &ref, pts.data(), (int)pts.size(), &np));
+        Result r;
+        for (int i = 0; i < nk; ++i) r.mvpLocalKeyFrames.push_back(kf_id_[kfs[i]]);
+        for (int i = 0; i < np; ++i) r.mvpLocalMapPoints.push_back(mp_id_[pts[i]]);
+        if (ref >= 0) r.mpReferenceKF = kf_id_[ref];
+        for (size_t i = 0; i < f.size(); ++i)
+            if (f[i] < 0) mvpMapPoints[i] = kNone;
+        return r;
+    }
+    // mnTrackReferenceForFrame of a keyframe / a point
+    uint64_t KeyFrameStamp(uint64_t kfId) { return stamp(ORBFE_MAP_KEYFRAMES, kf(kfId)); }
+    uint64_t MapPointStamp(uint64_t mpId) { return stamp(ORBFE_MAP_POINTS, mp(mpId)); }
+    orbfe_map* handle() const { return m_; }
+
+private:
+    int32_t kf(uint64_t id) const {
+        const auto it = kf_slot_.find(id);
+        if (it == kf_slot_.end()) throw Error("LocalMap: unknown keyframe", ORBFE_ERR_ARG);
+        return it->second;
+    }
+    int32_t mp(uint64_t id, bool none_ok = false) const {
+        if (none_ok && id == kNone) return -1;
+        const auto it = mp_slot_.find(id);
+        if (it == mp_slot_.end()) throw Error("LocalMap: unknown map point", ORBFE_ERR_ARG);
+        return it->second;
+    }
+    uint64_t stamp(int kind, int32_t slot) {
+        uint64_t v = 0;
+        check("orbfe_map_get_stamps", orbfe_map_get_stamps(m_, kind, 1, &slot, &v));
+        return v;
+    }
+    orbfe_map* m_ = nullptr;
+    std::vector<uint64_t> kf_id_, mp_id_;               // slot -> mnId
+    std::unordered_map<uint64_t, int32_t> kf_slot_, mp_slot_;
+    std::unordered_map<int32_t, std::vector<int32_t>> children_;
+};
+
 }  // namespace orbfe

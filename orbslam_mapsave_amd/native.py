@@ -66,6 +66,14 @@ EXPORTED = [
     "orbfe_kfdb_detect_loop_candidates", "orbfe_kfdb_detect_relocalization_candidates",
     "orbfe_kfdb_detect_loop_candidates_device",
     "orbfe_kfdb_detect_relocalization_candidates_device",
+    "orbfe_map_create", "orbfe_map_destroy", "orbfe_map_set_stream", "orbfe_map_clear",
+    "orbfe_map_size", "orbfe_map_add_keyframe", "orbfe_map_set_keyframe_points",
+    "orbfe_map_set_keyframe_bad", "orbfe_map_set_covisibility", "orbfe_map_set_children",
+    "orbfe_map_set_parent", "orbfe_map_add_points", "orbfe_map_set_points_bad",
+    "orbfe_map_add_observations", "orbfe_map_erase_observations", "orbfe_map_set_stamps",
+    "orbfe_map_get_stamps", "orbfe_map_set_local_keyframes", "orbfe_map_get_local_keyframes",
+    "orbfe_map_update_local", "orbfe_map_update_local_device", "orbfe_map_local_points_device",
+    "orbfe_map_get_local_points", "orbfe_map_gather_points_device",
     "orbfe_archive_mat_bytes",
     "orbfe_archive_write_keypoints_device", "orbfe_archive_read_keypoints_device",
     "orbfe_archive_write_descriptors_device", "orbfe_archive_read_descriptors_device",
@@ -136,6 +144,34 @@ def lib() -> C.CDLL:
                                                                    vp, i, vp]
             L.orbfe_kfdb_detect_relocalization_candidates_device.argtypes = [vp, u64, vp, vp, vp,
                                                                              vp, i, vp]
+        if hasattr(L, "orbfe_map_create"):
+            vp, i, u64 = C.c_void_p, C.c_int, C.c_uint64
+            L.orbfe_map_create.restype = vp
+            L.orbfe_map_create.argtypes = [i, i, i, vp]
+            L.orbfe_map_destroy.restype = None
+            L.orbfe_map_destroy.argtypes = [vp]
+            L.orbfe_map_set_stream.argtypes = [vp, vp]
+            L.orbfe_map_clear.argtypes = [vp]
+            L.orbfe_map_size.argtypes = [vp, vp, vp]
+            L.orbfe_map_add_keyframe.argtypes = [vp, u64, i, vp, vp]
+            L.orbfe_map_set_keyframe_points.argtypes = [vp, i, i, i, vp]
+            L.orbfe_map_set_keyframe_bad.argtypes = [vp, i, i]
+            L.orbfe_map_set_covisibility.argtypes = [vp, i, i, vp]
+            L.orbfe_map_set_children.argtypes = [vp, i, i, vp]
+            L.orbfe_map_set_parent.argtypes = [vp, i, i]
+            L.orbfe_map_add_points.argtypes = [vp, i, vp]
+            L.orbfe_map_set_points_bad.argtypes = [vp, i, vp, i]
+            L.orbfe_map_add_observations.argtypes = [vp, i, vp, vp]
+            L.orbfe_map_erase_observations.argtypes = [vp, i, vp, vp]
+            L.orbfe_map_set_stamps.argtypes = [vp, i, i, vp, vp]
+            L.orbfe_map_get_stamps.argtypes = [vp, i, i, vp, vp]
+            L.orbfe_map_set_local_keyframes.argtypes = [vp, i, vp, i]
+            L.orbfe_map_get_local_keyframes.argtypes = [vp, vp, i, vp, vp]
+            L.orbfe_map_update_local.argtypes = [vp, u64, i, vp, vp, i, vp, vp, vp, i, vp]
+            L.orbfe_map_update_local_device.argtypes = [vp, u64, i, vp, vp, i, vp, vp, vp]
+            L.orbfe_map_local_points_device.argtypes = [vp, vp, vp]
+            L.orbfe_map_get_local_points.argtypes = [vp, vp, i, vp]
+            L.orbfe_map_gather_points_device.argtypes = [vp, i, vp, vp, vp]
         if hasattr(L, "orbfe_archive_mat_bytes"):
             L.orbfe_archive_mat_bytes.restype = C.c_int64
             sz, vp, i = C.c_size_t, C.c_void_p, C.c_int
@@ -834,6 +870,209 @@ class KeyFrameDatabase:
         if st not in (ORBFE_OK, ORBFE_ERR_UNSUPPORTED):
             raise OrbfeError("orbfe_kfdb_detect_relocalization_candidates_device", st)
         return n.value, st
+
+
+class MapPointArrays(C.Structure):
+    """orbfe_map_point_arrays: device pointers of map-point data (map-wide or gathered)."""
+    _fields_ = [(k, C.c_void_p) for k in ("xyz", "normal", "min_dist", "max_dist", "desc", "n_obs",
+                                          "skip", "mp_ids", "bad")]
+
+
+MAP_KEYFRAMES, MAP_POINTS = 0, 1       # ORBFE_MAP_KEYFRAMES / ORBFE_MAP_POINTS
+MAP_MAX_VOTED, MAP_MAX_KF_SLOTS = 4096, 8192
+
+
+class LocalMap:
+    """Tracking::UpdateLocalMap (Tracking.cc:1455-1599) over a device mirror of the map graph
+    (orbfe_map).  Keyframes and points are named by the slots ``add_keyframe`` / ``add_points``
+    return.  The mutators carry the names of the reference methods they shadow; ``UpdateLocalMap``
+    returns ``(mvpLocalKeyFrames, mpReferenceKF, mvpLocalMapPoints, frame_mp)`` as slots."""
+
+    def __init__(self, device: int = 0, keyframes_hint: int = 0, points_hint: int = 0):
+        st = C.c_int(0)
+        h = lib().orbfe_map_create(device, keyframes_hint, points_hint, C.byref(st))
+        if not h:
+            raise OrbfeError("orbfe_map_create", st.value)
+        self._h = C.c_void_p(h)
+        self._children: dict[int, set] = {}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().orbfe_map_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _i32(a) -> np.ndarray:
+        return np.ascontiguousarray(a, np.int32).reshape(-1)
+
+    def set_stream(self, stream_handle: int | None) -> None:
+        _check("orbfe_map_set_stream", lib().orbfe_map_set_stream(self._h, _stream_arg(stream_handle)))
+
+    def clear(self) -> None:
+        _check("orbfe_map_clear", lib().orbfe_map_clear(self._h))
+        self._children.clear()
+
+    def size(self) -> tuple[int, int]:
+        a, b = C.c_int32(0), C.c_int32(0)
+        _check("orbfe_map_size", lib().orbfe_map_size(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def add_keyframe(self, order_key: int, n_slots: int, mp_slots=None) -> int:
+        s = C.c_int32(-1)
+        mp = None if mp_slots is None else self._i32(mp_slots)
+        if mp is not None and len(mp) != n_slots:
+            raise ValueError("mp_slots must hold n_slots entries")
+        _check("orbfe_map_add_keyframe", lib().orbfe_map_add_keyframe(
+            self._h, order_key, n_slots, None if mp is None else ptr(mp), C.byref(s)))
+        return s.value
+
+    def set_keyframe_points(self, slot: int, first: int, mp_slots) -> None:
+        mp = self._i32(mp_slots)
+        _check("orbfe_map_set_keyframe_points", lib().orbfe_map_set_keyframe_points(
+            self._h, slot, first, len(mp), ptr(mp)))
+
+    def AddMapPoint(self, kf: int, idx: int, mp: int) -> None:
+        """KeyFrame::AddMapPoint(pMP, idx); mp = -1: EraseMapPointMatch(idx)."""
+        self.set_keyframe_points(kf, idx, [mp])
+
+    def SetBadFlag(self, kf: int, bad: bool = True) -> None:
+        """KeyFrame::SetBadFlag."""
+        _check("orbfe_map_set_keyframe_bad", lib().orbfe_map_set_keyframe_bad(self._h, kf, int(bad)))
+
+    def UpdateBestCovisibles(self, kf: int, neigh_slots) -> None:
+        """GetBestCovisibilityKeyFrames(10) after KeyFrame::UpdateBestCovisibles."""
+        n = self._i32(neigh_slots)
+        _check("orbfe_map_set_covisibility", lib().orbfe_map_set_covisibility(
+            self._h, kf, len(n), ptr(n)))
+
+    def set_children(self, kf: int, child_slots) -> None:
+        c = self._i32(child_slots)
+        self._children[kf] = set(int(x) for x in c)
+        _check("orbfe_map_set_children", lib().orbfe_map_set_children(self._h, kf, len(c), ptr(c)))
+
+    def set_parent(self, kf: int, parent: int) -> None:
+        """mpParent = parent (or -1) alone."""
+        _check("orbfe_map_set_parent", lib().orbfe_map_set_parent(self._h, kf, parent))
+
+    def AddChild(self, kf: int, child: int) -> None:
+        """KeyFrame::AddChild: mspChildrens.insert(child)."""
+        self.set_children(kf, sorted(self._children.get(kf, set()) | {child}))
+
+    def EraseChild(self, kf: int, child: int) -> None:
+        self.set_children(kf, sorted(self._children.get(kf, set()) - {child}))
+
+    def ChangeParent(self, kf: int, parent: int) -> None:
+        """KeyFrame::ChangeParent (KeyFrame.cc): mpParent = parent; parent->AddChild(this)."""
+        self.set_parent(kf, parent)
+        self.AddChild(parent, kf)
+
+    def add_points(self, n: int) -> int:
+        s = C.c_int32(-1)
+        _check("orbfe_map_add_points", lib().orbfe_map_add_points(self._h, n, C.byref(s)))
+        return s.value
+
+    def SetBadFlagPoints(self, mp_slots, bad: bool = True) -> None:
+        """MapPoint::SetBadFlag of every listed point."""
+        p = self._i32(mp_slots)
+        _check("orbfe_map_set_points_bad", lib().orbfe_map_set_points_bad(
+            self._h, len(p), ptr(p), int(bad)))
+
+    def AddObservation(self, mp_slots, kf_slots) -> None:
+        p, k = self._i32(mp_slots), self._i32(kf_slots)
+        if len(p) != len(k):
+            raise ValueError("one keyframe per point")
+        _check("orbfe_map_add_observations", lib().orbfe_map_add_observations(
+            self._h, len(p), ptr(p), ptr(k)))
+
+    def EraseObservation(self, mp_slots, kf_slots) -> None:
+        p, k = self._i32(mp_slots), self._i32(kf_slots)
+        if len(p) != len(k):
+            raise ValueError("one keyframe per point")
+        _check("orbfe_map_erase_observations", lib().orbfe_map_erase_observations(
+            self._h, len(p), ptr(p), ptr(k)))
+
+    def set_stamps(self, kind: int, slots, stamps) -> None:
+        s, v = self._i32(slots), np.ascontiguousarray(stamps, np.uint64).reshape(-1)
+        if len(s) != len(v):
+            raise ValueError("one stamp per slot")
+        _check("orbfe_map_set_stamps", lib().orbfe_map_set_stamps(self._h, kind, len(s), ptr(s), ptr(v)))
+
+    def get_stamps(self, kind: int, slots) -> np.ndarray:
+        s = self._i32(slots)
+        v = np.zeros(len(s), np.uint64)
+        _check("orbfe_map_get_stamps", lib().orbfe_map_get_stamps(self._h, kind, len(s), ptr(s), ptr(v)))
+        return v
+
+    def set_local_keyframes(self, kf_slots, ref_kf: int) -> None:
+        k = self._i32(kf_slots)
+        _check("orbfe_map_set_local_keyframes", lib().orbfe_map_set_local_keyframes(
+            self._h, len(k), ptr(k), ref_kf))
+
+    def get_local_keyframes(self) -> tuple[np.ndarray, int]:
+        out = np.zeros(MAP_MAX_VOTED + 8, np.int32)
+        n, ref = C.c_int32(0), C.c_int32(-1)
+        _check("orbfe_map_get_local_keyframes", lib().orbfe_map_get_local_keyframes(
+            self._h, ptr(out), len(out), C.byref(n), C.byref(ref)))
+        return out[:n.value].copy(), ref.value
+
+    def UpdateLocalMap(self, frame_id: int, frame_mp, kf_cap: int = MAP_MAX_VOTED + 8,
+                       mp_cap: int | None = None):
+        """-> (local keyframes, reference keyframe, local points, updated frame_mp)."""
+        f = self._i32(frame_mp).copy()
+        if mp_cap is None:
+            mp_cap = self.size()[1]
+        kf = np.zeros(max(kf_cap, 1), np.int32)
+        mp = np.zeros(max(mp_cap, 1), np.int32)
+        nk, ref, nm = C.c_int32(0), C.c_int32(-1), C.c_int32(0)
+        st = lib().orbfe_map_update_local(self._h, frame_id, len(f), ptr(f), ptr(kf), kf_cap,
+                                          C.byref(nk), C.byref(ref), ptr(mp), mp_cap, C.byref(nm))
+        if st != ORBFE_OK:
+            e = OrbfeError("orbfe_map_update_local", st)
+            e.counts = (nk.value, nm.value)
+            e.frame_mp = f
+            raise e
+        return kf[:nk.value].copy(), ref.value, mp[:nm.value].copy(), f
+
+    def update_local_device(self, frame_id: int, n: int, d_frame_mp: int,
+                            kf_cap: int = MAP_MAX_VOTED + 8):
+        """-> (local keyframes, reference keyframe, n_local_mp); the points stay on the device
+        (``local_points_device``) and d_frame_mp is updated in place."""
+        kf = np.zeros(max(kf_cap, 1), np.int32)
+        nk, ref, nm = C.c_int32(0), C.c_int32(-1), C.c_int32(0)
+        st = lib().orbfe_map_update_local_device(self._h, frame_id, n, C.c_void_p(d_frame_mp),
+                                                 ptr(kf), kf_cap, C.byref(nk), C.byref(ref),
+                                                 C.byref(nm))
+        if st != ORBFE_OK:
+            e = OrbfeError("orbfe_map_update_local_device", st)
+            e.counts = (nk.value, nm.value)
+            raise e
+        return kf[:nk.value].copy(), ref.value, nm.value
+
+    def local_points_device(self) -> tuple[int, int]:
+        """-> (device pointer of the point list, its length)."""
+        p, n = C.c_void_p(0), C.c_int32(0)
+        _check("orbfe_map_local_points_device", lib().orbfe_map_local_points_device(
+            self._h, C.byref(p), C.byref(n)))
+        return p.value or 0, n.value
+
+    def get_local_points(self) -> np.ndarray:
+        """mvpLocalMapPoints of the last successful query, copied to the host."""
+        out = np.zeros(max(self.size()[1], 1), np.int32)
+        n = C.c_int32(0)
+        _check("orbfe_map_get_local_points", lib().orbfe_map_get_local_points(
+            self._h, ptr(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def gather_points_device(self, n: int, d_list: int, src: MapPointArrays,
+                             dst: MapPointArrays) -> None:
+        _check("orbfe_map_gather_points_device", lib().orbfe_map_gather_points_device(
+            self._h, n, C.c_void_p(d_list), C.byref(src), C.byref(dst)))
 
 
 class ORBmatcher:

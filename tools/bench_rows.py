@@ -908,11 +908,72 @@ def row_rgbd():
     ex.close()
 
 
+def row_localmap():
+    """Tracking::UpdateLocalMap at the config-5 shape: 1000 frame keypoints (3 in 4 hold a point),
+    60 keyframes of 2000 slots each over 50,000 points in a sliding window (neighbours share
+    points), ten covisibility neighbours and a parent each; per call orbfe_map_update_local_device
+    (a new frame id every call, so every point is listed again) and the gather of the listed
+    points into the inputs of orbfe_search_local_points_device.  Comparator: tests/cpp/localmap_test
+    --time, the literal std::map loop on one host thread of this machine.  Two repeats."""
+    import subprocess
+    nkf, per, npts, n = 60, 2000, 50000, 1000
+    rng = np.random.default_rng(5)
+    lm = native.LocalMap(0, nkf, npts)
+    assert lm.add_points(npts) == 0
+    for i in range(nkf):
+        mps = ((i * (npts - per) // (nkf - 1) + rng.integers(0, per, per)) % npts).astype(np.int32)
+        assert lm.add_keyframe(0x7f0000000000 + 0x2c0 * int(rng.integers(1, 1 << 20)) + i, per, mps) == i
+        lm.AddObservation(mps, np.full(per, i, np.int32))
+    for i in range(nkf):
+        lm.UpdateBestCovisibles(i, [(i + j) % nkf for j in range(1, 11)])
+        if i:
+            lm.set_parent(i, i - 1)
+    frame = np.where(rng.uniform(size=n) < 0.75, rng.integers(0, npts, n), -1).astype(np.int32)
+    d_frame = torch.from_numpy(frame).to(DEV)
+    world = {"xyz": torch.rand((npts, 3), device=DEV), "normal": torch.rand((npts, 3), device=DEV),
+             "min_dist": torch.rand(npts, device=DEV), "max_dist": torch.rand(npts, device=DEV),
+             "desc": torch.randint(0, 256, (npts, 32), dtype=torch.uint8, device=DEV),
+             "n_obs": torch.ones(npts, dtype=torch.int32, device=DEV),
+             "skip": torch.zeros(npts, dtype=torch.uint8, device=DEV)}
+    out = {k: torch.empty_like(v) for k, v in world.items()}
+    out["mp_ids"] = torch.empty(npts, dtype=torch.int32, device=DEV)
+    out["bad"] = torch.empty(npts, dtype=torch.uint8, device=DEV)
+    src = native.MapPointArrays(**{k: v.data_ptr() for k, v in world.items()})
+    dst = native.MapPointArrays(**{k: v.data_ptr() for k, v in out.items()})
+    lm.set_stream(torch.cuda.current_stream(DEV).cuda_stream)
+    fid, last = [100], [0, 0]
+
+    def update():
+        fid[0] += 1
+        kfs, _, nmp = lm.update_local_device(fid[0], n, d_frame.data_ptr())
+        last[0], last[1] = len(kfs), nmp
+
+    def both():
+        update()
+        p, cnt = lm.local_points_device()
+        lm.gather_points_device(cnt, p, src, dst)
+    exe = os.path.join(ROOT, "tests", "cpp", "build", "localmap_test")
+    for rep in range(2):
+        tu = timed(update, 200, warm=5)
+        t = timed(both, 200, warm=5)
+        r = subprocess.run([exe, "--time", "50"], capture_output=True, text=True, check=True)
+        t_cpu = float(r.stdout.split("ms_per_call=")[1].split()[0]) * 1e-3
+        jrow("local_map", "calls/s", 1, t,
+             f"repeat {rep}: orbfe_map_update_local_device + gather, {n} frame points, {last[0]} local "
+             f"keyframes of {per} slots, {last[1]} local points; comparator: the literal std::map loop, "
+             f"one host thread ({r.stdout.strip()})", update_only_ms=round(tu * 1e3, 4),
+             gather_ms=round((t - tu) * 1e3, 4), comparator_ms=round(t_cpu * 1e3, 4),
+             device_over_comparator=round(t / t_cpu, 3), comparator_over_device=round(t_cpu / t, 3),
+             bytes_per_call=int(last[1] * (4 + 72 + 6) + nkf * per * 8))
+    lm.close()
+
+
 if __name__ == "__main__":
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         rows = {"single": row_single, "color": row_color, "stereo": row_stereo, "reloc": row_reloc, "fuse": row_fuse, "triangulation": row_triangulation, "track": row_track,
                 "distinctive": row_distinctive, "bow": lambda: row_bow(td),
-                "loop": row_loop, "kfdb": lambda: row_kfdb(td), "rgbd": row_rgbd}
+                "loop": row_loop, "kfdb": lambda: row_kfdb(td), "rgbd": row_rgbd,
+                "localmap": row_localmap}
         for name in (sys.argv[1:] or list(rows)):
             rows[name]()
