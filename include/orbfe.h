@@ -1079,7 +1079,10 @@ int orbfe_map_set_keyframe_points(orbfe_map* m, int slot, int first, int n, cons
 /* KeyFrame::SetBadFlag (mbBad). */
 int orbfe_map_set_keyframe_bad(orbfe_map* m, int slot, int bad);
 /* GetBestCovisibilityKeyFrames(10) of the keyframe, in its order: n <= 10 slots; -1 entries keep
- * their place and are skipped (the contract of orbfe_kfdb_set_covisibility). */
+ * their place and are skipped (the contract of orbfe_kfdb_set_covisibility).  Writes the ten
+ * neighbours UpdateLocalKeyFrames reads and nothing else: the covisibility graph below
+ * (weights, ordered list) is not touched, and the next call there that writes this keyframe's
+ * ordered list overwrites the ten. */
 int orbfe_map_set_covisibility(orbfe_map* m, int slot, int n, const int32_t* neigh_slots);
 /* mspChildrens: the whole set, in any order; the handle sorts it by order key. */
 int orbfe_map_set_children(orbfe_map* m, int slot, int n, const int32_t* child_slots);
@@ -1163,6 +1166,63 @@ typedef struct orbfe_map_point_arrays {
 int orbfe_map_gather_points_device(orbfe_map* m, int n, const int32_t* d_list,
                                    const orbfe_map_point_arrays* src,
                                    const orbfe_map_point_arrays* dst);
+
+/* ---- the covisibility graph: KeyFrame::UpdateConnections (KeyFrame.cc:1010-1100) ------------
+ * Per keyframe of an orbfe_map, device-resident: mConnectedKeyFrameWeights as a row of
+ * (slot, weight) in pointer order (ascending order key), mvpOrderedConnectedKeyFrames with
+ * mvOrderedWeights, and mbFirstConnection (1 for a new keyframe).  The ordered list is state, not
+ * a function of the weights: UpdateConnections leaves it thresholded at 15,
+ * AddConnection re-sorts the whole weight map into it only when a weight changed.  A weight map
+ * holds at most ORBFE_MAP_MAX_VOTED entries and a weight is at most ORBFE_MAP_MAX_KF_SLOTS.
+ * Whenever a call below writes a keyframe's ordered list, its first ten entries (padded with -1)
+ * become the neighbours UpdateLocalKeyFrames reads (orbfe_map_set_covisibility's data).  Device
+ * storage grows inside these calls only.  All of them are synchronous; orbfe_map_clear resets
+ * all of it.  The counting, the sorts, the upserts into the neighbours and their re-sorts run in
+ * kernels; the host keeps row lengths and capacities only. */
+
+/* UpdateConnections() on kf_slots[0 .. n) in that order, with the result of the reference's
+ * sequential loop (n = 1: the online call; every keyframe: System.cc:188-191).  allow_parent[i]
+ * is `mnId != 0` of keyframe i (NULL: all 1): with it and the first-connection flag set, the
+ * parent becomes the front of the new ordered list, the keyframe joins the parent's children
+ * (kept sorted by order key) and the flag is cleared.  parent_out[i] (or NULL) = the parent this
+ * call assigned, else -1; n_ordered_out[i] (or NULL) = the length of the ordered list afterwards.
+ * A keyframe whose points have no other observer is left exactly as it was (:1044).  Slots that
+ * are out of range or not distinct: ORBFE_ERR_ARG.  A counter of more than 4096 keyframes, or a
+ * neighbour's weight map that would pass 4096 entries: ORBFE_ERR_CAPACITY.  Either way nothing has
+ * changed.  The batch is not cut into chunks: at most six kernel launches and five host waits
+ * whatever n is (plus one of each when a parent was assigned). */
+int orbfe_map_update_connections(orbfe_map* m, int n, const int32_t* kf_slots,
+                                 const uint8_t* allow_parent, int32_t* parent_out,
+                                 int32_t* n_ordered_out);
+/* KeyFrame::AddConnection (:844-857): an absent key is inserted, a different weight overwritten,
+ * both followed by UpdateBestCovisibles; an equal weight changes nothing.  0 <= weight <= 8192. */
+int orbfe_map_add_connection(orbfe_map* m, int slot, int other, int weight);
+/* KeyFrame::EraseConnection (:1295-1309): erases and re-sorts only if the key is present. */
+int orbfe_map_erase_connection(orbfe_map* m, int slot, int other);
+/* KeyFrame::UpdateBestCovisibles (:859-878): the ordered list becomes the whole weight map,
+ * descending weight and, among equal weights, descending order key. */
+int orbfe_map_update_best_covisibles(orbfe_map* m, int slot);
+/* The connection part of KeyFrame::SetBadFlag (:1188-1189, :1198-1199): EraseConnection(slot) on
+ * every key of the keyframe's weight map, then its own weight map and ordered list cleared. */
+int orbfe_map_erase_keyframe_connections(orbfe_map* m, int slot);
+/* Plain assignments, as a map archive holds them (KeyFrame.cc:400-443); nothing is re-sorted.
+ * The weight map: n <= 4096 distinct keyframes in any order.  The ordered list with its weights:
+ * n <= 4096 entries in the list's order (this one also writes the ten neighbours).  The flag. */
+int orbfe_map_set_connections(orbfe_map* m, int slot, int n, const int32_t* kf_slots,
+                              const int32_t* weights);
+int orbfe_map_set_ordered_connections(orbfe_map* m, int slot, int n, const int32_t* kf_slots,
+                                      const int32_t* weights);
+int orbfe_map_set_first_connection(orbfe_map* m, int slot, int flag);
+/* Read back from device memory.  The weight map in pointer order; the ordered list in its order;
+ * weights may be NULL.  *n > cap: ORBFE_ERR_CAPACITY with nothing copied. */
+int orbfe_map_get_connections(orbfe_map* m, int slot, int32_t* kf_slots, int32_t* weights, int cap,
+                              int32_t* n);
+int orbfe_map_get_ordered_connections(orbfe_map* m, int slot, int32_t* kf_slots, int32_t* weights,
+                                      int cap, int32_t* n);
+/* mpParent (or -1), mbFirstConnection and mspChildrens in pointer order; parent and
+ * first_connection may be NULL. */
+int orbfe_map_get_spanning_tree(orbfe_map* m, int slot, int32_t* parent, int32_t* first_connection,
+                                int32_t* child_slots, int cap, int32_t* n_children);
 
 /* ---- map-archive records of the extractor outputs (device side) ---------------------------
  * The bodies the reference's Boost map archive stores for the extractor's outputs, written

@@ -885,6 +885,73 @@ public:
             if (f[i] < 0) mvpMapPoints[i] = kNone;
         return r;
     }
+    // ---- the covisibility graph on the device
+    // KeyFrame::UpdateConnections (KeyFrame.cc:1010-1100) of one keyframe, or of several in that
+    // order (System.cc:188-191 after LoadMap: every keyframe of the map); `mnId != 0` is kfId != 0.
+    // The children the device assigned are added to the cache AddChild / EraseChild upload from.
+    void UpdateConnections(uint64_t kfId) { UpdateConnections(std::vector<uint64_t>{kfId}); }
+    void UpdateConnections(const std::vector<uint64_t>& kfIds) {
+        std::vector<int32_t> s, parent(kfIds.size(), -1);
+        std::vector<uint8_t> allow;
+        for (uint64_t id : kfIds) {
+            s.push_back(kf(id));
+            allow.push_back(id != 0);
+        }
+        check("orbfe_map_update_connections",
+              orbfe_map_update_connections(m_, (int)s.size(), s.data(), allow.data(), parent.data(), nullptr));
+        for (size_t i = 0; i < s.size(); ++i) {
+            if (parent[i] < 0) continue;
+            std::vector<int32_t>& c = children_[parent[i]];
+            if (std::find(c.begin(), c.end(), s[i]) == c.end()) c.push_back(s[i]);
+        }
+    }
+    // KeyFrame::AddConnection / EraseConnection / UpdateBestCovisibles (:844-878, :1295-1309)
+    void AddConnection(uint64_t kfId, uint64_t otherId, int weight) {
+        check("orbfe_map_add_connection", orbfe_map_add_connection(m_, kf(kfId), kf(otherId), weight));
+    }
+    void EraseConnection(uint64_t kfId, uint64_t otherId) {
+        check("orbfe_map_erase_connection", orbfe_map_erase_connection(m_, kf(kfId), kf(otherId)));
+    }
+    void UpdateBestCovisibles(uint64_t kfId) {
+        check("orbfe_map_update_best_covisibles", orbfe_map_update_best_covisibles(m_, kf(kfId)));
+    }
+    // the connection part of KeyFrame::SetBadFlag (:1188-1189, :1198-1199)
+    void EraseKeyFrameConnections(uint64_t kfId) {
+        check("orbfe_map_erase_keyframe_connections", orbfe_map_erase_keyframe_connections(m_, kf(kfId)));
+    }
+    void SetFirstConnection(uint64_t kfId, bool flag) {
+        check("orbfe_map_set_first_connection", orbfe_map_set_first_connection(m_, kf(kfId), flag));
+    }
+    // GetConnectedKeyFrames (:880-887) in pointer order; GetVectorCovisibleKeyFrames (:889-893);
+    // GetBestCovisibilityKeyFrames (:895-903)
+    std::vector<uint64_t> GetConnectedKeyFrames(uint64_t kfId) { return ids(row(kfId, false).first); }
+    std::vector<uint64_t> GetVectorCovisibleKeyFrames(uint64_t kfId) { return ids(row(kfId, true).first); }
+    std::vector<uint64_t> GetBestCovisibilityKeyFrames(uint64_t kfId, int N) {
+        std::vector<uint64_t> v = GetVectorCovisibleKeyFrames(kfId);
+        if ((int)v.size() >= N) v.resize((size_t)std::max(N, 0));
+        return v;
+    }
+    // mvOrderedWeights, next to GetVectorCovisibleKeyFrames
+    std::vector<int> GetOrderedWeights(uint64_t kfId) { return row(kfId, true).second; }
+    // GetCovisiblesByWeight (:905-920): upper_bound with a > b over the descending weights; when
+    // every weight is >= w the iterator is end() and the reference returns nothing
+    std::vector<uint64_t> GetCovisiblesByWeight(uint64_t kfId, int w) {
+        const auto r = row(kfId, true);
+        const auto it = std::upper_bound(r.second.begin(), r.second.end(), w, [](int a, int b) { return a > b; });
+        if (r.first.empty() || it == r.second.end()) return {};
+        return ids(std::vector<int32_t>(r.first.begin(), r.first.begin() + (it - r.second.begin())));
+    }
+    // GetWeight (:922-929)
+    int GetWeight(uint64_t kfId, uint64_t otherId) {
+        const auto r = row(kfId, false);
+        const auto it = std::find(r.first.begin(), r.first.end(), kf(otherId));
+        return it == r.first.end() ? 0 : r.second[(size_t)(it - r.first.begin())];
+    }
+    // GetParent (kNone: none) / GetChilds in pointer order / mbFirstConnection
+    uint64_t GetParent(uint64_t kfId) { return tree(kfId).parent; }
+    std::vector<uint64_t> GetChilds(uint64_t kfId) { return tree(kfId).children; }
+    bool FirstConnection(uint64_t kfId) { return tree(kfId).first; }
+
     // mnTrackReferenceForFrame of a keyframe / a point
     uint64_t KeyFrameStamp(uint64_t kfId) { return stamp(ORBFE_MAP_KEYFRAMES, kf(kfId)); }
     uint64_t MapPointStamp(uint64_t mpId) { return stamp(ORBFE_MAP_POINTS, mp(mpId)); }
@@ -906,6 +973,41 @@ private:
         uint64_t v = 0;
         check("orbfe_map_get_stamps", orbfe_map_get_stamps(m_, kind, 1, &slot, &v));
         return v;
+    }
+    std::vector<uint64_t> ids(const std::vector<int32_t>& slots) const {
+        std::vector<uint64_t> out;
+        for (int32_t s : slots) out.push_back(kf_id_[s]);
+        return out;
+    }
+    // the weight map (pointer order) or the ordered list of a keyframe: (slots, weights)
+    std::pair<std::vector<int32_t>, std::vector<int>> row(uint64_t kfId, bool ordered) {
+        std::vector<int32_t> s(ORBFE_MAP_MAX_VOTED), w(ORBFE_MAP_MAX_VOTED);
+        int32_t n = 0;
+        if (ordered)
+            check("orbfe_map_get_ordered_connections",
+                  orbfe_map_get_ordered_connections(m_, kf(kfId), s.data(), w.data(), (int)s.size(), &n));
+        else
+            check("orbfe_map_get_connections",
+                  orbfe_map_get_connections(m_, kf(kfId), s.data(), w.data(), (int)s.size(), &n));
+        s.resize((size_t)n);
+        return {s, std::vector<int>(w.begin(), w.begin() + n)};
+    }
+    struct Tree {
+        uint64_t parent = kNone;
+        bool first = false;
+        std::vector<uint64_t> children;
+    };
+    Tree tree(uint64_t kfId) {
+        std::vector<int32_t> c(std::max<size_t>(kf_id_.size(), 1));
+        int32_t p = -1, f = 0, n = 0;
+        check("orbfe_map_get_spanning_tree",
+              orbfe_map_get_spanning_tree(m_, kf(kfId), &p, &f, c.data(), (int)c.size(), &n));
+        Tree t;
+        if (p >= 0) t.parent = kf_id_[p];
+        t.first = f != 0;
+        c.resize((size_t)n);
+        t.children = ids(c);
+        return t;
     }
     orbfe_map* m_ = nullptr;
     std::vector<uint64_t> kf_id_, mp_id_;               // slot -> mnId

@@ -474,6 +474,11 @@ struct MapRowWrite {
     const int* data;
 };
 
+// The covisibility graph of the handle (orbfe_covis.hip): made by its first call there.
+struct MapCovis;
+void map_covis_free(MapCovis* c);
+void map_covis_reset(MapCovis* c);
+
 }  // namespace
 
 struct orbfe_map {
@@ -491,6 +496,7 @@ struct orbfe_map {
     hipStream_t own = nullptr, stream = nullptr;
     int* pin = nullptr;
     int* pin_dev = nullptr;
+    MapCovis* covis = nullptr;
 
     MapDev dev() const {
         MapDev d;
@@ -524,6 +530,7 @@ struct orbfe_map {
     bool kf_ok(int s) const { return s >= 0 && s < n_kf; }
     bool mp_ok(int s) const { return s >= 0 && s < n_mp; }
     ~orbfe_map() {
+        map_covis_free(covis);
         if (pin) hipHostFree(pin);
         if (own) hipStreamDestroy(own);
     }
@@ -769,6 +776,7 @@ int orbfe_map_clear(orbfe_map* m) {
         m->kf_mp.reset();
         m->kf_ch.reset();
         m->mp_obs.reset();
+        map_covis_reset(m->covis);
         return map_reset_ctl(m);
     });
 }

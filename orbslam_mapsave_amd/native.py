@@ -74,6 +74,11 @@ EXPORTED = [
     "orbfe_map_get_stamps", "orbfe_map_set_local_keyframes", "orbfe_map_get_local_keyframes",
     "orbfe_map_update_local", "orbfe_map_update_local_device", "orbfe_map_local_points_device",
     "orbfe_map_get_local_points", "orbfe_map_gather_points_device",
+    "orbfe_map_update_connections", "orbfe_map_add_connection", "orbfe_map_erase_connection",
+    "orbfe_map_update_best_covisibles", "orbfe_map_erase_keyframe_connections",
+    "orbfe_map_set_connections", "orbfe_map_set_ordered_connections",
+    "orbfe_map_set_first_connection", "orbfe_map_get_connections",
+    "orbfe_map_get_ordered_connections", "orbfe_map_get_spanning_tree",
     "orbfe_archive_mat_bytes",
     "orbfe_archive_write_keypoints_device", "orbfe_archive_read_keypoints_device",
     "orbfe_archive_write_descriptors_device", "orbfe_archive_read_descriptors_device",
@@ -172,6 +177,19 @@ def lib() -> C.CDLL:
             L.orbfe_map_local_points_device.argtypes = [vp, vp, vp]
             L.orbfe_map_get_local_points.argtypes = [vp, vp, i, vp]
             L.orbfe_map_gather_points_device.argtypes = [vp, i, vp, vp, vp]
+        if hasattr(L, "orbfe_map_update_connections"):
+            vp, i = C.c_void_p, C.c_int
+            L.orbfe_map_update_connections.argtypes = [vp, i, vp, vp, vp, vp]
+            L.orbfe_map_add_connection.argtypes = [vp, i, i, i]
+            L.orbfe_map_erase_connection.argtypes = [vp, i, i]
+            L.orbfe_map_update_best_covisibles.argtypes = [vp, i]
+            L.orbfe_map_erase_keyframe_connections.argtypes = [vp, i]
+            L.orbfe_map_set_connections.argtypes = [vp, i, i, vp, vp]
+            L.orbfe_map_set_ordered_connections.argtypes = [vp, i, i, vp, vp]
+            L.orbfe_map_set_first_connection.argtypes = [vp, i, i]
+            L.orbfe_map_get_connections.argtypes = [vp, i, vp, vp, i, vp]
+            L.orbfe_map_get_ordered_connections.argtypes = [vp, i, vp, vp, i, vp]
+            L.orbfe_map_get_spanning_tree.argtypes = [vp, i, vp, vp, vp, i, vp]
         if hasattr(L, "orbfe_archive_mat_bytes"):
             L.orbfe_archive_mat_bytes.restype = C.c_int64
             sz, vp, i = C.c_size_t, C.c_void_p, C.c_int
@@ -945,8 +963,14 @@ class LocalMap:
         """KeyFrame::SetBadFlag."""
         _check("orbfe_map_set_keyframe_bad", lib().orbfe_map_set_keyframe_bad(self._h, kf, int(bad)))
 
-    def UpdateBestCovisibles(self, kf: int, neigh_slots) -> None:
-        """GetBestCovisibilityKeyFrames(10) after KeyFrame::UpdateBestCovisibles."""
+    def UpdateBestCovisibles(self, kf: int, neigh_slots=None) -> None:
+        """With ``neigh_slots``: GetBestCovisibilityKeyFrames(10) after KeyFrame::UpdateBestCovisibles,
+        computed by the caller.  Without: KeyFrame::UpdateBestCovisibles itself, the ordered list
+        re-sorted from the whole weight map on the device."""
+        if neigh_slots is None:
+            _check("orbfe_map_update_best_covisibles",
+                   lib().orbfe_map_update_best_covisibles(self._h, kf))
+            return
         n = self._i32(neigh_slots)
         _check("orbfe_map_set_covisibility", lib().orbfe_map_set_covisibility(
             self._h, kf, len(n), ptr(n)))
@@ -1073,6 +1097,102 @@ class LocalMap:
                              dst: MapPointArrays) -> None:
         _check("orbfe_map_gather_points_device", lib().orbfe_map_gather_points_device(
             self._h, n, C.c_void_p(d_list), C.byref(src), C.byref(dst)))
+
+    # ---- the covisibility graph (KeyFrame.cc:844-929, 1010-1100, 1188-1199, 1295-1309)
+    def UpdateConnections(self, kf, allow_parent=None):
+        """KeyFrame::UpdateConnections of one keyframe slot, or of a sequence of them in that
+        order.  ``allow_parent`` is ``mnId != 0`` per keyframe (default: all true).
+        -> (parents assigned by this call or -1, lengths of the ordered lists)."""
+        k = self._i32([kf] if np.isscalar(kf) else kf)
+        a = None if allow_parent is None else np.ascontiguousarray(
+            [allow_parent] if np.isscalar(allow_parent) else allow_parent, np.uint8).reshape(-1)
+        if a is not None and len(a) != len(k):
+            raise ValueError("one allow_parent per keyframe")
+        par, no = np.full(len(k), -1, np.int32), np.zeros(len(k), np.int32)
+        _check("orbfe_map_update_connections", lib().orbfe_map_update_connections(
+            self._h, len(k), ptr(k), ptr(a), ptr(par), ptr(no)))
+        for c, p in zip(k, par):
+            if p >= 0:
+                self._children.setdefault(int(p), set()).add(int(c))
+        return par, no
+
+    def AddConnection(self, kf: int, other: int, weight: int) -> None:
+        _check("orbfe_map_add_connection", lib().orbfe_map_add_connection(self._h, kf, other, weight))
+
+    def EraseConnection(self, kf: int, other: int) -> None:
+        _check("orbfe_map_erase_connection", lib().orbfe_map_erase_connection(self._h, kf, other))
+
+    def erase_keyframe_connections(self, kf: int) -> None:
+        """The connection part of KeyFrame::SetBadFlag (:1188-1189, :1198-1199)."""
+        _check("orbfe_map_erase_keyframe_connections",
+               lib().orbfe_map_erase_keyframe_connections(self._h, kf))
+
+    def set_connections(self, kf: int, kf_slots, weights) -> None:
+        s, w = self._i32(kf_slots), self._i32(weights)
+        if len(s) != len(w):
+            raise ValueError("one weight per keyframe")
+        _check("orbfe_map_set_connections", lib().orbfe_map_set_connections(
+            self._h, kf, len(s), ptr(s), ptr(w)))
+
+    def set_ordered_connections(self, kf: int, kf_slots, weights) -> None:
+        s, w = self._i32(kf_slots), self._i32(weights)
+        if len(s) != len(w):
+            raise ValueError("one weight per keyframe")
+        _check("orbfe_map_set_ordered_connections", lib().orbfe_map_set_ordered_connections(
+            self._h, kf, len(s), ptr(s), ptr(w)))
+
+    def set_first_connection(self, kf: int, flag: bool) -> None:
+        _check("orbfe_map_set_first_connection",
+               lib().orbfe_map_set_first_connection(self._h, kf, int(flag)))
+
+    def _connections(self, fn: str, kf: int):
+        s, w = np.zeros(MAP_MAX_VOTED, np.int32), np.zeros(MAP_MAX_VOTED, np.int32)
+        n = C.c_int32(0)
+        _check(fn, getattr(lib(), fn)(self._h, kf, ptr(s), ptr(w), len(s), C.byref(n)))
+        return s[:n.value].copy(), w[:n.value].copy()
+
+    def get_connections(self, kf: int):
+        """mConnectedKeyFrameWeights in pointer order -> (slots, weights)."""
+        return self._connections("orbfe_map_get_connections", kf)
+
+    def get_ordered_connections(self, kf: int):
+        """mvpOrderedConnectedKeyFrames, mvOrderedWeights -> (slots, weights)."""
+        return self._connections("orbfe_map_get_ordered_connections", kf)
+
+    def get_spanning_tree(self, kf: int):
+        """-> (mpParent or -1, mbFirstConnection, mspChildrens in pointer order)."""
+        p, f, n = C.c_int32(-1), C.c_int32(0), C.c_int32(0)
+        ch = np.zeros(max(self.size()[0], 1), np.int32)
+        _check("orbfe_map_get_spanning_tree", lib().orbfe_map_get_spanning_tree(
+            self._h, kf, C.byref(p), C.byref(f), ptr(ch), len(ch), C.byref(n)))
+        return p.value, bool(f.value), ch[:n.value].copy()
+
+    def GetConnectedKeyFrames(self, kf: int) -> set:
+        return set(int(x) for x in self.get_connections(kf)[0])
+
+    def GetVectorCovisibleKeyFrames(self, kf: int) -> np.ndarray:
+        return self.get_ordered_connections(kf)[0]
+
+    def GetBestCovisibilityKeyFrames(self, kf: int, n: int) -> np.ndarray:
+        return self.get_ordered_connections(kf)[0][:max(n, 0)]
+
+    def GetCovisiblesByWeight(self, kf: int, w: int) -> np.ndarray:
+        """KeyFrame.cc:905-920 with its `it == end` quirk: when every weight is >= w the
+        reference returns nothing."""
+        s, ws = self.get_ordered_connections(kf)
+        n = int(np.count_nonzero(ws >= w))  # upper_bound with a > b over descending weights
+        return s[:0] if n == len(ws) else s[:n]
+
+    def GetWeight(self, kf: int, other: int) -> int:
+        s, w = self.get_connections(kf)
+        hit = np.nonzero(s == other)[0]
+        return int(w[hit[0]]) if len(hit) else 0
+
+    def GetParent(self, kf: int) -> int:
+        return self.get_spanning_tree(kf)[0]
+
+    def GetChilds(self, kf: int) -> set:
+        return set(int(x) for x in self.get_spanning_tree(kf)[2])
 
 
 class ORBmatcher:

@@ -968,12 +968,63 @@ def row_localmap():
     lm.close()
 
 
+def row_covis():
+    """KeyFrame::UpdateConnections on the device.  (a) The online call on the config-5 map of
+    row_localmap (60 keyframes of 2000 slots over 50,000 points in a sliding window): one keyframe
+    per call, every keyframe in turn.  (b) The load-map call (System.cc:188-191): 1000 keyframes
+    of 1000 slots over a sliding window in which each shares points with about 20 others, one
+    batch call over all of them.  A host clock around calls that end synchronised; comparator:
+    tests/cpp/covis_test --time, the literal std::map loop on one host thread of this machine.
+    Two repeats."""
+    import subprocess
+
+    def world(nkf, per, npts, seed):
+        rng = np.random.default_rng(seed)
+        lm = native.LocalMap(0, nkf, npts)
+        assert lm.add_points(npts) == 0
+        for i in range(nkf):
+            mps = ((i * (npts - per) // (nkf - 1) + rng.integers(0, per, per)) % npts).astype(np.int32)
+            assert lm.add_keyframe(0x7f0000000000 + 0x2c0 * int(rng.integers(1, 1 << 20)) + i, per, mps) == i
+            lm.AddObservation(mps, np.full(per, i, np.int32))
+        return lm
+
+    exe = os.path.join(ROOT, "tests", "cpp", "build", "covis_test")
+    online = world(60, 2000, 50000, 5)
+    load = world(1000, 1000, 100000, 6)
+    every = np.arange(1000, dtype=np.int32)
+    turn = [0]
+
+    def one():
+        online.UpdateConnections(turn[0] % 60)
+        turn[0] += 1
+    for i in range(60):   # as the comparator: every keyframe has been connected once before the clock
+        online.UpdateConnections(i)
+    for rep in range(2):
+        ta = timed(one, 240, warm=5)
+        tb = timed(lambda: load.UpdateConnections(every), 10, warm=5)
+        r = subprocess.run([exe, "--time", "8"], capture_output=True, text=True, check=True)
+        ca, cb = (float(l.split("ms_per_call=")[1].split()[0]) * 1e-3 for l in r.stdout.splitlines()[:2])
+        na = float(np.mean([len(online.get_connections(i)[0]) for i in range(60)]))
+        nb = float(np.mean([len(load.get_connections(i)[0]) for i in range(0, 1000, 10)]))
+        jrow("covis_online", "calls/s", 1, ta,
+             f"repeat {rep}: orbfe_map_update_connections, one keyframe of 2000 slots per call, "
+             f"{na:.1f} neighbours; comparator: the literal std::map loop, one host thread "
+             f"({r.stdout.splitlines()[0]})", comparator_ms=round(ca * 1e3, 4),
+             comparator_over_device=round(ca / ta, 3))
+        jrow("covis_loadmap", "keyframes/s", 1000, tb,
+             f"repeat {rep}: orbfe_map_update_connections, one batch of 1000 keyframes of 1000 slots, "
+             f"{nb:.1f} neighbours; comparator: the literal loop ({r.stdout.splitlines()[1]})",
+             comparator_ms=round(cb * 1e3, 4), comparator_over_device=round(cb / tb, 3))
+    online.close()
+    load.close()
+
+
 if __name__ == "__main__":
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         rows = {"single": row_single, "color": row_color, "stereo": row_stereo, "reloc": row_reloc, "fuse": row_fuse, "triangulation": row_triangulation, "track": row_track,
                 "distinctive": row_distinctive, "bow": lambda: row_bow(td),
                 "loop": row_loop, "kfdb": lambda: row_kfdb(td), "rgbd": row_rgbd,
-                "localmap": row_localmap}
+                "localmap": row_localmap, "covis": row_covis}
         for name in (sys.argv[1:] or list(rows)):
             rows[name]()
