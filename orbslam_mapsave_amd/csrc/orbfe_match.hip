@@ -278,18 +278,25 @@ __global__ __launch_bounds__(kBfBlock) void bf_match_kernel(
 // Lane half h of chunk c (bits 64 c .. 64 c + 63) holds descriptor dword 2 c + h as 32 nibbles;
 // the nibble order inside the lane is the same permutation for references and queries (a K
 // permutation common to A and B leaves the product unchanged): bit 8 q + b -> dword q, byte b,
-// low nibble; bit 8 q + 4 + b -> the high nibble.  Ranking as above, on f32 keys (min / med3 of
-// exact integers), converted to the 32-bit keys when a tile closes.
-// ORBFE_BF_WAVES: minimum waves per SIMD the FP4 kernel is compiled for.  At 3 it takes 135
-// VGPRs; 4 (<= 128 VGPRs, 3 spilled, all 1,024 blocks of a 256-frame step resident at once
-// instead of in 1.33 rounds) measured the same 103.2-103.9 us per launch
-// (profiles/r03/experiments/bf_waves.json)
+// low nibble; bit 8 q + 4 + b -> the high nibble.
+// The kernel is bound by the vector instructions a wave issues beside its MFMAs
+// (profiles/bf_rank/), so the loop is built to issue few of them.  The four chains of a tile run
+// m-tile major, (m-tile 0, n-tile 0), (0, 1), (1, 0), (1, 1): a reference fragment read from LDS
+// serves both query halves (8 ds_read_b128 per tile).  The C input also carries kBfBias, so every
+// key is an f32 holding a non-negative integer, and a chain's 16 keys reduce to their two smallest
+// through a ternary tree (BfPairF) in 20 instructions; m-tile 1's pair merges with m-tile 0's, and
+// the tile's pair becomes 32-bit keys and merges into the lane's running pair (BfLaneF::close).
+// ORBFE_BF_WAVES: minimum waves per SIMD the FP4 kernel is compiled for.  At 3 it takes 141
+// VGPRs (152 with the pre-expanded references); 4 (<= 128 VGPRs, 3 spilled, all 1,024 blocks of
+// a 256-frame step resident at once instead of in 1.33 rounds) measured the same 103.2-103.9 us
+// per launch on the earlier one-push-per-key loop (profiles/r03/experiments/bf_waves.json)
 #ifndef ORBFE_BF_WAVES
 #define ORBFE_BF_WAVES 3
 #endif
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr float kBfNoneF = 32767.f;
+constexpr int kBfBias = 64 * 256;       // in every f32 key: 64 (X + 256) + p >= 0
+constexpr float kBfNoneF = 65535.f;     // never wins (> 64 * 512 + 63)
 // 8 bits (s .. s+7 of w) as 8 nibbles of one dword, each 0 or 1 (bit s+b -> byte b low nibble,
 // bit s+4+b -> byte b high nibble)
 __device__ __forceinline__ uint32_t bits8_nib(uint32_t w, int s) {
@@ -303,22 +310,42 @@ __device__ __forceinline__ i32x4 qry_fp4(uint32_t w) {  // 0 -> +1.0 (0x2), 1 ->
     return i32x4{(int)((bits8_nib(w, 0) << 3) | 0x22222222u), (int)((bits8_nib(w, 8) << 3) | 0x22222222u),
                  (int)((bits8_nib(w, 16) << 3) | 0x22222222u), (int)((bits8_nib(w, 24) << 3) | 0x22222222u)};
 }
+// The f32 keys are exact integers >= 0 (the C input carries kBfBias), so their bit patterns order
+// as they do: the minimum is an integer minimum (v_min_i32 / v_min3_i32; fminf would
+// canonicalize its operands, and an inline-asm v_min_f32 makes the compiler pad the next use of
+// its result with s_nop), the median v_med3_f32.
+__device__ __forceinline__ float kminf(float a, float b) {
+    return __int_as_float(kmin(__float_as_int(a), __float_as_int(b)));
+}
+__device__ __forceinline__ float kmin3f(float a, float b, float c) { return kminf(kminf(a, b), c); }
+// The two smallest keys of a set, b <= s.  The keys of a tile are distinct (their positions are),
+// so the pair does not depend on the order of the merges: a chain's 16 keys go through a ternary
+// tree -- 3 keys to a pair in 2 instructions, 3 pairs to one in 4 -- at 20 instructions per chain
+// where one push per key takes 32, and the leaves are independent of each other.
+struct BfPairF {
+    float b, s;
+};
+__device__ __forceinline__ BfPairF bf_top2(float x, float y, float z) {
+    return {kmin3f(x, y, z), __builtin_amdgcn_fmed3f(x, y, z)};
+}
+__device__ __forceinline__ BfPairF bf_merge3(BfPairF x, BfPairF y, BfPairF z) {
+    // the second of the union: the median of the bests, or the smallest second
+    return {kmin3f(x.b, y.b, z.b), kminf(__builtin_amdgcn_fmed3f(x.b, y.b, z.b), kmin3f(x.s, y.s, z.s))};
+}
+__device__ __forceinline__ BfPairF bf_merge2(BfPairF x, BfPairF y) {
+    return {kminf(x.b, y.b), __builtin_amdgcn_fmed3f(x.b, y.b, kminf(x.s, y.s))};
+}
+__device__ __forceinline__ BfPairF bf_push(BfPairF x, float k) {
+    return {kminf(x.b, k), __builtin_amdgcn_fmed3f(x.b, x.s, k)};
+}
 struct BfLaneF {
-    float tb, ts;
+    BfPairF t;  // the tile's pair: m-tile 0's, then merged with m-tile 1's
     int best, second;
-    __device__ __forceinline__ void push(float k) {
-        // exact integers, never NaN: plain v_min_f32 (fminf would canonicalize its operands)
-        ts = __builtin_amdgcn_fmed3f(tb, ts, k);
-        float m;
-        asm("v_min_f32 %0, %1, %2" : "=v"(m) : "v"(tb), "v"(k));
-        tb = m;
-    }
     __device__ __forceinline__ void close(int base) {
-        const int ib = (int)tb, is = (int)ts;
+        const int ib = (int)t.b, is = (int)t.s;  // (X + 256) * 64 + position
         const int kb = ((ib >> 6) << 16) + base + (ib & 63), ks = (is >> 6) << 16;
         second = kmin(kmin(second, ks), kmax(best, kb));
         best = kmin(best, kb);
-        tb = ts = kBfNoneF;
     }
 };
 // A reference set shared by every batch entry (r_pitch 0: config 3's one reference frame) is
@@ -383,14 +410,15 @@ __device__ __forceinline__ void bf_fp4_body(
 #pragma unroll
         for (int c = 0; c < 4; ++c) bq[nt][c] = qry_fp4(dw[2 * c + h]);
         popc[nt] = pc;
-        st[nt].best = st[nt].second = (256 - pc) << 16;
-        st[nt].tb = st[nt].ts = kBfNoneF;
+        // the running keys carry the bias as (X + 256) << 16: distance 256 is X + 256 = 512 - popc
+        st[nt].best = st[nt].second = (512 - pc) << 16;
+        st[nt].t = {kBfNoneF, kBfNoneF};
     }
     f32x16 pos[2];
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        pos[0][e] = (float)bf_pos(0, e);
-        pos[1][e] = (float)bf_pos(1, e);
+        pos[0][e] = (float)(kBfBias + bf_pos(0, e));
+        pos[1][e] = (float)(kBfBias + bf_pos(1, e));
     }
     const int lrow = tid & 63, lcp = tid >> 6;
     struct Raw { uint32_t w[kBfWords]; };
@@ -447,29 +475,48 @@ __device__ __forceinline__ void bf_fp4_body(
         const int cur = t & 1;
         const RawT raw2 = fetch_any(t + 2);
         const int valid = nr - t * kBfRefs - 4 * h;
-        // fragment ring, two reads ahead: fragment f = 4 p + c is chunk c of m-tile p & 1
-        auto frag = [&](int f) { return tile[cur][2 * (f & 3) + h][32 * ((f >> 2) & 1) + col]; };
-        i32x4 a = frag(0), a1 = frag(1);
+        // Reference fragment g = 4 mt + c is chunk c of m-tile mt.  The chains run m-tile major
+        // (p = 2 mt + nt), so both query halves consume a fragment from registers and each of the
+        // 8 fragments is read from LDS once per tile: 0 and 1 at the head, 2 and 3 two MFMAs
+        // ahead of their first use, 4 .. 7 three ahead, each into the registers of a fragment
+        // whose second use has issued (16 fragment VGPRs live).
+        auto frag = [&](int g) { return tile[cur][2 * (g & 3) + h][32 * (g >> 2) + col]; };
+        i32x4 fr[8];
+        fr[0] = frag(0);
+        fr[1] = frag(1);
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            const int mt = p & 1, nt = p >> 1;
-            const int pmt = (p + 3) & 1, pnt = ((p + 3) & 3) >> 1;
+            const int mt = p >> 1, nt = p & 1;
+            const int pmt = ((p + 3) & 3) >> 1, pnt = (p + 3) & 1;
             f32x16 acc;
+            // chain p - 1 of this tile may be partial; chain 3 of the previous tile not
+            auto key = [&](int e) {
+                return partial && p > 0 && bf_pos(pmt, e) >= valid ? kBfNoneF : accp[e];
+            };
+            BfPairF ru{}, rv{}, rw{};
+            if (p == 0) st[0].close((t - 1) * kBfRefs);  // complete since chain 3 of tile t - 1
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const int f = 4 * p + c;
-                i32x4 a2 = a1;
-                if (f + 2 < 16) a2 = frag(f + 2);
+                const int rd = f < 2 ? f + 2 : (f >= 5 && f <= 8) ? f - 1 : -1;  // fragment read in this gap
+                if (rd >= 0) fr[rd] = frag(rd);
+                const i32x4 a = fr[4 * mt + c];
                 const i32x8 av = i32x8{a[0], a[1], a[2], a[3], 0, 0, 0, 0};
                 const i32x8 bv = i32x8{bq[nt][c][0], bq[nt][c][1], bq[nt][c][2], bq[nt][c][3], 0, 0, 0, 0};
                 acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, c ? acc : pos[mt], 4, 4, 0,
                                                                        scale_a, 0, scale_b);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = 4 * c + u;
-                    float k = accp[e];
-                    if (partial && p > 0 && bf_pos(pmt, e) >= valid) k = kBfNoneF;
-                    st[pnt].push(k);
+                // the previous chain's 16 keys through the ternary tree, a part per gap
+                if (c == 0) {
+                    ru = bf_top2(key(0), key(1), key(2));
+                    rv = bf_top2(key(3), key(4), key(5));
+                } else if (c == 1) {
+                    ru = bf_merge3(ru, rv, bf_top2(key(6), key(7), key(8)));
+                } else if (c == 2) {
+                    rv = bf_top2(key(9), key(10), key(11));
+                    rw = bf_top2(key(12), key(13), key(14));
+                } else {
+                    ru = bf_push(bf_merge3(ru, rv, rw), key(15));
+                    st[pnt].t = pmt ? bf_merge2(st[pnt].t, ru) : ru;
                 }
                 // next tile's expansion: word f / 8 of this thread's kBfWords at gap f % 8 == 7
                 if (f % 8 == 7 && (f >> 3) < kBfWords) {
@@ -478,15 +525,14 @@ __device__ __forceinline__ void bf_fp4_body(
                     else
                         tile[cur ^ 1][kBfWords * lcp + (f >> 3)][lrow] = ref_fp4(raw.w[f >> 3]);
                 }
-                a = a1;
-                a1 = a2;
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // fragment read, 2 ahead
+                if (rd >= 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // fragment read
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
                 __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);  // fillers
                 __builtin_amdgcn_sched_barrier(0);
             }
+            // tile t - 1 closes in the gaps of chains 0 and 1, each beside the ranking of the
+            // other n-tile (for t = 0 a no-op merge of "never wins" keys)
             if (p == 0) st[1].close((t - 1) * kBfRefs);
-            if (p == 2) st[0].close(t * kBfRefs);
             accp = acc;
         }
         raw = raw2;
@@ -497,7 +543,8 @@ __device__ __forceinline__ void bf_fp4_body(
     if (ntiles) {
         const int valid = nr - (ntiles - 1) * kBfRefs - 4 * h;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) st[1].push(bf_pos(1, e) < valid ? accp[e] : kBfNoneF);
+        for (int e = 0; e < 16; ++e) st[1].t = bf_push(st[1].t, bf_pos(1, e) < valid ? accp[e] : kBfNoneF);
+        st[0].close((ntiles - 1) * kBfRefs);
         st[1].close((ntiles - 1) * kBfRefs);
     }
     int best[2] = {st[0].best, st[1].best}, second[2] = {st[0].second, st[1].second};
@@ -511,7 +558,7 @@ __device__ __forceinline__ void bf_fp4_body(
     const int qi = q0 + 32 * h + col;
     if (qi < nq) {
         const int kb = h ? best[1] : best[0], ks = h ? second[1] : second[0];
-        const int pc = h ? popc[1] : popc[0];
+        const int pc = (h ? popc[1] : popc[0]) - 256;  // the keys hold X + 256
         const int db = (kb >> 16) + pc;
         int* o = out + ((long long)b * nq_cap + qi) * 3;
         o[0] = db >= 256 ? -1 : (kb & 0xffff);
