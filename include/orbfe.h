@@ -250,6 +250,15 @@ int orbfe_profile_read(orbfe_extractor* h, double* total_ms, int32_t* launches);
 #define ORBFE_PYR_PER_LEVEL 0
 #define ORBFE_PYR_BANDS     1
 int orbfe_pyramid_path(const orbfe_extractor* h, int nframes);
+/* How that extraction makes the small top levels (a test hook as well): ORBFE_TAIL_NONE (no
+ * resize_tail_kernel launch: the band kernel, a batch below the tail's minimum, or no run of
+ * top levels that fits), ORBFE_TAIL_GATHER (its horizontal pass by byte gathers: scale factors
+ * without column-group tables, ORBFE_RESIZE_TABLE=0), ORBFE_TAIL_TABLE (on the column-group
+ * tables). */
+#define ORBFE_TAIL_NONE   0
+#define ORBFE_TAIL_GATHER 1
+#define ORBFE_TAIL_TABLE  2
+int orbfe_pyramid_tail(const orbfe_extractor* h, int nframes);
 /* Measurement hook: relaunch the stages in `stage_mask` (bits 1 << ORBFE_STAGE_*) of the most
  * recent extraction on its own buffers, `reps` times, asynchronously on the handle's stream
  * (outputs meaningful only for a full mask). */

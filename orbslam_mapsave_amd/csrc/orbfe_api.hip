@@ -242,7 +242,8 @@ struct orbfe_extractor {
         bool pyr_batch_band = env_is("ORBFE_PYR_BATCH", "band");
         // ORBFE_RS2=0: one resize launch per level where resize2_kernel would take two (A/B)
         bool use_rs2 = env_on("ORBFE_RS2");
-        // ORBFE_RESIZE_TABLE=0: resize_kernel's horizontal pass by byte gathers (A/B)
+        // ORBFE_RESIZE_TABLE=0: resize_kernel's and resize_tail_kernel's horizontal pass by byte
+        // gathers (A/B)
         bool table_off = env_is("ORBFE_RESIZE_TABLE", "0");
         // ORBFE_DESC_MFMA=0: describe blurs its raw windows on the VALU instead of the matrix cores
         bool desc_mfma = env_on("ORBFE_DESC_MFMA");
@@ -525,18 +526,28 @@ struct orbfe_extractor {
                          p.lds[l], stream, ra);
     }
 
+    // resize_tail_kernel's horizontal pass runs on the column-group tables (else byte gathers)
+    bool tail_table() const { return plan.pyr.ok && !sw.table_off; }
+    // first level resize_tail_kernel makes for a batch of n frames (nlevels: no tail launch)
+    int tail_start(int n) const {
+        return n >= kTailMinFrames ? std::min(plan.pyr.tail_start, plan.geo.nlevels) : plan.geo.nlevels;
+    }
+
     // K1b: levels ts .. L - 1 from level ts - 1, a workgroup per frame (resize_tail_kernel)
     void launch_tail(int n, const LevelPtr* lp, int ts) {
         const Geo& geo = plan.geo;
         ResizeTailArgs ta;
         ta.src = lp[ts - 1], ta.sh = geo.lv[ts - 1].h, ta.nt = geo.nlevels - ts;
-        ta.lp[0] = (geo.lv[ts - 1].w + 15) & ~15;  // 16-byte chunk staging
+        ta.cpr0 = (geo.lv[ts - 1].w + 15) >> 4;  // 16-byte chunk staging
+        ta.lp[0] = tail_pitch0(geo.lv[ts - 1].w);
         ta.buf_b = ta.lp[0] * ta.sh;
+        const bool table = tail_table();
         for (int k = 0; k < ta.nt; ++k) {
             const int l = ts + k;
-            ta.lp[k + 1] = (geo.lv[l].w + 3) & ~3;
+            ta.lp[k + 1] = tail_pitch(geo.lv[l].w);
             ta.dw[k] = geo.lv[l].w, ta.dh[k] = geo.lv[l].h;
             ta.xt[k] = xt(l), ta.yt[k] = yt(l), ta.simd_xb[k] = xb_resize(ta.dw[k]);
+            ta.gtab[k] = table ? gtab(l) : nullptr;
             ta.dst[k] = lp[l];
         }
         ORBFE_LAUNCH_X86(x86(), prof, ORBFE_STAGE_RESIZE, resize_tail_kernel, dim3(n), dim3(kTailBlock), 0,
@@ -550,7 +561,7 @@ struct orbfe_extractor {
     void launch_pyramid(int n, const LevelPtr* lp) {
         if (band_path(n)) return launch_bands(n, lp);
         const int L = plan.geo.nlevels;
-        const int ts = n >= kTailMinFrames ? std::min(plan.pyr.tail_start, L) : L;
+        const int ts = tail_start(n);
         for (int l = 1; l < ts; ++l) {
             // levels l and l + 1 in one launch where planned; ORBFE_RS2=0: one launch per level
             if (sw.use_rs2 && l + 1 < ts && plan.pyr.rs2.ok[l] && !sw.table_off)
@@ -1368,6 +1379,12 @@ int orbfe_set_stage_mask(orbfe_extractor* h, unsigned stage_mask) {
 int orbfe_pyramid_path(const orbfe_extractor* h, int nframes) {
     if (!h || !h->planned || nframes < 1) return ORBFE_ERR_ARG;
     return h->band_path(nframes) ? ORBFE_PYR_BANDS : ORBFE_PYR_PER_LEVEL;
+}
+
+int orbfe_pyramid_tail(const orbfe_extractor* h, int nframes) {
+    if (!h || !h->planned || nframes < 1) return ORBFE_ERR_ARG;
+    if (h->band_path(nframes) || h->tail_start(nframes) >= h->plan.geo.nlevels) return ORBFE_TAIL_NONE;
+    return h->tail_table() ? ORBFE_TAIL_TABLE : ORBFE_TAIL_GATHER;
 }
 
 int orbfe_set_stream(orbfe_extractor* h, void* s) {

@@ -242,7 +242,7 @@ struct PyrArgs {
     int nlevels;
     int w[kMaxLevels];             // level widths
     int lp[kMaxLevels];            // LDS row pitch per level
-    int buf_b, ybuf, ymax;         // LDS offsets: second level buffer, y-table rows (2 x ymax)
+    int buf_b, ybuf, ymax;         // LDS offsets: second level buffer, row tables (2 x ymax int4)
     const int4* bands;             // [band][level] {c0, c1, w0, w1}: rows computed / written
     const uint4* gtab[kMaxLevels]; // per level >= 1: 3 uint4 per column group
     const int* yt[kMaxLevels];     // per level >= 1: the resize y table
@@ -254,10 +254,12 @@ struct ResizeTailArgs {
     int sh;                       // its rows
     int nt;                       // tail levels ts .. ts+nt-1
     int buf_b;                    // LDS offset of the second buffer
-    int lp[kMaxLevels + 1];       // LDS row pitch of level ts-1+k (k = 0 .. nt)
+    int cpr0;                     // 16-byte chunks per row of level ts-1
+    int lp[kMaxLevels + 1];       // LDS row pitch of level ts-1+k (k = 0 .. nt): tail_pitch0 / tail_pitch
     int dw[kMaxLevels], dh[kMaxLevels];
     const int* xt[kMaxLevels];
     const int* yt[kMaxLevels];
+    const uint4* gtab[kMaxLevels];  // per tail level: its column-group table; [0] null: byte gathers
     LevelPtr dst[kMaxLevels];
     int simd_xb[kMaxLevels];      // per tail level, as ResizeArgs::simd_xb
 };
@@ -282,32 +284,43 @@ constexpr int kTailMinFrames = 8;   // batches below this skip the one-workgroup
 // row coefficients b0 + b1 = 2048.  Scalar FixedPtCast<int, uchar, 22>: the sum is never
 // negative, so only the upper clamp remains (the signed min(max(x >> 22, 0), 255) form can be
 // matched to gfx950's v_ashr_pk_u8_i32 for two of four bytes, and that packing was seen to
-// corrupt the upper two).  With `sse2` the x86 body of VResizeLinearVec_32s8u (H5):
+// corrupt the upper two).  The x86 body of VResizeLinearVec_32s8u (H5) is resize4's:
 // ((((t0 >> 4) * b0) >> 16) + (((t1 >> 4) * b1) >> 16) + 2) >> 2, every operand < 2^24 (no
 // 16-bit saturation is reachable).  All products are full-rate v_mul_u32_u24.
-template <bool kX86>
-__device__ __forceinline__ uint32_t resize_px(uint32_t t0, uint32_t t1, uint32_t b0, uint32_t b1,
-                                              bool sse2) {
-    const uint32_t sc = (__umul24(t0, b0) + __umul24(t1, b1) + (1u << 21)) >> 22;
-    if constexpr (!kX86) return min(sc, 255u);
-    const uint32_t sv = ((__umul24(t0 >> 4, b0) >> 16) + (__umul24(t1 >> 4, b1) >> 16) + 2) >> 2;
-    return min(sse2 ? sv : sc, 255u);
+__device__ __forceinline__ uint32_t resize_px(uint32_t t0, uint32_t t1, uint32_t b0, uint32_t b1) {
+    return min((__umul24(t0, b0) + __umul24(t1, b1) + (1u << 21)) >> 22, 255u);
 }
 
 // ORBFE_RS_X86 — the x86 (H5) body formula ((t0 >> 4) * b0 >> 16) + ((t1 >> 4) * b1 >> 16) + 2
 // >> 2 (build-time A/B): 0 = shifts, multiplies, shifts and a clamp per pixel; 1 = the
 // horizontal sums scaled by 16 (hcoef) so each term is one AND + v_mul_hi_u32_u24; 2 = the +2
-// folded into the first product (v_mad_u32_u24) and both >> 16 into one SDWA add.
+// folded into the first product (v_mad_u32_u24) and both >> 16 into one SDWA add; 3 = the
+// horizontal sums scaled by 4096 (col_group: the source bytes in the high byte of each u16, the
+// coefficients times 16; 4096 t < 2^31), so t >> 4 is word 1 of a sum and b0 / b1 are words 0 /
+// 1 of the row's coefficient pair: each term is one SDWA v_mul_u32_u24 with no shift or unpack
+// before it, the + 2 and >> 2 run on two pixels per dword and one v_perm places the four bytes
+// (19 instructions per four pixels, 29 in mode 2).
 #ifndef ORBFE_RS_X86
-#define ORBFE_RS_X86 2
+#define ORBFE_RS_X86 3
 #endif
 constexpr int kRsX86 = ORBFE_RS_X86;
+// the horizontal sums feeding resize4 are t << kHShift<kX86>
+template <bool kX86>
+constexpr int kHShift = !kX86 ? 0 : kRsX86 == 3 ? 12 : kRsX86 == 1 ? 4 : 0;
 
 // Horizontal coefficient pairs (a0 | a1 << 16) as the horizontal passes feeding resize4 use
-// them: in mode 1 x86 scales both by 16 (a0, a1 <= 2049: each half stays below 2^16), so the
-// sums arrive as h = 16 t (< 2^23).
+// them: in modes 1 and 3 x86 scales both by 16 (a0, a1 <= 2049: each half stays below 2^16).
 template <bool kX86>
-__device__ __forceinline__ uint32_t hcoef(uint32_t a01) { return kX86 && kRsX86 == 1 ? a01 << 4 : a01; }
+__device__ __forceinline__ uint32_t hcoef(uint32_t a01) {
+    return kX86 && (kRsX86 == 1 || kRsX86 == 3) ? a01 << 4 : a01;
+}
+// The byte-gather form multiplies single source bytes, so its coefficients carry the whole
+// scale: a << kHShift <= 2049 * 4096 < 2^24, a source byte times it < 2^31.
+template <bool kX86>
+__device__ __forceinline__ void gather_coef(uint32_t a01, int& a0, int& a1) {
+    a0 = (int)((a01 & 0xffffu) << kHShift<kX86>);
+    a1 = (int)((a01 >> 16) << kHShift<kX86>);
+}
 
 // (P0 >> 16) + (P1 >> 16) in one VOP2 SDWA add (word 1 of each operand)
 __device__ __forceinline__ uint32_t add_hi16(uint32_t p0, uint32_t p1) {
@@ -316,19 +329,43 @@ __device__ __forceinline__ uint32_t add_hi16(uint32_t p0, uint32_t p1) {
         : "=v"(r) : "v"(p0), "v"(p1));
     return r;
 }
+// (h >> 16) * (bb & 0xffff) and (h >> 16) * (bb >> 16): one VOP2 SDWA multiply each
+__device__ __forceinline__ uint32_t mul_hi16_lo16(uint32_t h, uint32_t bb) {
+    uint32_t r;
+    asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0"
+        : "=v"(r) : "v"(h), "v"(bb));
+    return r;
+}
+__device__ __forceinline__ uint32_t mul_hi16_hi16(uint32_t h, uint32_t bb) {
+    uint32_t r;
+    asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1"
+        : "=v"(r) : "v"(h), "v"(bb));
+    return r;
+}
 
-// Four pixels of a row (columns x .. x + 3) from their horizontal sums (16 t in x86 mode 1,
-// else t).  x86: a group entirely inside the SSE2 body (x + 3 < xb, nearly every group) takes
-// the body formula alone; t >> 4 <= 32,655 and b0 + b1 <= 2049 keep the body's sum <= 1,022,
-// so it needs no clamp.  Groups reaching the scalar tail select per pixel.
+// Four pixels of a row (columns x .. x + 3) from their horizontal sums h = t << kHShift and the
+// row's coefficient pair bb = b0 | b1 << 16.  x86: a group entirely inside the SSE2 body (x + 3
+// < xb, nearly every group) takes the body formula alone; t >> 4 <= 32,655 and b0 + b1 <= 2049
+// keep the body's sum <= 1,022, so it needs no clamp.  Groups reaching the scalar tail select
+// per pixel.
 template <bool kX86>
 __device__ __forceinline__ uint32_t resize4(const uint32_t (&h0)[4], const uint32_t (&h1)[4],
-                                            uint32_t b0, uint32_t b1, int x, int xb) {
-    constexpr int kS = kX86 && kRsX86 == 1 ? 4 : 0;  // h >> kS = t
+                                            uint32_t bb, int x, int xb) {
+    constexpr int kS = kHShift<kX86>;  // h >> kS = t
     uint32_t packed = 0;
     if (kX86 && x + 3 < xb) {
+        if constexpr (kRsX86 == 3) {
+            uint32_t s[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s[k] = add_hi16(mul_hi16_lo16(h0[k], bb), mul_hi16_hi16(h1[k], bb));
+            // two sums (<= 1,020) per dword: + 2 and >> 2 leave each pixel in bytes 0 and 2
+            const uint32_t s01 = (((s[1] << 16) | s[0]) + 0x00020002u) >> 2;
+            const uint32_t s23 = (((s[3] << 16) | s[2]) + 0x00020002u) >> 2;
+            return __builtin_amdgcn_perm(s23, s01, 0x06040200u);
+        }
+        const uint32_t b0 = bb & 0xffffu, b1 = bb >> 16;
         if constexpr (kRsX86 == 1) {
-            const uint32_t c0 = (b0 & 0xffffu) << 8, c1 = (b1 & 0xffffu) << 8;  // < 2^24
+            const uint32_t c0 = b0 << 8, c1 = b1 << 8;  // < 2^24
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const uint32_t p0 = (uint32_t)(((unsigned long long)(h0[k] & 0x7fff00u) * c0) >> 32);
@@ -350,11 +387,68 @@ __device__ __forceinline__ uint32_t resize4(const uint32_t (&h0)[4], const uint3
                                ((uint32_t)__umul24(h1[k] >> 4, b1) >> 16) + 2u) >> 2, 255u) << (8 * k);
         }
     } else {
+        // (x86: the body bound is a multiple of 4, sse2_body_resize, so a group that is not
+        // wholly inside the body lies wholly in the scalar tail: no per-pixel choice.  A wave
+        // that holds one such group walks this path beside the body's for all its lanes.)
+        const uint32_t b0 = bb & 0xffffu, b1 = bb >> 16;
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-            packed |= resize_px<kX86>(h0[k] >> kS, h1[k] >> kS, b0, b1, x + k < xb) << (8 * k);
+        for (int k = 0; k < 4; ++k) packed |= resize_px(h0[k] >> kS, h1[k] >> kS, b0, b1) << (8 * k);
     }
     return packed;
+}
+
+// The horizontal pass on the column-group tables (pyramid_group_table: 3 uint4 per group of 4
+// output columns), shared by resize_kernel, resize2_kernel, resize_tail_kernel and
+// pyramid_kernel.  A thread keeps its group's entry for all its rows: the first source column,
+// the four v_perm selectors and the four coefficient pairs.  x86 mode 3 moves the two source
+// bytes of each selector to the high byte of its u16 (kHShift).
+typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+struct ColGroup {
+    int x0;
+    uint32_t sel[4];
+    us2 cf[4];
+};
+template <bool kX86>
+__device__ __forceinline__ ColGroup col_group(const uint4 g0, const uint4 g1, const uint4 g2) {
+    ColGroup c;
+    c.x0 = (int)g0.x;
+    const uint32_t sel[4] = {g0.y, g0.z, g0.w, g1.x}, cf[4] = {g1.y, g1.z, g1.w, g2.x};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        // {o0, 0x0c, o1, 0x0c} -> {0x0c, o0, 0x0c, o1} (0x0c selects a zero byte)
+        c.sel[k] = kX86 && kRsX86 == 3 ? __builtin_amdgcn_perm(sel[k], 0x0c0c0c0cu, 0x06000400u) : sel[k];
+        c.cf[k] = __builtin_bit_cast(us2, hcoef<kX86>(cf[k]));
+    }
+    return c;
+}
+// Horizontal sums of four output columns from one source row in LDS.  row: the row's dword
+// holding the group's first source column; sh: that column's byte in the dword.  3 dword LDS
+// reads, an 8-byte window by two v_alignbyte, v_perm + v_dot2 per pixel.  The window may reach
+// up to 8 bytes past the row's last column: no selector picks those bytes.
+__device__ __forceinline__ void hsum4(const unsigned char* row, int sh, const ColGroup& c, uint32_t (&t)[4]) {
+    const uint32_t* r = reinterpret_cast<const uint32_t*>(row);
+    const uint32_t w0 = r[0], w1 = r[1], w2 = r[2];
+    const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, sh), hi = __builtin_amdgcn_alignbyte(w2, w1, sh);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        t[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(hi, lo, c.sel[k])), c.cf[k], 0u, false);
+}
+// n <= 4 pixels of a packed group to the pyramid
+__device__ __forceinline__ void store_px(uint8_t* o, uint32_t packed, int n) {
+    if (n == 4) {
+        *reinterpret_cast<uint32_t*>(o) = packed;
+    } else {  // 1 <= n <= 3: byte stores under the lane mask, no loop
+        o[0] = (uint8_t)packed;
+        if (n > 1) o[1] = (uint8_t)(packed >> 8);
+        if (n > 2) o[2] = (uint8_t)(packed >> 16);
+    }
+}
+// A row-table entry as the row loops read it from LDS: the LDS byte offsets of the row's two
+// source rows from the staged image's first row, and the coefficient pair b0 | b1 << 16.  Made
+// once per row and workgroup from the y table's {sy0, sy1, b0 | b1 << 16} while the image is
+// staged, so a loop iteration adds its column offset and multiplies nothing.
+__device__ __forceinline__ int4 row_entry(const int* yt3, int row0, int pitch) {
+    return make_int4((yt3[0] - row0) * pitch, (yt3[1] - row0) * pitch, yt3[2], 0);
 }
 
 #ifndef ORBFE_RS_TH
@@ -400,37 +494,19 @@ __global__ __launch_bounds__(256) void resize_kernel(ResizeArgs a) {
         // pyramid_kernel's horizontal pass (the level's column-group table): 3 dword LDS reads
         // per source row, an 8-byte window by v_alignbyte, v_perm + v_dot2 per pixel, instead of
         // 4 byte gathers, 4 multiplies and 2 adds per pixel
-        typedef unsigned short us2 __attribute__((ext_vector_type(2)));
         const uint4* gp = a.gtab + 3 * (x >> 2);
-        const uint4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
-        const int base = (int)g0.x - sx0, wofs = base & ~3, sh = base & 3;
-        const uint32_t sel[4] = {g0.y, g0.z, g0.w, g1.x};
-        const us2 cf[4] = {__builtin_bit_cast(us2, hcoef<kX86>(g1.y)), __builtin_bit_cast(us2, hcoef<kX86>(g1.z)),
-                           __builtin_bit_cast(us2, hcoef<kX86>(g1.w)), __builtin_bit_cast(us2, hcoef<kX86>(g2.x))};
-        auto hsum = [&](int r, uint32_t (&t)[4]) {
-            const uint32_t* row = reinterpret_cast<const uint32_t*>(rs_lds + r * P + wofs);
-            const uint32_t w0 = row[0], w1 = row[1], w2 = row[2];
-            const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, sh), hi = __builtin_amdgcn_alignbyte(w2, w1, sh);
+        const ColGroup cg = col_group<kX86>(gp[0], gp[1], gp[2]);
+        const int base = cg.x0 - sx0, wofs = base & ~3, sh = base & 3;
+        const int y0 = oy + kRsRPT * ty;
+        uint32_t doff = (uint32_t)y0 * (uint32_t)a.dst.pitch + (uint32_t)x;  // a frame is < 2^31 bytes
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                t[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(hi, lo, sel[k])), cf[k], 0u, false);
-        };
-#pragma unroll
-        for (int j = 0; j < kRsRPT; ++j) {
-            const int y = oy + kRsRPT * ty + j;
-            if (y >= a.dh) break;
-            const int ry0 = ytr[j][0] - sy0, ry1 = ytr[j][1] - sy0, bb = ytr[j][2];
-            const uint32_t b0 = (uint32_t)bb & 0xffffu, b1 = (uint32_t)bb >> 16;
+        for (int j = 0; j < kRsRPT; ++j, doff += (uint32_t)a.dst.pitch) {
+            if (y0 + j >= a.dh) break;
+            const int4 e = row_entry(ytr[j], sy0, P);
             uint32_t t0[4], t1[4];
-            hsum(ry0, t0);
-            hsum(ry1, t1);
-            const uint32_t packed = resize4<kX86>(t0, t1, b0, b1, x, a.simd_xb);
-            uint8_t* d = dst + (long long)y * a.dst.pitch + x;
-            if (n == 4) {
-                *reinterpret_cast<uint32_t*>(d) = packed;
-            } else {
-                for (int k = 0; k < n; ++k) d[k] = (uint8_t)(packed >> (8 * k));
-            }
+            hsum4(rs_lds + e.x + wofs, sh, cg, t0);
+            hsum4(rs_lds + e.y + wofs, sh, cg, t1);
+            store_px(dst + doff, resize4<kX86>(t0, t1, (uint32_t)e.z, x, a.simd_xb), n);
         }
         return;
     }
@@ -440,16 +516,13 @@ __global__ __launch_bounds__(256) void resize_kernel(ResizeArgs a) {
         const int dx = min(x + k, a.dw - 1);
         x0[k] = a.xt[3 * dx] - sx0;
         x1[k] = a.xt[3 * dx + 1] - sx0;
-        const int aa = a.xt[3 * dx + 2];
-        a0[k] = (int)(hcoef<kX86>((uint32_t)aa) & 0xffffu);  // x86: 16 a0, 16 a1 (hcoef)
-        a1[k] = (int)(hcoef<kX86>((uint32_t)aa) >> 16);
+        gather_coef<kX86>((uint32_t)a.xt[3 * dx + 2], a0[k], a1[k]);
     }
 #pragma unroll
     for (int j = 0; j < kRsRPT; ++j) {
         const int y = oy + kRsRPT * ty + j;
         if (y >= a.dh) break;
         const int ry0 = ytr[j][0] - sy0, ry1 = ytr[j][1] - sy0, bb = ytr[j][2];
-        const int b0 = bb & 0xffff, b1 = (int)((unsigned)bb >> 16);
         const uint8_t* s0 = rs_lds + ry0 * P;
         const uint8_t* s1 = rs_lds + ry1 * P;
         uint32_t t0[4], t1[4];
@@ -460,13 +533,7 @@ __global__ __launch_bounds__(256) void resize_kernel(ResizeArgs a) {
             t0[k] = __umul24(s0[x0[k]], a0[k]) + __umul24(s0[x1[k]], a1[k]);
             t1[k] = __umul24(s1[x0[k]], a0[k]) + __umul24(s1[x1[k]], a1[k]);
         }
-        const uint32_t packed = resize4<kX86>(t0, t1, b0, b1, x, a.simd_xb);
-        uint8_t* d = dst + (long long)y * a.dst.pitch + x;
-        if (n == 4) {
-            *reinterpret_cast<uint32_t*>(d) = packed;
-        } else {
-            for (int k = 0; k < n; ++k) d[k] = (uint8_t)(packed >> (8 * k));
-        }
+        store_px(dst + (long long)y * a.dst.pitch + x, resize4<kX86>(t0, t1, (uint32_t)bb, x, a.simd_xb), n);
     }
 }
 
@@ -487,72 +554,58 @@ __global__ __launch_bounds__(256) void resize2_kernel(Resize2Args a) {
     const int4 c = a.tiles[2 * bx], own = a.tiles[2 * bx + 1];
     const int tid = threadIdx.x;
     const int oy = (bx / a.tiles_x) * kRsTH;
-    // The row tables both passes walk (level l's rows c.x .. c.y, the tile's level l + 1 rows),
-    // staged in LDS beside the image rows: read from global inside the row loops they cost one
-    // round trip per row.  Loads and stores unconditional at clamped indices.
-    __shared__ int ytm_s[3 * kR2Rows];  // c.y - c.x < kR2Rows (host plan)
-    __shared__ int ytd_s[3 * kRsTH];
-    static_assert(3 * kRsTH <= 256, "ytd_s is filled with one entry per thread (ORBFE_RS_TH <= 85)");
-    {
-        const int n3 = 3 * (c.y - c.x + 1);
-        const int i0 = min(tid, n3 - 1), i1 = min(tid + 256, n3 - 1), i2 = min(tid, 3 * kRsTH - 1);
-        const int yd = min(oy + i2 / 3, a.dh - 1);
-        const int v0 = a.yt_m[3 * c.x + i0], v1 = a.yt_m[3 * c.x + i1], v2 = a.yt_d[3 * yd + i2 % 3];
-        ytm_s[i0] = v0;
-        ytm_s[i1] = v1;
-        ytd_s[i2] = v2;
-    }
     // level l - 1 rectangle the level-l region reads
     const int ay0 = a.yt_m[3 * c.x], ay1 = a.yt_m[3 * c.y + 1];
     const int ax0 = a.xt_m[3 * c.z] & ~3, ax1 = a.xt_m[3 * c.w + 1];
+    // The row tables both passes walk (level l's rows c.x .. c.y, then the tile's level l + 1
+    // rows), staged in LDS beside the image rows as row_entry: read from global inside the row
+    // loops they cost one round trip per row.  Threads 0 .. 127 make level l's entries, 128 ..
+    // 255 level l + 1's; loads and stores unconditional at clamped indices.
+    __shared__ int4 rows_s[kR2Rows + kRsTH];  // c.y - c.x < kR2Rows (host plan)
+    static_assert(kR2Rows <= 128 && kRsTH <= 128, "one row-table entry per thread");
+    const int nrows = c.y - c.x + 1;
+    {
+        const bool up = tid >= 128;
+        const int i = up ? min(tid - 128, kRsTH - 1) : min(tid, nrows - 1);
+        const int* yt3 = up ? a.yt_d + 3 * min(oy + i, a.dh - 1) : a.yt_m + 3 * (c.x + i);
+        rows_s[up ? kR2Rows + i : i] = row_entry(yt3, up ? c.x : ay0, up ? a.pb : a.pa);
+    }
     {
         const int nrow = ay1 - ay0 + 1, cpr = ((ax1 - ax0) >> 4) + 1, total = nrow * cpr;
         const uint8_t* src = a.src.base + f * a.src.fpitch;
         stage_rows16<256>(src, a.src.pitch, ay0, ax0, a.sw, cpr, total, r2_lds, a.pa, tid);
     }
     __syncthreads();
-    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-    // one thread per (column group, row phase): the group's table entry loaded once
-    auto hsum = [&](const unsigned char* base, int pitch, int r, int wofs, int sh, const uint32_t (&sel)[4],
-                    const us2 (&cf)[4], uint32_t (&t)[4]) {
-        const uint32_t* row = reinterpret_cast<const uint32_t*>(base + r * pitch + wofs);
-        const uint32_t w0 = row[0], w1 = row[1], w2 = row[2];
-        const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, sh), hi = __builtin_amdgcn_alignbyte(w2, w1, sh);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            t[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(hi, lo, sel[k])), cf[k], 0u, false);
-    };
     unsigned char* B = r2_lds + a.bofs;
-    {   // level l region: rows c.x .. c.y, column groups c.z / 4 .. c.w / 4
+    {   // level l region: rows c.x .. c.y, column groups c.z / 4 .. c.w / 4; one thread per
+        // (column group, row phase), the group's table entry loaded once
         const int gpr = ((c.w - c.z) >> 2) + 1, rps = 256 / gpr;
         const int gx = tid % gpr, ry = tid / gpr;
         if (ry < rps) {
             const int x = c.z + 4 * gx;
             const uint4* gp = a.gtab_m + 3 * (x >> 2);
-            const uint4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
-            const int xrel = (int)g0.x - ax0, wofs = (xrel >> 2) << 2, sh = xrel & 3;
-            const uint32_t sel[4] = {g0.y, g0.z, g0.w, g1.x};
-            const us2 cf[4] = {__builtin_bit_cast(us2, hcoef<kX86>(g1.y)), __builtin_bit_cast(us2, hcoef<kX86>(g1.z)),
-                               __builtin_bit_cast(us2, hcoef<kX86>(g1.w)), __builtin_bit_cast(us2, hcoef<kX86>(g2.x))};
+            const ColGroup cg = col_group<kX86>(gp[0], gp[1], gp[2]);
+            const int xrel = cg.x0 - ax0, wofs = xrel & ~3, sh = xrel & 3;
             const int n = min(4, a.mw - x);
             const bool own_x = x >= own.z && x < own.w;  // own column bounds are multiples of 4
             uint8_t* mid = const_cast<uint8_t*>(a.mid.base) + f * a.mid.fpitch;
-            for (int r = c.x + ry; r <= c.y; r += rps) {
-                const int* yy = ytm_s + 3 * (r - c.x);
-                const uint32_t b0 = (uint32_t)yy[2] & 0xffffu, b1 = (uint32_t)yy[2] >> 16;
+            // Row i = j + jo of the region; the rows this tile owns are j in [0, jn) (none where
+            // the column group is not its own), one unsigned compare.  Every offset the loop
+            // uses advances by a workgroup-uniform step.
+            const int jo = own.x - c.x;
+            const uint32_t jn = own_x ? (uint32_t)(own.y - own.x) : 0u;
+            int eoff = ry * (int)sizeof(int4), boff = a.bofs + ry * a.pb + (x - c.z);
+            uint32_t moff = (uint32_t)(c.x + ry) * (uint32_t)a.mid.pitch + (uint32_t)x;  // a frame is < 2^31 bytes
+            const int estep = rps * (int)sizeof(int4), bstep = rps * a.pb;
+            const uint32_t mstep = (uint32_t)rps * (uint32_t)a.mid.pitch;
+            for (int j = ry - jo; j < nrows - jo; j += rps, eoff += estep, boff += bstep, moff += mstep) {
+                const int4 e = *reinterpret_cast<const int4*>(reinterpret_cast<const unsigned char*>(rows_s) + eoff);
                 uint32_t t0[4], t1[4];
-                hsum(r2_lds, a.pa, yy[0] - ay0, wofs, sh, sel, cf, t0);
-                hsum(r2_lds, a.pa, yy[1] - ay0, wofs, sh, sel, cf, t1);
-                const uint32_t packed = resize4<kX86>(t0, t1, b0, b1, x, a.xb_m);
-                *reinterpret_cast<uint32_t*>(B + (r - c.x) * a.pb + (x - c.z)) = packed;
-                if (own_x && r >= own.x && r < own.y) {
-                    uint8_t* o = mid + (long long)r * a.mid.pitch + x;
-                    if (n == 4) {
-                        *reinterpret_cast<uint32_t*>(o) = packed;
-                    } else {
-                        for (int k = 0; k < n; ++k) o[k] = (uint8_t)(packed >> (8 * k));
-                    }
-                }
+                hsum4(r2_lds + e.x + wofs, sh, cg, t0);
+                hsum4(r2_lds + e.y + wofs, sh, cg, t1);
+                const uint32_t packed = resize4<kX86>(t0, t1, (uint32_t)e.z, x, a.xb_m);
+                *reinterpret_cast<uint32_t*>(r2_lds + boff) = packed;
+                if ((uint32_t)j < jn) store_px(mid + moff, packed, n);
             }
         }
     }
@@ -565,28 +618,20 @@ __global__ __launch_bounds__(256) void resize2_kernel(Resize2Args a) {
         if (x >= a.dw) return;
         const int n = min(4, a.dw - x);
         const uint4* gp = a.gtab_d + 3 * (x >> 2);
-        const uint4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
-        const int xrel = (int)g0.x - c.z, wofs = (xrel >> 2) << 2, sh = xrel & 3;
-        const uint32_t sel[4] = {g0.y, g0.z, g0.w, g1.x};
-        const us2 cf[4] = {__builtin_bit_cast(us2, hcoef<kX86>(g1.y)), __builtin_bit_cast(us2, hcoef<kX86>(g1.z)),
-                           __builtin_bit_cast(us2, hcoef<kX86>(g1.w)), __builtin_bit_cast(us2, hcoef<kX86>(g2.x))};
+        const ColGroup cg = col_group<kX86>(gp[0], gp[1], gp[2]);
+        const int xrel = cg.x0 - c.z, wofs = xrel & ~3, sh = xrel & 3;
         uint8_t* dst = const_cast<uint8_t*>(a.dst.base) + f * a.dst.fpitch;
+        const int y0 = oy + kRsRPT * ty;
+        const int4* ee = rows_s + kR2Rows + kRsRPT * ty;
+        uint32_t doff = (uint32_t)y0 * (uint32_t)a.dst.pitch + (uint32_t)x;
 #pragma unroll
-        for (int j = 0; j < kRsRPT; ++j) {
-            const int y = oy + kRsRPT * ty + j;
-            if (y >= a.dh) break;
-            const int* yy = ytd_s + 3 * (y - oy);
-            const uint32_t b0 = (uint32_t)yy[2] & 0xffffu, b1 = (uint32_t)yy[2] >> 16;
+        for (int j = 0; j < kRsRPT; ++j, doff += (uint32_t)a.dst.pitch) {
+            if (y0 + j >= a.dh) break;
+            const int4 e = ee[j];
             uint32_t t0[4], t1[4];
-            hsum(B, a.pb, yy[0] - c.x, wofs, sh, sel, cf, t0);
-            hsum(B, a.pb, yy[1] - c.x, wofs, sh, sel, cf, t1);
-            const uint32_t packed = resize4<kX86>(t0, t1, b0, b1, x, a.xb_d);
-            uint8_t* o = dst + (long long)y * a.dst.pitch + x;
-            if (n == 4) {
-                *reinterpret_cast<uint32_t*>(o) = packed;
-            } else {
-                for (int k = 0; k < n; ++k) o[k] = (uint8_t)(packed >> (8 * k));
-            }
+            hsum4(B + e.x + wofs, sh, cg, t0);
+            hsum4(B + e.y + wofs, sh, cg, t1);
+            store_px(dst + doff, resize4<kX86>(t0, t1, (uint32_t)e.z, x, a.xb_d), n);
         }
     }
 }
@@ -691,9 +736,11 @@ __global__ __launch_bounds__(kPyrBlock) void pyramid_kernel(PyrArgs a) {
         const int nrows = bl.y - bl.x + 1;  // may be 0 for a thin band of a small level
         const int w = a.w[l], gpr = (w + 3) >> 2, rps = kPyrBlock / gpr;
         const int gx = tid % gpr, ry = tid / gpr;
-        // this level's y-table rows, and the thread's column group (issued before the barrier)
-        int* yb = reinterpret_cast<int*>(py_lds + a.ybuf) + ((l & 1) ? 3 * a.ymax : 0);
-        for (int i = tid; i < 3 * nrows; i += kPyrBlock) yb[i] = a.yt[l][3 * bl.x + i];
+        // this level's row table as row_entry, and the thread's column group (issued before the
+        // barrier)
+        const int sp = a.lp[l - 1], dpitch = a.lp[l];
+        int4* yb = reinterpret_cast<int4*>(py_lds + a.ybuf) + ((l & 1) ? a.ymax : 0);
+        for (int i = tid; i < nrows; i += kPyrBlock) yb[i] = row_entry(a.yt[l] + 3 * (bl.x + i), bs.x, sp);
         uint4 g0 = make_uint4(0u, 0u, 0u, 0u), g1 = g0, g2 = g0;
         if (ry < rps && nrows > 0) {
             const uint4* gp = a.gtab[l] + 3 * gx;
@@ -705,51 +752,40 @@ __global__ __launch_bounds__(kPyrBlock) void pyramid_kernel(PyrArgs a) {
         if (ry >= rps || nrows <= 0) continue;
         const uint8_t* s = py_lds + (((l - 1) & 1) ? a.buf_b : 0);
         uint8_t* d = py_lds + ((l & 1) ? a.buf_b : 0);
-        const int sp = a.lp[l - 1], dpitch = a.lp[l];
-        const int xbase = (int)g0.x, wofs = (xbase >> 2) << 2, sh = xbase & 3;
-        const uint32_t sel[4] = {g0.y, g0.z, g0.w, g1.x};
-        typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-        const us2 cf[4] = {__builtin_bit_cast(us2, hcoef<kX86>(g1.y)), __builtin_bit_cast(us2, hcoef<kX86>(g1.z)),
-                           __builtin_bit_cast(us2, hcoef<kX86>(g1.w)), __builtin_bit_cast(us2, hcoef<kX86>(g2.x))};
+        const ColGroup cg = col_group<kX86>(g0, g1, g2);
+        const int wofs = cg.x0 & ~3, sh = cg.x0 & 3;
         const int x = 4 * gx, n = min(4, w - x);
         const int xb = a.simd_xb[l];
         const LevelPtr dp = a.dst[l];
         uint8_t* dst = const_cast<uint8_t*>(dp.base) + f * dp.fpitch;
-        auto hsum = [&](int r, uint32_t (&t)[4]) {  // horizontal sums of source row r (LDS row)
-            const uint32_t* row = reinterpret_cast<const uint32_t*>(s + r * sp + wofs);
-            const uint32_t w0 = row[0], w1 = row[1], w2 = row[2];
-            const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, sh), hi = __builtin_amdgcn_alignbyte(w2, w1, sh);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                t[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(hi, lo, sel[k])), cf[k], 0u, false);
-        };
-        auto row_out = [&](int r) {
-            const int* yy = yb + 3 * (r - bl.x);
-            const int bb = yy[2];
-            const uint32_t b0 = (uint32_t)bb & 0xffffu, b1 = (uint32_t)bb >> 16;
+        // Row i = j + jo of the band's rows; the rows it writes to the pyramid are j in [0, jn).
+        // eoff / doff / goff: the row's table entry, its LDS row and its pyramid row (a frame is
+        // < 2^31 bytes); all advance by workgroup-uniform steps.
+        const int jo = bl.z - bl.x;
+        const uint32_t jn = (uint32_t)(bl.w - bl.z);
+        auto row_out = [&](int j, int eoff, int doff, uint32_t goff) {
+            const int4 e = *reinterpret_cast<const int4*>(reinterpret_cast<const unsigned char*>(yb) + eoff);
             uint32_t t0[4], t1[4];
-            hsum(yy[0] - bs.x, t0);
-            hsum(yy[1] - bs.x, t1);
-            const uint32_t packed = resize4<kX86>(t0, t1, b0, b1, x, xb);
-            *reinterpret_cast<uint32_t*>(d + (r - bl.x) * dpitch + x) = packed;
-            if (r >= bl.z && r < bl.w) {
-                uint8_t* o = dst + (long long)r * dp.pitch + x;
-                if (n == 4) {
-                    *reinterpret_cast<uint32_t*>(o) = packed;
-                } else {
-                    for (int k = 0; k < n; ++k) o[k] = (uint8_t)(packed >> (8 * k));
-                }
-            }
+            hsum4(s + e.x + wofs, sh, cg, t0);
+            hsum4(s + e.y + wofs, sh, cg, t1);
+            const uint32_t packed = resize4<kX86>(t0, t1, (uint32_t)e.z, x, xb);
+            *reinterpret_cast<uint32_t*>(d + doff) = packed;
+            if ((uint32_t)j < jn) store_px(dst + goff, packed, n);
         };
+        const int estep = rps * (int)sizeof(int4), dstep = rps * dpitch;
+        const uint32_t gstep = (uint32_t)rps * (uint32_t)dp.pitch;
+        int j = ry - jo, eoff = ry * (int)sizeof(int4), doff = ry * dpitch + x;
+        uint32_t goff = (uint32_t)(bl.x + ry) * (uint32_t)dp.pitch + (uint32_t)x;
+        const int jend = nrows - jo;
         // kPyrRows rows per iteration: their LDS reads are issued together.  (Runs of
         // consecutive rows per thread, summing a source row shared with the previous row once
         // — 1.2 instead of 2 sums per row — measured slower: 0.307 -> 0.334 ms)
-        int r = bl.x + ry;
-        for (; r + (kPyrRows - 1) * rps <= bl.y; r += kPyrRows * rps) {
+        for (; j + (kPyrRows - 1) * rps < jend;
+             j += kPyrRows * rps, eoff += kPyrRows * estep, doff += kPyrRows * dstep, goff += kPyrRows * gstep) {
 #pragma unroll
-            for (int j = 0; j < kPyrRows; ++j) row_out(r + j * rps);
+            for (int q = 0; q < kPyrRows; ++q) row_out(j + q * rps, eoff + q * estep, doff + q * dstep, goff + q * gstep);
         }
-        for (; r <= bl.y; r += rps) row_out(r);
+        for (; j < jend; j += rps, eoff += estep, doff += dstep, goff += gstep) row_out(j, eoff, doff, goff);
     }
 }
 
@@ -784,42 +820,62 @@ static bool pyramid_group_table(const std::vector<int>& xtab, int xoff, int dw, 
 // K1b — the small top levels in one launch: one 1024-thread workgroup per frame copies level
 // ts-1 into LDS, then makes levels ts .. L-1 one after the other, each from the previous one
 // held in LDS (two buffers, ping-pong), writing every level to the pyramid as well.  Same
-// host tables and integer arithmetic as resize_kernel.  Used when the two largest levels of
-// the tail fit the workgroup's LDS (levels 5-7 at 640 x 480).
+// host tables and integer arithmetic as resize_kernel: the horizontal pass on the column-group
+// tables (hsum4), or by byte gathers from the x tables where the plan has no group tables
+// (gtab null: scale factors whose source columns do not fit the 8-byte window, or
+// ORBFE_RESIZE_TABLE=0).  Used when the two largest levels of the tail fit the workgroup's LDS
+// (levels 5-7 at 640 x 480).
 constexpr int kTailBlock = 1024;
 constexpr int kTailLds = 144 * 1024;
-constexpr int kTailRows = 512;  // rows of a tail level whose y table is staged in LDS
+constexpr int kTailRows = 512;  // rows of a tail level whose row table is staged in LDS
+// LDS row pitches: level ts-1 in 16-byte chunks, the levels made here in dwords; both leave
+// the 8 bytes past a row's last dword that a column group's window read may reach (hsum4)
+// inside the row, so the last row's read stays inside its buffer.
+constexpr int tail_pitch0(int w) { return ((w + 15) & ~15) + 16; }
+constexpr int tail_pitch(int w) { return ((w + 3) & ~3) + 8; }
 template <bool kX86>
 __global__ __launch_bounds__(kTailBlock) void resize_tail_kernel(ResizeTailArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[kTailLds];
     const int f = blockIdx.x;
     const int tid = threadIdx.x;
-    // The tables of each level (its y table for LDS, this thread's four x entries) are loaded
+    const bool table = a.gtab[0] != nullptr;
+    // The tables of each level (a row's y-table entry for LDS, this thread's column group: its
+    // 3 uint4 of the group table, or its four x-table entries, 12 dwords either way) are loaded
     // one level ahead, so they arrive while the level before is made: loaded at the top of
     // their own level, each level began with two global round trips.  Loads unconditional at
-    // clamped indices (3 dh <= 3 kTailRows: entries tid and tid + kTailBlock).
-    static_assert(3 * kTailRows <= 2 * kTailBlock, "two y-table entries per thread");
-    int yn[2], xn[4][3];
+    // clamped indices (dh <= kTailRows: row tid).
+    static_assert(kTailRows <= kTailBlock, "one row-table entry per thread");
+    int yn[3];
+    uint32_t cn[12];
     auto fetch_tables = [&](int k) __attribute__((always_inline)) {
-        const int n3 = 3 * a.dh[k], dw = a.dw[k];
-        const int* yt = a.yt[k];
-        const int* xt = a.xt[k];
-        yn[0] = yt[min(tid, n3 - 1)];
-        yn[1] = yt[min(tid + kTailBlock, n3 - 1)];
-        const int x = 4 * (tid % ((dw + 3) >> 2));
+        const int dw = a.dw[k];
+        const int* yt = a.yt[k] + 3 * min(tid, a.dh[k] - 1);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int dx = min(x + q, dw - 1);
+        for (int e = 0; e < 3; ++e) yn[e] = yt[e];
+        const int gx = tid % ((dw + 3) >> 2);
+        if (table) {
+            const uint4* gp = a.gtab[k] + 3 * gx;
 #pragma unroll
-            for (int e = 0; e < 3; ++e) xn[q][e] = xt[3 * dx + e];
+            for (int q = 0; q < 3; ++q) {
+                const uint4 g = gp[q];
+                cn[4 * q] = g.x, cn[4 * q + 1] = g.y, cn[4 * q + 2] = g.z, cn[4 * q + 3] = g.w;
+            }
+        } else {
+            const int* xt = a.xt[k];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int dx = min(4 * gx + q, dw - 1);
+#pragma unroll
+                for (int e = 0; e < 3; ++e) cn[3 * q + e] = (uint32_t)xt[3 * dx + e];
+            }
         }
     };
     fetch_tables(0);
-    {   // level ts-1 from the pyramid in 16-byte chunks (LDS pitch lp[0] % 16 == 0, inside the
+    {   // level ts-1 from the pyramid in 16-byte chunks (whole chunks of its columns: inside the
         // slab's 64-byte row pitch), four per thread in flight before the LDS stores
         const LevelPtr sp = a.src;
         const uint8_t* src = sp.base + f * sp.fpitch;
-        const int cpr = a.lp[0] >> 4, total = a.sh * cpr;
+        const int cpr = a.cpr0, total = a.sh * cpr;
         for (int base = 0; base < total; base += 4 * kTailBlock) {
             uint4 v[4];
 #pragma unroll
@@ -837,25 +893,21 @@ __global__ __launch_bounds__(kTailBlock) void resize_tail_kernel(ResizeTailArgs 
         }
     }
     __syncthreads();
-    // the row tables of the level being made, staged in LDS: the row loop below would
-    // otherwise wait on three dependent global loads per iteration
-    __shared__ int yts[3 * kTailRows];
+    // the row table of the level being made, staged in LDS as row_entry: the row loop below
+    // would otherwise wait on three dependent global loads per iteration
+    __shared__ int4 yts[kTailRows];
     for (int k = 0; k < a.nt; ++k) {
         // (offsets from lds, not a pointer array: that would make every access a flat one)
         const uint8_t* s = lds + ((k & 1) ? a.buf_b : 0);
         uint8_t* d = lds + (((k + 1) & 1) ? a.buf_b : 0);
         const int sp_l = a.lp[k], dp_l = a.lp[k + 1];
         const int dw = a.dw[k], dh = a.dh[k], xb = a.simd_xb[k];
-        const int* yt = yts;
-        const int ycur[2] = {yn[0], yn[1]};
-        int xc[4][3];
+        const int ycur[3] = {yn[0], yn[1], yn[2]};
+        uint32_t cc[12];
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 3; ++e) xc[q][e] = xn[q][e];
+        for (int q = 0; q < 12; ++q) cc[q] = cn[q];
         if (k + 1 < a.nt) fetch_tables(k + 1);
-        yts[min(tid, 3 * dh - 1)] = ycur[0];
-        yts[min(tid + kTailBlock, 3 * dh - 1)] = ycur[1];
+        yts[min(tid, dh - 1)] = row_entry(ycur, 0, sp_l);
         __syncthreads();
         const int gpr = (dw + 3) >> 2;           // 4-pixel groups per row
         const int rps = kTailBlock / gpr;        // rows per sweep
@@ -865,33 +917,45 @@ __global__ __launch_bounds__(kTailBlock) void resize_tail_kernel(ResizeTailArgs 
         if (ry < rps) {
             const int x = 4 * gx;
             const int n = min(4, dw - x);
-            int x0[4], x1[4], a0[4], a1[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                x0[q] = xc[q][0];
-                x1[q] = xc[q][1];
-                const int aa = xc[q][2];
-                a0[q] = (int)(hcoef<kX86>((uint32_t)aa) & 0xffffu);  // x86: 16 a0, 16 a1 (hcoef)
-                a1[q] = (int)(hcoef<kX86>((uint32_t)aa) >> 16);
-            }
-            for (int y = ry; y < dh; y += rps) {
-                const int bb = yt[3 * y + 2];
-                const int b0 = bb & 0xffff, b1 = (int)((unsigned)bb >> 16);
-                const uint8_t* s0 = s + yt[3 * y] * sp_l;
-                const uint8_t* s1 = s + yt[3 * y + 1] * sp_l;
-                uint32_t t0[4], t1[4];
+            // the row's table entry, its LDS row and its pyramid row advance by uniform steps
+            int eoff = ry * (int)sizeof(int4), doff = ry * dp_l + x;
+            uint32_t goff = (uint32_t)ry * (uint32_t)dp.pitch + (uint32_t)x;
+            const int estep = rps * (int)sizeof(int4), dstep = rps * dp_l;
+            const uint32_t gstep = (uint32_t)rps * (uint32_t)dp.pitch;
+            if (table) {
+                const ColGroup cg = col_group<kX86>(make_uint4(cc[0], cc[1], cc[2], cc[3]), make_uint4(cc[4], cc[5], cc[6], cc[7]),
+                                                    make_uint4(cc[8], cc[9], cc[10], cc[11]));
+                const int wofs = cg.x0 & ~3, sh = cg.x0 & 3;
+                for (int y = ry; y < dh; y += rps, eoff += estep, doff += dstep, goff += gstep) {
+                    const int4 e = *reinterpret_cast<const int4*>(reinterpret_cast<const unsigned char*>(yts) + eoff);
+                    uint32_t t0[4], t1[4];
+                    hsum4(s + e.x + wofs, sh, cg, t0);
+                    hsum4(s + e.y + wofs, sh, cg, t1);
+                    const uint32_t packed = resize4<kX86>(t0, t1, (uint32_t)e.z, x, xb);
+                    *reinterpret_cast<uint32_t*>(d + doff) = packed;  // LDS pitch % 4 == 0
+                    store_px(dst + goff, packed, n);
+                }
+            } else {
+                int x0[4], x1[4], a0[4], a1[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    t0[q] = __umul24(s0[x0[q]], a0[q]) + __umul24(s0[x1[q]], a1[q]);
-                    t1[q] = __umul24(s1[x0[q]], a0[q]) + __umul24(s1[x1[q]], a1[q]);
+                    x0[q] = (int)cc[3 * q];
+                    x1[q] = (int)cc[3 * q + 1];
+                    gather_coef<kX86>(cc[3 * q + 2], a0[q], a1[q]);
                 }
-                const uint32_t packed = resize4<kX86>(t0, t1, b0, b1, x, xb);
-                *reinterpret_cast<uint32_t*>(d + y * dp_l + x) = packed;  // LDS pitch % 4 == 0
-                uint8_t* o = dst + (long long)y * dp.pitch + x;
-                if (n == 4) {
-                    *reinterpret_cast<uint32_t*>(o) = packed;
-                } else {
-                    for (int q = 0; q < n; ++q) o[q] = (uint8_t)(packed >> (8 * q));
+                for (int y = ry; y < dh; y += rps, eoff += estep, doff += dstep, goff += gstep) {
+                    const int4 e = *reinterpret_cast<const int4*>(reinterpret_cast<const unsigned char*>(yts) + eoff);
+                    const uint8_t* s0 = s + e.x;
+                    const uint8_t* s1 = s + e.y;
+                    uint32_t t0[4], t1[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        t0[q] = __umul24(s0[x0[q]], a0[q]) + __umul24(s0[x1[q]], a1[q]);
+                        t1[q] = __umul24(s1[x0[q]], a0[q]) + __umul24(s1[x1[q]], a1[q]);
+                    }
+                    const uint32_t packed = resize4<kX86>(t0, t1, (uint32_t)e.z, x, xb);
+                    *reinterpret_cast<uint32_t*>(d + doff) = packed;  // LDS pitch % 4 == 0
+                    store_px(dst + goff, packed, n);
                 }
             }
         }
@@ -3417,7 +3481,8 @@ static int plan_pyramid(Plan& g, int lds_cap_kb) {
     }
     {   // K1b: the longest run of top levels ts..L-1 (ts >= 2) whose two largest LDS images,
         // levels ts-1 and ts (rows padded to dwords), fit the tail kernel's LDS
-        auto bytes = [&](int l) { return (size_t)g.geo.lv[l].h * (((size_t)g.geo.lv[l].w + 15) & ~(size_t)15); };
+        // (both at tail_pitch0, the wider of the kernel's two row pitches)
+        auto bytes = [&](int l) { return (size_t)g.geo.lv[l].h * (size_t)tail_pitch0(g.geo.lv[l].w); };
         p.tail_start = L;
         for (int ts = L - 1; ts >= 2; --ts) {
             if (bytes(ts - 1) + bytes(ts) > (size_t)kTailLds || g.geo.lv[ts].h > kTailRows) break;
@@ -3472,7 +3537,7 @@ static int plan_pyramid(Plan& g, int lds_cap_kb) {
             }
             bufb = (int)((A + 15) & ~(size_t)15);
             ybuf = bufb + (int)((B + 15) & ~(size_t)15);
-            lds = (size_t)ybuf + 2 * 3 * (size_t)ymax * sizeof(int);
+            lds = (size_t)ybuf + 2 * (size_t)ymax * sizeof(int4);  // row_entry per row, two levels
         };
         const size_t cap = (size_t)lds_cap_kb * 1024;
         std::vector<int> bt[2];

@@ -42,7 +42,7 @@ EXPORTED = [
     "orbfe_extract_color", "orbfe_human_mask_rect", "orbfe_extract_batch",
     "orbfe_extract_batch_device", "orbfe_extract_color_batch_device", "orbfe_set_stream",
     "orbfe_synchronize", "orbfe_compute_stereo_matches", "orbfe_compute_stereo_matches_device",
-    "orbfe_stereo_status", "orbfe_profile", "orbfe_profile_read", "orbfe_pyramid_path", "orbfe_debug_replay", "orbfe_set_stage_mask", "orbfe_get_level", "orbfe_get_blurred_level", "orbfe_get_fast_keys",
+    "orbfe_stereo_status", "orbfe_profile", "orbfe_profile_read", "orbfe_pyramid_path", "orbfe_pyramid_tail", "orbfe_debug_replay", "orbfe_set_stage_mask", "orbfe_get_level", "orbfe_get_blurred_level", "orbfe_get_fast_keys",
     "orbfe_matcher_create", "orbfe_matcher_destroy", "orbfe_matcher_set_stream",
     "orbfe_matcher_profile", "orbfe_matcher_profile_read", "orbfe_matcher_profile_read_stages", "orbfe_hamming",
     "orbfe_bf_match", "orbfe_bf_match_batch_device", "orbfe_search_for_initialization",
@@ -116,6 +116,8 @@ def lib() -> C.CDLL:
                    "orbfe_synchronize"):
             getattr(L, fn).argtypes = [C.c_void_p]
         L.orbfe_pyramid_path.argtypes = [C.c_void_p, C.c_int]
+        if hasattr(L, "orbfe_pyramid_tail"):  # an older build selected with ORBFE_LIB has none
+            L.orbfe_pyramid_tail.argtypes = [C.c_void_p, C.c_int]
         if hasattr(L, "orbfe_matcher_create"):
             L.orbfe_matcher_create.restype = C.c_void_p
             L.orbfe_matcher_create.argtypes = [C.c_int, C.c_void_p]
@@ -598,6 +600,15 @@ class ORBextractor:
         r = lib().orbfe_pyramid_path(self._h, int(nframes))
         _check("orbfe_pyramid_path", r if r < 0 else 0)
         return self.PYR_PATHS[r]
+
+    PYR_TAILS = ("none", "gather", "table")
+
+    def pyramid_tail(self, nframes: int) -> str:
+        """How that extraction makes the small top levels (orbfe_pyramid_tail): "none" (no
+        resize_tail_kernel launch), "gather" (byte gathers) or "table" (column-group tables)."""
+        r = lib().orbfe_pyramid_tail(self._h, int(nframes))
+        _check("orbfe_pyramid_tail", r if r < 0 else 0)
+        return self.PYR_TAILS[r]
 
     # ---- probes of the last extraction
     def _level(self, fn, frame: int, level: int) -> np.ndarray:
