@@ -1233,6 +1233,145 @@ int orbfe_map_get_ordered_connections(orbfe_map* m, int slot, int32_t* kf_slots,
 int orbfe_map_get_spanning_tree(orbfe_map* m, int slot, int32_t* parent, int32_t* first_connection,
                                 int32_t* child_slots, int cap, int32_t* n_children);
 
+/* ---- culling: LocalMapping::MapPointCulling (LocalMapping.cc:170-205) and what it reads -------
+ * More state of an orbfe_map, all of it plain state with a setter and a getter and
+ * reset by orbfe_map_clear.  Per keyframe keypoint: mvKeysUn[i].octave, whether mvuRight[i] >= 0,
+ * mvDepth[i]; per keyframe mThDepth.  Per observation: the feature index mObservations[pKF], or -1
+ * for an observation added without one.  Per point: nObs (state, not the size of the observation
+ * set: MapPoint::SetBadFlag clears the set and leaves nObs), mnFound and mnVisible (1 for a new
+ * point), mnFirstKFid (0).  orbfe_map_add_observations records the index -1 and adds 1 to nObs;
+ * orbfe_map_erase_observations subtracts what the stored index says (1 for -1) and never sets a
+ * point bad.  All calls are synchronous. */
+
+#define ORBFE_MAP_FOUND    0   /* `kind` of orbfe_map_increase_counters */
+#define ORBFE_MAP_VISIBLE  1
+
+/* The keypoints of a keyframe: n must equal its slot count.  octaves in [0, 127] (NULL: all 0),
+ * mvu_right (NULL: all -1; only `>= 0` is kept), depth (NULL: all -1).  A keyframe that never had
+ * the call reads as octave 0, no right coordinate, depth -1, th_depth 0.  An octave out of range:
+ * ORBFE_ERR_ARG with nothing written. */
+int orbfe_map_set_keyframe_features(orbfe_map* m, int slot, int n, const int32_t* octaves,
+                                    const float* mvu_right, const float* depth, float th_depth);
+/* octaves, has_right, depth and th_depth may be NULL; *n > cap: ORBFE_ERR_CAPACITY. */
+int orbfe_map_get_keyframe_features(orbfe_map* m, int slot, int cap, int32_t* octaves,
+                                    uint8_t* has_right, float* depth, float* th_depth, int32_t* n);
+/* MapPoint::AddObservation(pKF, idx) (MapPoint.cc:339-350), batched: a pair already present is a
+ * no-op (its index stays); else the index is stored and nObs grows by 2 if the keyframe's right
+ * flag at idx is set, else by 1.  idx outside the keyframe's slots: ORBFE_ERR_ARG. */
+int orbfe_map_add_observations_idx(orbfe_map* m, int n, const int32_t* mp_slots,
+                                   const int32_t* kf_slots, const int32_t* idx);
+/* MapPoint::EraseObservation(pKF) (:352-378): an absent pair is a no-op; else nObs goes down by 2
+ * or 1 by the right flag at the stored index, the pair is erased and, if nObs <= 2, the point's
+ * SetBadFlag runs (*went_bad = 1; may be NULL).  mpRefKF is not mirrored. */
+int orbfe_map_erase_observation(orbfe_map* m, int mp_slot, int kf_slot, int32_t* went_bad);
+/* MapPoint::SetBadFlag (:392-409) of n points: the bad flag set, the observation row cleared (nObs
+ * untouched) and EraseMapPointMatch(idx) on every former observer: entry idx of that keyframe's
+ * mvpMapPoints becomes -1 whatever it held.  A listed point with an observation of index -1:
+ * ORBFE_ERR_ARG before anything changes.  One launch, a wave per point. */
+int orbfe_map_set_point_bad_flag(orbfe_map* m, int n, const int32_t* mp_slots);
+/* nObs, mnFound, mnVisible, mnFirstKFid of n points (distinct slots for the setter); an array
+ * that is NULL is left alone / not read back. */
+int orbfe_map_set_point_counters(orbfe_map* m, int n, const int32_t* mp_slots, const int32_t* n_obs,
+                                 const int32_t* found, const int32_t* visible,
+                                 const int64_t* first_kf_id);
+int orbfe_map_get_point_counters(orbfe_map* m, int n, const int32_t* mp_slots, int32_t* n_obs,
+                                 int32_t* found, int32_t* visible, int64_t* first_kf_id);
+/* MapPoint::IncreaseFound / IncreaseVisible(amounts[i]) (NULL: 1) of n points; a repeated slot
+ * adds up. */
+int orbfe_map_increase_counters(orbfe_map* m, int kind, int n, const int32_t* mp_slots,
+                                const int32_t* amounts);
+/* The same by 1 from a device array of n point slots (e.g. the d_frame_mp of
+ * orbfe_search_local_points_device) and an optional device byte mask (e.g. its in_view): entries
+ * of -1 and entries whose mask byte is 0 are skipped.  An entry outside [-1, points) is caught on
+ * the device: ORBFE_ERR_ARG with nothing added. */
+int orbfe_map_increase_counters_device(orbfe_map* m, int kind, int n, const int32_t* d_mp_slots,
+                                       const uint8_t* d_mask);
+/* LocalMapping::MapPointCulling.  list: inout, mlpRecentAddedMapPoints as n_in point slots (a point
+ * may repeat: the later occurrence sees the bad flag the earlier one set); afterwards its first
+ * *n_out entries are the list that remains, in order.  culled (n_in entries): the *n_culled points
+ * whose SetBadFlag ran, in order.  In the reference's order: bad -> dropped;
+ * (float)mnFound / mnVisible < 0.25f -> SetBadFlag and dropped (mnVisible 0 gives inf or NaN: kept);
+ * (int)current - (int)mnFirstKFid >= 2 and nObs <= (monocular ? 2 : 3) -> SetBadFlag and dropped;
+ * difference >= 3 -> dropped; else kept.  current_kf_id or the mnFirstKFid of a listed point that is
+ * not bad outside [0, 2^31), or a culled point with an observation of index -1: ORBFE_ERR_ARG with
+ * nothing changed.  Two launches (deciding in one workgroup; a wave per culled point) and two host
+ * waits. */
+int orbfe_map_cull_points(orbfe_map* m, int64_t current_kf_id, int monocular, int32_t* list, int n_in,
+                          int32_t* n_out, int32_t* culled, int32_t* n_culled);
+/* KeyFrame::TrackedMapPoints(min_obs) (KeyFrame.cc:971-996): the keyframe's entries that are not
+ * NULL, not bad and, when min_obs > 0, have nObs >= min_obs. */
+int orbfe_map_tracked_map_points(orbfe_map* m, int slot, int min_obs, int32_t* n);
+/* Read back from device memory: mvpMapPoints of a keyframe; the observation row of a point (in
+ * ascending keyframe slot) with its indices (idx may be NULL); mbBad of n keyframes or points
+ * (`kind` as in orbfe_map_get_stamps).  *n > cap: ORBFE_ERR_CAPACITY. */
+int orbfe_map_get_keyframe_points(orbfe_map* m, int slot, int32_t* mp_slots, int cap, int32_t* n);
+int orbfe_map_get_observations(orbfe_map* m, int mp_slot, int32_t* kf_slots, int32_t* idx, int cap,
+                               int32_t* n);
+int orbfe_map_get_bad_flags(orbfe_map* m, int kind, int n, const int32_t* slots, uint8_t* bad);
+
+/* ---- culling: KeyFrame::SetBadFlag complete (KeyFrame.cc:1174-1287) and
+ * LocalMapping::KeyFrameCulling (LocalMapping.cc:632-698) --------------------------------------
+ * Per keyframe, more plain state: mbNotErase and mbToBeErased (KeyFrame.cc:1152-1186), both 0 for
+ * a new keyframe.  mTcp, Map::EraseKeyFrame and KeyFrameDatabase::erase stay with the caller
+ * (orbfe_kfdb_erase); mpRefKF of a point is not mirrored. */
+
+#define ORBFE_MAP_BAD_NOTHING   0   /* *what of a SetBadFlag: mnId == 0, nothing changed          */
+#define ORBFE_MAP_BAD_DEFERRED  1   /* mbNotErase: mbToBeErased set, nothing else                 */
+#define ORBFE_MAP_BAD_DONE      2
+#define ORBFE_MAP_CULL_KEPT     0   /* result[] of orbfe_map_cull_keyframes                       */
+#define ORBFE_MAP_CULL_CULLED   1
+#define ORBFE_MAP_CULL_DEFERRED 2
+#define ORBFE_MAP_MAX_CULL_LIST 4096
+
+int orbfe_map_set_not_erase(orbfe_map* m, int slot, int flag);
+int orbfe_map_get_erase_flags(orbfe_map* m, int slot, int32_t* not_erase, int32_t* to_be_erased);
+/* KeyFrame::SetBadFlag.  is_first (`mnId == 0`): nothing changes.  mbNotErase: mbToBeErased is set
+ * and nothing else.  Otherwise, in the reference's order: the connection part
+ * (orbfe_map_erase_keyframe_connections); EraseObservation(this) on every non-NULL entry of
+ * mvpMapPoints (the keyframe leaves the point's row, nObs goes down by 2 or 1 by the right flag at
+ * the observation's index, a point left with nObs <= 2 has its SetBadFlag run; a point held at two
+ * indices is erased once, a point that does not list the keyframe is untouched, the keyframe's own
+ * entries stay); the spanning tree (:1201-1280): candidates are the parent; per round, over the
+ * children that are not bad in pointer order and each one's ordered list as it stands, the first
+ * largest GetWeight (read from the weight map, 0 when absent) towards a candidate changes that
+ * child's parent, makes it a candidate and removes it from mspChildrens; the children left over,
+ * bad ones included, go to the parent if there is one (mspChildrens is not cleared then) and keep
+ * this keyframe otherwise; EraseChild on the parent; mbBad.
+ * bad_points: the points whose SetBadFlag ran, in slot order of the entries; pairs: (child, new
+ * parent) as 2 x *n_pairs ints in the order of the ChangeParent calls.  A buffer that is too
+ * small: ORBFE_ERR_CAPACITY with the true counts, the state changed as after a successful call.  A
+ * point that would go bad while another observer of it has index -1: ORBFE_ERR_ARG before anything
+ * changes.  Three launches of a wave per held point (marking, checking, applying), the
+ * connection part's launches, one workgroup for the lists and the tournament; the host waits
+ * after the check, inside the connection part and on the done word. */
+int orbfe_map_set_keyframe_bad_flag(orbfe_map* m, int slot, int is_first, int32_t* what,
+                                    int32_t* bad_points, int bad_cap, int32_t* n_bad,
+                                    int32_t* pairs, int pair_cap, int32_t* n_pairs);
+/* KeyFrame::SetErase (:1158-1172): clears mbNotErase unless has_loop_edges, then runs SetBadFlag as
+ * above if mbToBeErased. */
+int orbfe_map_set_erase(orbfe_map* m, int slot, int has_loop_edges, int is_first, int32_t* what,
+                        int32_t* bad_points, int bad_cap, int32_t* n_bad, int32_t* pairs,
+                        int pair_cap, int32_t* n_pairs);
+/* LocalMapping::KeyFrameCulling with the result of the reference's sequential loop.  The list:
+ * kf_slots[0 .. n), or with kf_slots NULL the ordered covisibility list of current_slot as it
+ * stands (copied before anything is culled); *n_listed its length, result[i] one of
+ * ORBFE_MAP_CULL_*.  first_kf_slot (`mnId == 0`, or -1) is skipped.  Per keyframe: mvpMapPoints as
+ * a vector (a point held twice counts twice), NULL and bad skipped; unless monocular, entries with
+ * mvDepth > mThDepth or mvDepth < 0 skipped (float compares: NaN and -0 count); nMPs counts the
+ * rest; a point with nObs > 3 is redundant when three observers other than the keyframe have an
+ * octave (at their index) <= the entry's octave + 1; culled when nRedundant > 0.9 * nMPs, by the
+ * full SetBadFlag above (a mbNotErase keyframe is deferred).  One launch decides every listed
+ * keyframe (a workgroup each); the first that culls, in list order, has seen an unchanged map: its
+ * SetBadFlag is applied and only the keyframes after it decide again: culled + 1 decide launches
+ * and host waits, plus what each SetBadFlag costs.  bad_points and pairs as above, concatenated
+ * in the order of the culls.  More than 4,096 listed keyframes or *n_listed > result_cap:
+ * ORBFE_ERR_CAPACITY with nothing changed.  While any observation of the map has index -1:
+ * ORBFE_ERR_ARG with nothing changed (an observer's octave could not be read). */
+int orbfe_map_cull_keyframes(orbfe_map* m, int current_slot, int n, const int32_t* kf_slots,
+                             int first_kf_slot, int monocular, int32_t* result, int result_cap,
+                             int32_t* n_listed, int32_t* bad_points, int bad_cap, int32_t* n_bad,
+                             int32_t* pairs, int pair_cap, int32_t* n_pairs);
+
 /* ---- map-archive records of the extractor outputs (device side) ---------------------------
  * The bodies the reference's Boost map archive stores for the extractor's outputs, written
  * from / read into HBM (MapPoint.h:196-247; KeyFrame::serialize KeyFrame.cc:133-134 / 354-355

@@ -7,7 +7,9 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cmath>
+#include <list>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -952,6 +954,137 @@ public:
     std::vector<uint64_t> GetChilds(uint64_t kfId) { return tree(kfId).children; }
     bool FirstConnection(uint64_t kfId) { return tree(kfId).first; }
 
+    // ---- culling on the device
+    struct BadFlagResult {
+        int what = ORBFE_MAP_BAD_NOTHING;                           // ORBFE_MAP_BAD_*
+        std::vector<uint64_t> bad_points;                           // MapPoint::SetBadFlag ran, in order
+        std::vector<std::pair<uint64_t, uint64_t>> reparented;      // (child, new parent), in order
+    };
+    struct CullingResult {
+        std::vector<uint64_t> listed;                               // vpLocalKeyFrames
+        std::vector<int> result;                                    // ORBFE_MAP_CULL_* per listed keyframe
+        std::vector<uint64_t> culled;                               // SetBadFlag ran, in order
+        std::vector<uint64_t> bad_points;
+        std::vector<std::pair<uint64_t, uint64_t>> reparented;
+    };
+    // mvKeysUn[i].octave, mvuRight, mvDepth (empty: all 0 / -1 / -1) and mThDepth of a keyframe
+    void SetKeyFrameFeatures(uint64_t kfId, const std::vector<int32_t>& octaves, const std::vector<float>& mvuRight,
+                             const std::vector<float>& mvDepth, float mThDepth) {
+        const size_t n = std::max(octaves.size(), std::max(mvuRight.size(), mvDepth.size()));
+        check("orbfe_map_set_keyframe_features",
+              orbfe_map_set_keyframe_features(m_, kf(kfId), (int)n, octaves.empty() ? nullptr : octaves.data(),
+                                              mvuRight.empty() ? nullptr : mvuRight.data(),
+                                              mvDepth.empty() ? nullptr : mvDepth.data(), mThDepth));
+    }
+    // MapPoint::AddObservation(pKF, idx) in full (MapPoint.cc:339-350)
+    void AddObservation(uint64_t mpId, uint64_t kfId, size_t idx) {
+        const int32_t p = mp(mpId), k = kf(kfId), x = (int32_t)idx;
+        check("orbfe_map_add_observations_idx", orbfe_map_add_observations_idx(m_, 1, &p, &k, &x));
+    }
+    // MapPoint::EraseObservation(pKF) in full (:352-378): *went_bad when nObs <= 2 set the point bad
+    void EraseObservation(uint64_t mpId, uint64_t kfId, bool* went_bad) {
+        int32_t b = 0;
+        check("orbfe_map_erase_observation", orbfe_map_erase_observation(m_, mp(mpId), kf(kfId), &b));
+        if (went_bad) *went_bad = b != 0;
+    }
+    // MapPoint::SetBadFlag in full (:392-409)
+    void SetMapPointBadFlag(uint64_t mpId) {
+        const int32_t p = mp(mpId);
+        check("orbfe_map_set_point_bad_flag", orbfe_map_set_point_bad_flag(m_, 1, &p));
+    }
+    // mbBad of a keyframe alone: what SetKeyFrameBadFlag(kfId) without a second argument does
+    void set_keyframe_bad(uint64_t kfId) { SetKeyFrameBadFlag(kfId); }
+    // KeyFrame::SetBadFlag in full (KeyFrame.cc:1174-1287); is_first is `mnId == 0`
+    BadFlagResult SetKeyFrameBadFlag(uint64_t kfId, bool is_first) {
+        return bad_flag([&](int32_t* what, int32_t* bad, int nb_cap, int32_t* nb, int32_t* pr, int np_cap, int32_t* np) {
+            return orbfe_map_set_keyframe_bad_flag(m_, kf(kfId), is_first, what, bad, nb_cap, nb, pr, np_cap, np);
+        }, "orbfe_map_set_keyframe_bad_flag");
+    }
+    void SetNotErase(uint64_t kfId) { check("orbfe_map_set_not_erase", orbfe_map_set_not_erase(m_, kf(kfId), 1)); }
+    // KeyFrame::SetErase (:1158-1172); has_loop_edges is `!mspLoopEdges.empty()`
+    BadFlagResult SetErase(uint64_t kfId, bool has_loop_edges, bool is_first = false) {
+        return bad_flag([&](int32_t* what, int32_t* bad, int nb_cap, int32_t* nb, int32_t* pr, int np_cap, int32_t* np) {
+            return orbfe_map_set_erase(m_, kf(kfId), has_loop_edges, is_first, what, bad, nb_cap, nb, pr, np_cap, np);
+        }, "orbfe_map_set_erase");
+    }
+    bool NotErase(uint64_t kfId) { return erase_flags(kfId).first; }
+    bool ToBeErased(uint64_t kfId) { return erase_flags(kfId).second; }
+    void IncreaseFound(uint64_t mpId, int n = 1) { increase(ORBFE_MAP_FOUND, mpId, n); }
+    void IncreaseVisible(uint64_t mpId, int n = 1) { increase(ORBFE_MAP_VISIBLE, mpId, n); }
+    void SetFirstKFid(uint64_t mpId, int64_t id) {
+        const int32_t p = mp(mpId);
+        check("orbfe_map_set_point_counters", orbfe_map_set_point_counters(m_, 1, &p, nullptr, nullptr, nullptr, &id));
+    }
+    int Observations(uint64_t mpId) { return counters(mpId)[0]; }
+    float GetFoundRatio(uint64_t mpId) {
+        const auto c = counters(mpId);
+        return static_cast<float>(c[1]) / c[2];
+    }
+    bool MapPointIsBad(uint64_t mpId) { return bad(ORBFE_MAP_POINTS, mp(mpId)); }
+    bool KeyFrameIsBad(uint64_t kfId) { return bad(ORBFE_MAP_KEYFRAMES, kf(kfId)); }
+    // GetMapPointMatches as ids or kNone; GetObservations as (keyframe id, idx) in slot order
+    std::vector<uint64_t> GetMapPointMatches(uint64_t kfId) {
+        std::vector<int32_t> s(ORBFE_MAP_MAX_KF_SLOTS);
+        int32_t n = 0;
+        check("orbfe_map_get_keyframe_points", orbfe_map_get_keyframe_points(m_, kf(kfId), s.data(), (int)s.size(), &n));
+        std::vector<uint64_t> out((size_t)n, kNone);
+        for (int i = 0; i < n; ++i)
+            if (s[i] >= 0) out[i] = mp_id_[s[i]];
+        return out;
+    }
+    std::vector<std::pair<uint64_t, int64_t>> GetObservations(uint64_t mpId) {
+        std::vector<int32_t> k(std::max<size_t>(kf_id_.size(), 1)), x(k.size());
+        int32_t n = 0;
+        check("orbfe_map_get_observations", orbfe_map_get_observations(m_, mp(mpId), k.data(), x.data(), (int)k.size(), &n));
+        std::vector<std::pair<uint64_t, int64_t>> out;
+        for (int i = 0; i < n; ++i) out.push_back({kf_id_[k[i]], x[i]});
+        return out;
+    }
+    // KeyFrame::TrackedMapPoints(minObs) (KeyFrame.cc:971-996)
+    int TrackedMapPoints(uint64_t kfId, int minObs) {
+        int32_t n = 0;
+        check("orbfe_map_tracked_map_points", orbfe_map_tracked_map_points(m_, kf(kfId), minObs, &n));
+        return n;
+    }
+    // LocalMapping::MapPointCulling (LocalMapping.cc:170-205): mlpRecentAddedMapPoints is edited in
+    // place; returns the points whose SetBadFlag ran
+    std::vector<uint64_t> MapPointCulling(std::list<uint64_t>& mlpRecentAddedMapPoints, uint64_t nCurrentKFid,
+                                          bool mbMonocular) {
+        std::vector<int32_t> l, gone(std::max<size_t>(mlpRecentAddedMapPoints.size(), 1));
+        for (uint64_t id : mlpRecentAddedMapPoints) l.push_back(mp(id));
+        int32_t n = 0, nc = 0;
+        check("orbfe_map_cull_points", orbfe_map_cull_points(m_, (int64_t)nCurrentKFid, mbMonocular, l.data(),
+                                                             (int)l.size(), &n, gone.data(), &nc));
+        mlpRecentAddedMapPoints.clear();
+        for (int i = 0; i < n; ++i) mlpRecentAddedMapPoints.push_back(mp_id_[l[i]]);
+        std::vector<uint64_t> out;
+        for (int i = 0; i < nc; ++i) out.push_back(mp_id_[gone[i]]);
+        return out;
+    }
+    // LocalMapping::KeyFrameCulling (:632-698) over GetVectorCovisibleKeyFrames of the current
+    // keyframe; the keyframe with id 0 is the map's first
+    CullingResult KeyFrameCulling(uint64_t currentKfId, bool mbMonocular) {
+        const auto first = kf_slot_.find(0);
+        std::vector<int32_t> res(ORBFE_MAP_MAX_CULL_LIST), bad(std::max<size_t>(mp_id_.size(), 1));
+        std::vector<int32_t> pr(2 * std::max<size_t>(kf_id_.size(), 1) * 8);
+        const std::vector<uint64_t> listed = GetVectorCovisibleKeyFrames(currentKfId);
+        pr.resize(2 * std::max<size_t>(kf_id_.size(), 1) * std::max<size_t>(listed.size(), 1));
+        int32_t nl = 0, nb = 0, np = 0;
+        check("orbfe_map_cull_keyframes",
+              orbfe_map_cull_keyframes(m_, kf(currentKfId), -1, nullptr, first == kf_slot_.end() ? -1 : first->second,
+                                       mbMonocular, res.data(), (int)res.size(), &nl, bad.data(), (int)bad.size(), &nb,
+                                       pr.data(), (int)pr.size() / 2, &np));
+        CullingResult r;
+        r.listed = listed;
+        r.result.assign(res.begin(), res.begin() + nl);
+        for (int i = 0; i < nl; ++i)
+            if (res[i] == ORBFE_MAP_CULL_CULLED) r.culled.push_back(listed[(size_t)i]);
+        for (int i = 0; i < nb; ++i) r.bad_points.push_back(mp_id_[bad[i]]);
+        for (int i = 0; i < np; ++i) r.reparented.push_back({kf_id_[pr[2 * i]], kf_id_[pr[2 * i + 1]]});
+        refresh_children();
+        return r;
+    }
+
     // mnTrackReferenceForFrame of a keyframe / a point
     uint64_t KeyFrameStamp(uint64_t kfId) { return stamp(ORBFE_MAP_KEYFRAMES, kf(kfId)); }
     uint64_t MapPointStamp(uint64_t mpId) { return stamp(ORBFE_MAP_POINTS, mp(mpId)); }
@@ -968,6 +1101,48 @@ private:
         const auto it = mp_slot_.find(id);
         if (it == mp_slot_.end()) throw Error("LocalMap: unknown map point", ORBFE_ERR_ARG);
         return it->second;
+    }
+    template <class F>
+    BadFlagResult bad_flag(F&& call, const char* fn) {
+        std::vector<int32_t> bad(std::max<size_t>(mp_id_.size(), 1)), pr(2 * std::max<size_t>(kf_id_.size(), 1));
+        int32_t what = 0, nb = 0, np = 0;
+        check(fn, call(&what, bad.data(), (int)bad.size(), &nb, pr.data(), (int)pr.size() / 2, &np));
+        BadFlagResult r;
+        r.what = what;
+        for (int i = 0; i < nb; ++i) r.bad_points.push_back(mp_id_[bad[i]]);
+        for (int i = 0; i < np; ++i) r.reparented.push_back({kf_id_[pr[2 * i]], kf_id_[pr[2 * i + 1]]});
+        if (what == ORBFE_MAP_BAD_DONE) refresh_children();
+        return r;
+    }
+    // the cache AddChild / EraseChild upload from, read back after the device changed the tree
+    void refresh_children() {
+        std::vector<int32_t> c(std::max<size_t>(kf_id_.size(), 1));
+        for (size_t s = 0; s < kf_id_.size(); ++s) {
+            int32_t n = 0;
+            check("orbfe_map_get_spanning_tree",
+                  orbfe_map_get_spanning_tree(m_, (int)s, nullptr, nullptr, c.data(), (int)c.size(), &n));
+            if (n || children_.count((int32_t)s)) children_[(int32_t)s].assign(c.begin(), c.begin() + n);
+        }
+    }
+    std::pair<bool, bool> erase_flags(uint64_t kfId) {
+        int32_t a = 0, b = 0;
+        check("orbfe_map_get_erase_flags", orbfe_map_get_erase_flags(m_, kf(kfId), &a, &b));
+        return {a != 0, b != 0};
+    }
+    void increase(int kind, uint64_t mpId, int n) {
+        const int32_t p = mp(mpId), a = n;
+        check("orbfe_map_increase_counters", orbfe_map_increase_counters(m_, kind, 1, &p, &a));
+    }
+    std::array<int32_t, 3> counters(uint64_t mpId) {
+        const int32_t p = mp(mpId);
+        std::array<int32_t, 3> c{};
+        check("orbfe_map_get_point_counters", orbfe_map_get_point_counters(m_, 1, &p, &c[0], &c[1], &c[2], nullptr));
+        return c;
+    }
+    bool bad(int kind, int32_t slot) {
+        uint8_t b = 0;
+        check("orbfe_map_get_bad_flags", orbfe_map_get_bad_flags(m_, kind, 1, &slot, &b));
+        return b != 0;
     }
     uint64_t stamp(int kind, int32_t slot) {
         uint64_t v = 0;

@@ -479,6 +479,16 @@ struct MapCovis;
 void map_covis_free(MapCovis* c);
 void map_covis_reset(MapCovis* c);
 
+// What the culling calls add to the handle (orbfe_cull.hip): made by their first call.
+struct MapCull;
+void map_cull_free(MapCull* c);
+void map_cull_reset(MapCull* c);
+
+// nObs of the listed points changed by the listed amounts; whether mvuRight[idx] of a keyframe is
+// >= 0 as orbfe_map_set_keyframe_features left it (orbfe_cull.hip).
+int map_cull_add_nobs(orbfe_map* m, const std::vector<int>& mp_slots, const std::vector<int>& amounts);
+bool map_cull_right(const orbfe_map* m, int kf, int idx);
+
 }  // namespace
 
 struct orbfe_map {
@@ -488,15 +498,19 @@ struct orbfe_map {
     std::unordered_map<uint64_t, int> by_key;
     std::vector<uint64_t> h_key;
     std::vector<std::vector<int>> h_obs;  // sorted
+    std::vector<std::vector<int>> h_idx;  // mObservations[pKF] of h_obs' entries, or -1
+    long long n_unknown = 0;              // entries of h_idx that are -1
     std::vector<int> h_local;             // the list as of the last query / set_local_keyframes
     int h_ref = -1, h_n_local_mp = 0;
     MapRagged kf_mp, kf_ch, mp_obs;
+    MapRagged mp_idx;  // the feature indices, row for row beside mp_obs
     DevBuf kf_key, kf_bad, kf_stamp, kf_neigh, kf_parent, kf_cnt, mp_bad, mp_stamp, first_pos, touched,
         ctl, local_kf, local_mp, blk, stage_i, stage_items, stage_v, frame;
     hipStream_t own = nullptr, stream = nullptr;
     int* pin = nullptr;
     int* pin_dev = nullptr;
     MapCovis* covis = nullptr;
+    MapCull* cull = nullptr;
 
     MapDev dev() const {
         MapDev d;
@@ -531,6 +545,7 @@ struct orbfe_map {
     bool mp_ok(int s) const { return s >= 0 && s < n_mp; }
     ~orbfe_map() {
         map_covis_free(covis);
+        map_cull_free(cull);
         if (pin) hipHostFree(pin);
         if (own) hipStreamDestroy(own);
     }
@@ -576,6 +591,8 @@ int map_grow_mp(orbfe_map* m, int n) {
     if ((st = map_regrow(m, m->mp_stamp, 8, k, n))) return st;
     if ((st = map_regrow(m, m->mp_obs.off, 8, k, n))) return st;
     if ((st = map_regrow(m, m->mp_obs.len, sizeof(int), k, n))) return st;
+    if ((st = map_regrow(m, m->mp_idx.off, 8, k, n))) return st;
+    if ((st = map_regrow(m, m->mp_idx.len, sizeof(int), k, n))) return st;
     if ((st = map_regrow(m, m->first_pos, sizeof(int), 0, n, 0x7f))) return st;  // kMapNoPos
     if ((st = map_regrow(m, m->local_mp, sizeof(int), k, n))) return st;
     m->mp_alloc = n;
@@ -770,13 +787,17 @@ int orbfe_map_clear(orbfe_map* m) {
         m->by_key.clear();
         m->h_key.clear();
         m->h_obs.clear();
+        m->h_idx.clear();
+        m->n_unknown = 0;
         m->h_local.clear();
         m->h_ref = -1;
         m->h_n_local_mp = 0;
         m->kf_mp.reset();
         m->kf_ch.reset();
         m->mp_obs.reset();
+        m->mp_idx.reset();
         map_covis_reset(m->covis);
+        map_cull_reset(m->cull);
         return map_reset_ctl(m);
     });
 }
@@ -885,19 +906,23 @@ int orbfe_map_add_points(orbfe_map* m, int n, int32_t* first_slot) {
             ORBFE_HIP(hipMemsetAsync(m->mp_bad.as<uint8_t>() + o, 0, (size_t)n, m->stream));
             ORBFE_HIP(hipMemsetAsync(m->mp_stamp.as<unsigned long long>() + o, 0, 8 * (size_t)n, m->stream));
             ORBFE_HIP(hipMemsetAsync(m->mp_obs.len.as<int>() + o, 0, sizeof(int) * (size_t)n, m->stream));
+            ORBFE_HIP(hipMemsetAsync(m->mp_idx.len.as<int>() + o, 0, sizeof(int) * (size_t)n, m->stream));
             ORBFE_HIP(hipStreamSynchronize(m->stream));
         }
         *first_slot = m->n_mp;
         m->n_mp += n;
         m->h_obs.resize((size_t)m->n_mp);
-        if (m->mp_obs.h_cap.size() < (size_t)m->n_mp) {
-            m->mp_obs.h_off.resize((size_t)m->n_mp, 0);
-            m->mp_obs.h_n.resize((size_t)m->n_mp, 0);
-            m->mp_obs.h_cap.resize((size_t)m->n_mp, 0);
-        }
+        m->h_idx.resize((size_t)m->n_mp);
+        for (MapRagged* r : {&m->mp_obs, &m->mp_idx})
+            if (r->h_cap.size() < (size_t)m->n_mp) {
+                r->h_off.resize((size_t)m->n_mp, 0);
+                r->h_n.resize((size_t)m->n_mp, 0);
+                r->h_cap.resize((size_t)m->n_mp, 0);
+            }
         for (int i = *first_slot; i < m->n_mp; ++i) {
             m->h_obs[i].clear();
-            m->mp_obs.h_n[i] = 0;
+            m->h_idx[i].clear();
+            m->mp_obs.h_n[i] = m->mp_idx.h_n[i] = 0;
         }
         return (int)ORBFE_OK;
     });
@@ -912,39 +937,65 @@ int orbfe_map_set_points_bad(orbfe_map* m, int n, const int32_t* mp_slots, int b
     });
 }
 
+// MapPoint::AddObservation (MapPoint.cc:339-350) / the erase of EraseObservation (:357-365),
+// batched.  idx = NULL: the index is not known (-1), nObs changes by 1.
 static int map_change_observations(orbfe_map* m, int n, const int32_t* mp_slots,
-                                   const int32_t* kf_slots, bool add) {
+                                   const int32_t* kf_slots, const int32_t* idx, bool add) {
     if (!m || n < 0 || (n && (!mp_slots || !kf_slots))) return ORBFE_ERR_ARG;
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < n; ++i) {
         if (!m->mp_ok(mp_slots[i]) || !m->kf_ok(kf_slots[i])) return ORBFE_ERR_ARG;
+        if (idx && (idx[i] < 0 || idx[i] >= m->kf_mp.h_n[kf_slots[i]])) return ORBFE_ERR_ARG;
+    }
     return map_guarded(m, [&]() {
-        std::vector<int> dirty;
+        std::vector<int> dirty, who, amount;
         for (int i = 0; i < n; ++i) {
             std::vector<int>& o = m->h_obs[mp_slots[i]];
+            std::vector<int>& x = m->h_idx[mp_slots[i]];
             auto it = std::lower_bound(o.begin(), o.end(), kf_slots[i]);
             const bool has = it != o.end() && *it == kf_slots[i];
-            if (add == has) continue;  // set semantics (MapPoint.cc:170-171, :183)
-            if (add) o.insert(it, kf_slots[i]);
-            else o.erase(it);
+            if (add == has) continue;  // set semantics (MapPoint.cc:342-343, :357)
+            const auto xi = x.begin() + (it - o.begin());
+            const int ix = add ? (idx ? idx[i] : -1) : *xi;
+            const int by = ix >= 0 && map_cull_right(m, kf_slots[i], ix) ? 2 : 1;  // :346-349, :360-363
+            if (ix < 0) m->n_unknown += add ? 1 : -1;
+            if (add) {
+                o.insert(it, kf_slots[i]);
+                x.insert(xi, ix);
+            } else {
+                o.erase(it);
+                x.erase(xi);
+            }
             dirty.push_back(mp_slots[i]);
+            who.push_back(mp_slots[i]);
+            amount.push_back(add ? by : -by);
         }
         std::sort(dirty.begin(), dirty.end());
         dirty.erase(std::unique(dirty.begin(), dirty.end()), dirty.end());
-        std::vector<MapRowWrite> w;
+        std::vector<MapRowWrite> w, wx;
         for (int p : dirty) {
             const std::vector<int>& o = m->h_obs[p];
             w.push_back({p, 0, (int)o.size(), (int)o.size(), o.data()});
+            wx.push_back({p, 0, (int)o.size(), (int)o.size(), m->h_idx[p].data()});
         }
-        return map_put_rows(m, m->mp_obs, w);
+        int st;
+        if ((st = map_put_rows(m, m->mp_obs, w))) return st;
+        if ((st = map_put_rows(m, m->mp_idx, wx))) return st;
+        return map_cull_add_nobs(m, who, amount);
     });
 }
 
 int orbfe_map_add_observations(orbfe_map* m, int n, const int32_t* mp_slots, const int32_t* kf_slots) {
-    return map_change_observations(m, n, mp_slots, kf_slots, true);
+    return map_change_observations(m, n, mp_slots, kf_slots, nullptr, true);
+}
+
+int orbfe_map_add_observations_idx(orbfe_map* m, int n, const int32_t* mp_slots, const int32_t* kf_slots,
+                                   const int32_t* idx) {
+    if (n > 0 && !idx) return ORBFE_ERR_ARG;
+    return map_change_observations(m, n, mp_slots, kf_slots, idx, true);
 }
 
 int orbfe_map_erase_observations(orbfe_map* m, int n, const int32_t* mp_slots, const int32_t* kf_slots) {
-    return map_change_observations(m, n, mp_slots, kf_slots, false);
+    return map_change_observations(m, n, mp_slots, kf_slots, nullptr, false);
 }
 
 int orbfe_map_set_stamps(orbfe_map* m, int kind, int n, const int32_t* slots, const uint64_t* stamps) {

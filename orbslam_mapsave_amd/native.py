@@ -79,6 +79,15 @@ EXPORTED = [
     "orbfe_map_set_connections", "orbfe_map_set_ordered_connections",
     "orbfe_map_set_first_connection", "orbfe_map_get_connections",
     "orbfe_map_get_ordered_connections", "orbfe_map_get_spanning_tree",
+    "orbfe_map_set_keyframe_features", "orbfe_map_get_keyframe_features",
+    "orbfe_map_add_observations_idx", "orbfe_map_erase_observation",
+    "orbfe_map_set_point_bad_flag", "orbfe_map_set_point_counters",
+    "orbfe_map_get_point_counters", "orbfe_map_increase_counters",
+    "orbfe_map_increase_counters_device", "orbfe_map_cull_points",
+    "orbfe_map_tracked_map_points", "orbfe_map_get_keyframe_points",
+    "orbfe_map_get_observations", "orbfe_map_get_bad_flags",
+    "orbfe_map_set_not_erase", "orbfe_map_get_erase_flags", "orbfe_map_set_keyframe_bad_flag",
+    "orbfe_map_set_erase", "orbfe_map_cull_keyframes",
     "orbfe_archive_mat_bytes",
     "orbfe_archive_write_keypoints_device", "orbfe_archive_read_keypoints_device",
     "orbfe_archive_write_descriptors_device", "orbfe_archive_read_descriptors_device",
@@ -192,6 +201,27 @@ def lib() -> C.CDLL:
             L.orbfe_map_get_connections.argtypes = [vp, i, vp, vp, i, vp]
             L.orbfe_map_get_ordered_connections.argtypes = [vp, i, vp, vp, i, vp]
             L.orbfe_map_get_spanning_tree.argtypes = [vp, i, vp, vp, vp, i, vp]
+        if hasattr(L, "orbfe_map_cull_points"):
+            vp, i, f = C.c_void_p, C.c_int, C.c_float
+            L.orbfe_map_set_keyframe_features.argtypes = [vp, i, i, vp, vp, vp, f]
+            L.orbfe_map_get_keyframe_features.argtypes = [vp, i, i, vp, vp, vp, vp, vp]
+            L.orbfe_map_add_observations_idx.argtypes = [vp, i, vp, vp, vp]
+            L.orbfe_map_erase_observation.argtypes = [vp, i, i, vp]
+            L.orbfe_map_set_point_bad_flag.argtypes = [vp, i, vp]
+            L.orbfe_map_set_point_counters.argtypes = [vp, i, vp, vp, vp, vp, vp]
+            L.orbfe_map_get_point_counters.argtypes = [vp, i, vp, vp, vp, vp, vp]
+            L.orbfe_map_increase_counters.argtypes = [vp, i, i, vp, vp]
+            L.orbfe_map_increase_counters_device.argtypes = [vp, i, i, vp, vp]
+            L.orbfe_map_cull_points.argtypes = [vp, C.c_int64, i, vp, i, vp, vp, vp]
+            L.orbfe_map_tracked_map_points.argtypes = [vp, i, i, vp]
+            L.orbfe_map_get_keyframe_points.argtypes = [vp, i, vp, i, vp]
+            L.orbfe_map_get_observations.argtypes = [vp, i, vp, vp, i, vp]
+            L.orbfe_map_get_bad_flags.argtypes = [vp, i, i, vp, vp]
+            L.orbfe_map_set_not_erase.argtypes = [vp, i, i]
+            L.orbfe_map_get_erase_flags.argtypes = [vp, i, vp, vp]
+            L.orbfe_map_set_keyframe_bad_flag.argtypes = [vp, i, i, vp, vp, i, vp, vp, i, vp]
+            L.orbfe_map_set_erase.argtypes = [vp, i, i, i, vp, vp, i, vp, vp, i, vp]
+            L.orbfe_map_cull_keyframes.argtypes = [vp, i, i, vp, i, i, vp, i, vp, vp, i, vp, vp, i, vp]
         if hasattr(L, "orbfe_archive_mat_bytes"):
             L.orbfe_archive_mat_bytes.restype = C.c_int64
             sz, vp, i = C.c_size_t, C.c_void_p, C.c_int
@@ -909,6 +939,10 @@ class MapPointArrays(C.Structure):
 
 MAP_KEYFRAMES, MAP_POINTS = 0, 1       # ORBFE_MAP_KEYFRAMES / ORBFE_MAP_POINTS
 MAP_MAX_VOTED, MAP_MAX_KF_SLOTS = 4096, 8192
+MAP_FOUND, MAP_VISIBLE = 0, 1          # ORBFE_MAP_FOUND / ORBFE_MAP_VISIBLE
+MAP_BAD_NOTHING, MAP_BAD_DEFERRED, MAP_BAD_DONE = 0, 1, 2      # ORBFE_MAP_BAD_*
+MAP_CULL_KEPT, MAP_CULL_CULLED, MAP_CULL_DEFERRED = 0, 1, 2    # ORBFE_MAP_CULL_*
+MAP_MAX_CULL_LIST = 4096
 
 
 class LocalMap:
@@ -970,9 +1004,11 @@ class LocalMap:
         """KeyFrame::AddMapPoint(pMP, idx); mp = -1: EraseMapPointMatch(idx)."""
         self.set_keyframe_points(kf, idx, [mp])
 
-    def SetBadFlag(self, kf: int, bad: bool = True) -> None:
-        """KeyFrame::SetBadFlag."""
+    def set_keyframe_bad(self, kf: int, bad: bool = True) -> None:
+        """mbBad of a keyframe alone."""
         _check("orbfe_map_set_keyframe_bad", lib().orbfe_map_set_keyframe_bad(self._h, kf, int(bad)))
+
+    SetBadFlag = set_keyframe_bad   # the name this call had before SetKeyFrameBadFlag existed
 
     def UpdateBestCovisibles(self, kf: int, neigh_slots=None) -> None:
         """With ``neigh_slots``: GetBestCovisibilityKeyFrames(10) after KeyFrame::UpdateBestCovisibles,
@@ -1018,19 +1054,37 @@ class LocalMap:
         _check("orbfe_map_set_points_bad", lib().orbfe_map_set_points_bad(
             self._h, len(p), ptr(p), int(bad)))
 
-    def AddObservation(self, mp_slots, kf_slots) -> None:
+    def AddObservation(self, mp_slots, kf_slots, idx=None) -> None:
+        """MapPoint::AddObservation(pKF, idx), batched.  Without ``idx`` the index is recorded as
+        unknown (-1) and nObs grows by 1."""
         p, k = self._i32(mp_slots), self._i32(kf_slots)
         if len(p) != len(k):
             raise ValueError("one keyframe per point")
-        _check("orbfe_map_add_observations", lib().orbfe_map_add_observations(
-            self._h, len(p), ptr(p), ptr(k)))
+        if idx is None:
+            _check("orbfe_map_add_observations", lib().orbfe_map_add_observations(
+                self._h, len(p), ptr(p), ptr(k)))
+            return
+        x = self._i32(idx)
+        if len(x) != len(p):
+            raise ValueError("one index per point")
+        _check("orbfe_map_add_observations_idx", lib().orbfe_map_add_observations_idx(
+            self._h, len(p), ptr(p), ptr(k), ptr(x)))
 
-    def EraseObservation(self, mp_slots, kf_slots) -> None:
+    def EraseObservation(self, mp_slots, kf_slots):
+        """Two scalars: MapPoint::EraseObservation(pKF) in full, with its `nObs <= 2` rule
+        -> whether the point went bad.  Sequences: the set erase alone, batched (nObs follows,
+        no point is set bad)."""
+        if np.isscalar(mp_slots) and np.isscalar(kf_slots):
+            bad = C.c_int32(0)
+            _check("orbfe_map_erase_observation", lib().orbfe_map_erase_observation(
+                self._h, int(mp_slots), int(kf_slots), C.byref(bad)))
+            return bool(bad.value)
         p, k = self._i32(mp_slots), self._i32(kf_slots)
         if len(p) != len(k):
             raise ValueError("one keyframe per point")
         _check("orbfe_map_erase_observations", lib().orbfe_map_erase_observations(
             self._h, len(p), ptr(p), ptr(k)))
+        return None
 
     def set_stamps(self, kind: int, slots, stamps) -> None:
         s, v = self._i32(slots), np.ascontiguousarray(stamps, np.uint64).reshape(-1)
@@ -1204,6 +1258,174 @@ class LocalMap:
 
     def GetChilds(self, kf: int) -> set:
         return set(int(x) for x in self.get_spanning_tree(kf)[2])
+
+    # ---- culling (LocalMapping.cc:170-205, MapPoint.cc:339-409, KeyFrame.cc:971-996)
+    def set_keyframe_features(self, kf: int, octaves=None, mvu_right=None, depth=None,
+                              th_depth: float = 0.0) -> None:
+        """mvKeysUn[i].octave, mvuRight (only ``>= 0`` is kept), mvDepth, mThDepth of a keyframe;
+        every array holds one entry per slot (None: octave 0 / -1 / -1)."""
+        arrs = [None if a is None else np.ascontiguousarray(a, t).reshape(-1)
+                for a, t in ((octaves, np.int32), (mvu_right, np.float32), (depth, np.float32))]
+        n = {len(a) for a in arrs if a is not None}
+        if len(n) > 1:
+            raise ValueError("one entry per slot in every array")
+        n = n.pop() if n else len(self.get_keyframe_points(kf))
+        _check("orbfe_map_set_keyframe_features", lib().orbfe_map_set_keyframe_features(
+            self._h, kf, n, ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), float(th_depth)))
+
+    def get_keyframe_features(self, kf: int):
+        """-> (octaves, has_right, depth, th_depth)."""
+        cap = MAP_MAX_KF_SLOTS
+        o, r, d = np.zeros(cap, np.int32), np.zeros(cap, np.uint8), np.zeros(cap, np.float32)
+        th, n = C.c_float(0), C.c_int32(0)
+        _check("orbfe_map_get_keyframe_features", lib().orbfe_map_get_keyframe_features(
+            self._h, kf, cap, ptr(o), ptr(r), ptr(d), C.byref(th), C.byref(n)))
+        return o[:n.value].copy(), r[:n.value].astype(bool), d[:n.value].copy(), th.value
+
+    def get_keyframe_points(self, kf: int) -> np.ndarray:
+        """mvpMapPoints as point slots or -1."""
+        out = np.zeros(MAP_MAX_KF_SLOTS, np.int32)
+        n = C.c_int32(0)
+        _check("orbfe_map_get_keyframe_points", lib().orbfe_map_get_keyframe_points(
+            self._h, kf, ptr(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def GetObservations(self, mp: int):
+        """mObservations -> (keyframe slots ascending, feature indices or -1)."""
+        cap = max(self.size()[0], 1)
+        k, x = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        n = C.c_int32(0)
+        _check("orbfe_map_get_observations", lib().orbfe_map_get_observations(
+            self._h, mp, ptr(k), ptr(x), cap, C.byref(n)))
+        return k[:n.value].copy(), x[:n.value].copy()
+
+    def get_bad_flags(self, kind: int, slots) -> np.ndarray:
+        s = self._i32(slots)
+        out = np.zeros(len(s), np.uint8)
+        _check("orbfe_map_get_bad_flags", lib().orbfe_map_get_bad_flags(
+            self._h, kind, len(s), ptr(s), ptr(out)))
+        return out.astype(bool)
+
+    def set_point_counters(self, mp_slots, n_obs=None, found=None, visible=None, first_kf_id=None) -> None:
+        s = self._i32(mp_slots)
+        a = [None if v is None else np.ascontiguousarray(v, t).reshape(-1)
+             for v, t in ((n_obs, np.int32), (found, np.int32), (visible, np.int32), (first_kf_id, np.int64))]
+        if any(v is not None and len(v) != len(s) for v in a):
+            raise ValueError("one value per point")
+        _check("orbfe_map_set_point_counters", lib().orbfe_map_set_point_counters(
+            self._h, len(s), ptr(s), ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[3])))
+
+    def get_point_counters(self, mp_slots):
+        """-> (nObs, mnFound, mnVisible, mnFirstKFid)."""
+        s = self._i32(mp_slots)
+        o, f, v = (np.zeros(len(s), np.int32) for _ in range(3))
+        k = np.zeros(len(s), np.int64)
+        _check("orbfe_map_get_point_counters", lib().orbfe_map_get_point_counters(
+            self._h, len(s), ptr(s), ptr(o), ptr(f), ptr(v), ptr(k)))
+        return o, f, v, k
+
+    def _increase(self, kind: int, mp_slots, amounts) -> None:
+        s = self._i32([mp_slots] if np.isscalar(mp_slots) else mp_slots)
+        a = None if amounts is None else self._i32([amounts] if np.isscalar(amounts) else amounts)
+        if a is not None and len(a) != len(s):
+            raise ValueError("one amount per point")
+        _check("orbfe_map_increase_counters", lib().orbfe_map_increase_counters(
+            self._h, kind, len(s), ptr(s), ptr(a)))
+
+    def IncreaseFound(self, mp_slots, n=None) -> None:
+        self._increase(MAP_FOUND, mp_slots, n)
+
+    def IncreaseVisible(self, mp_slots, n=None) -> None:
+        self._increase(MAP_VISIBLE, mp_slots, n)
+
+    def increase_counters_device(self, kind: int, n: int, d_mp_slots: int, d_mask: int | None = None) -> None:
+        """By 1 for every entry >= 0 of the device array whose mask byte (if any) is set."""
+        _check("orbfe_map_increase_counters_device", lib().orbfe_map_increase_counters_device(
+            self._h, kind, n, C.c_void_p(d_mp_slots), C.c_void_p(d_mask or 0)))
+
+    def Observations(self, mp: int) -> int:
+        return int(self.get_point_counters([mp])[0][0])
+
+    def GetFoundRatio(self, mp: int) -> float:
+        _, f, v, _ = self.get_point_counters([mp])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return float(np.float32(f[0]) / np.float32(v[0]))
+
+    def SetMapPointBadFlag(self, mp_slots) -> None:
+        """MapPoint::SetBadFlag in full: the flag, the observations cleared, EraseMapPointMatch on
+        every former observer."""
+        s = self._i32([mp_slots] if np.isscalar(mp_slots) else mp_slots)
+        _check("orbfe_map_set_point_bad_flag", lib().orbfe_map_set_point_bad_flag(self._h, len(s), ptr(s)))
+
+    def MapPointCulling(self, recent, current_kf_id: int, monocular: bool):
+        """LocalMapping::MapPointCulling over mlpRecentAddedMapPoints -> (the list that remains,
+        the points whose SetBadFlag ran)."""
+        lst = self._i32(recent).copy()
+        gone = np.zeros(max(len(lst), 1), np.int32)
+        n, nc = C.c_int32(0), C.c_int32(0)
+        _check("orbfe_map_cull_points", lib().orbfe_map_cull_points(
+            self._h, int(current_kf_id), int(bool(monocular)), ptr(lst), len(lst), C.byref(n),
+            ptr(gone), C.byref(nc)))
+        return lst[:n.value].copy(), gone[:nc.value].copy()
+
+    def SetNotErase(self, kf: int, flag: bool = True) -> None:
+        _check("orbfe_map_set_not_erase", lib().orbfe_map_set_not_erase(self._h, kf, int(flag)))
+
+    def get_erase_flags(self, kf: int) -> tuple[bool, bool]:
+        """-> (mbNotErase, mbToBeErased)."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        _check("orbfe_map_get_erase_flags", lib().orbfe_map_get_erase_flags(self._h, kf, C.byref(a), C.byref(b)))
+        return bool(a.value), bool(b.value)
+
+    def _bad_flag_call(self, fn: str, *head):
+        n_kf, n_mp = self.size()
+        bad, pairs = np.zeros(max(n_mp, 1), np.int32), np.zeros(2 * max(n_kf, 1), np.int32)
+        what, nb, npair = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _check(fn, getattr(lib(), fn)(self._h, *head, C.byref(what), ptr(bad), len(bad), C.byref(nb),
+                                      ptr(pairs), len(pairs) // 2, C.byref(npair)))
+        pr = pairs[:2 * npair.value].reshape(-1, 2).copy()
+        self._refresh_children(pr)
+        return what.value, bad[:nb.value].copy(), pr
+
+    def _refresh_children(self, pairs) -> None:
+        for k in list(self._children) + [int(x) for x in np.asarray(pairs).reshape(-1)]:
+            self._children[k] = set(int(x) for x in self.get_spanning_tree(k)[2])
+
+    def SetKeyFrameBadFlag(self, kf: int, is_first: bool = False):
+        """KeyFrame::SetBadFlag in full -> (MAP_BAD_NOTHING | MAP_BAD_DEFERRED | MAP_BAD_DONE, the
+        points that went bad, the (child, new parent) pairs)."""
+        return self._bad_flag_call("orbfe_map_set_keyframe_bad_flag", kf, int(bool(is_first)))
+
+    def SetErase(self, kf: int, has_loop_edges: bool = False, is_first: bool = False):
+        """KeyFrame::SetErase -> as SetKeyFrameBadFlag."""
+        return self._bad_flag_call("orbfe_map_set_erase", kf, int(bool(has_loop_edges)), int(bool(is_first)))
+
+    def KeyFrameCulling(self, current_kf: int, monocular: bool, kf_slots=None, first_kf: int = -1):
+        """LocalMapping::KeyFrameCulling over the ordered covisibility list of ``current_kf`` (or
+        over ``kf_slots``) -> (the list, its results MAP_CULL_*, the points that went bad, the
+        (child, new parent) pairs)."""
+        n_kf, n_mp = self.size()
+        k = None if kf_slots is None else self._i32(kf_slots)
+        if k is None:
+            lst = self.get_ordered_connections(current_kf)[0]
+        else:
+            lst = k.copy()
+        res = np.zeros(max(len(lst), 1), np.int32)
+        bad, pairs = np.zeros(max(n_mp, 1), np.int32), np.zeros(2 * max(n_kf, 1) * max(len(lst), 1), np.int32)
+        nl, nb, npair = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _check("orbfe_map_cull_keyframes", lib().orbfe_map_cull_keyframes(
+            self._h, current_kf, -1 if k is None else len(k), ptr(k) if k is not None and len(k) else
+            (None if k is None else ptr(np.zeros(1, np.int32))), first_kf, int(bool(monocular)), ptr(res), len(lst),
+            C.byref(nl), ptr(bad), len(bad), C.byref(nb), ptr(pairs), len(pairs) // 2, C.byref(npair)))
+        pr = pairs[:2 * npair.value].reshape(-1, 2).copy()
+        self._refresh_children(pr)
+        return lst, res[:nl.value].copy(), bad[:nb.value].copy(), pr
+
+    def TrackedMapPoints(self, kf: int, min_obs: int) -> int:
+        n = C.c_int32(0)
+        _check("orbfe_map_tracked_map_points", lib().orbfe_map_tracked_map_points(
+            self._h, kf, min_obs, C.byref(n)))
+        return n.value
 
 
 class ORBmatcher:

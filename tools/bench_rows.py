@@ -1019,12 +1019,82 @@ def row_covis():
     load.close()
 
 
+def row_culling():
+    """LocalMapping::KeyFrameCulling and MapPointCulling on the device.  A seeded map of the
+    local-BA kind: 31 keyframes of 1000 slots, 850 of them over 3,300 shared points (observation
+    rows of about 8) and 150 private ones, one octave, monocular; the current keyframe lists the
+    other 30.  (a) nothing culled: one decide launch; (b) keyframes 10 and 20 have no private
+    points and are culled: three decide launches and two SetBadFlags (the map is rebuilt for
+    every repeat, outside the clock).  (c) MapPointCulling over 500 recent points, none culled,
+    and once with about a third culled.  A host clock around calls that end synchronised;
+    comparator: tests/cpp/culling_test --time, the literal loops on one host thread."""
+    import subprocess
+
+    def world(full, seed=7):
+        rng = np.random.default_rng(seed)
+        nkf, per, shared, priv = 31, 1000, 3300, 150
+        lm = native.LocalMap(0, nkf, shared + nkf * priv)
+        assert lm.add_points(shared + nkf * priv) == 0
+        for i in range(nkf):
+            mps = rng.integers(0, shared, per).astype(np.int32)
+            if i not in full:
+                mps[per - priv:] = shared + i * priv + np.arange(priv)
+            assert lm.add_keyframe(0x7f0000000000 + 0x2c0 * int(rng.integers(1, 1 << 20)) + i, per, mps) == i
+            lm.set_keyframe_features(i, np.zeros(per, np.int32))
+            _, first = np.unique(mps, return_index=True)     # a point held twice is observed once
+            lm.AddObservation(mps[first], np.full(len(first), i, np.int32), first.astype(np.int32))
+        lm.set_ordered_connections(nkf - 1, list(range(1, nkf - 1)) + [0], list(range(nkf - 1, 0, -1)))
+        return lm
+
+    def clock(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t0, out
+
+    exe = os.path.join(ROOT, "tests", "cpp", "build", "culling_test")
+    r = subprocess.run([exe, "--time", "5"], capture_output=True, text=True, check=True)
+    comp = r.stdout.strip().splitlines()
+    lm = world(())
+    rows = float(np.mean([len(lm.GetObservations(p)[0]) for p in range(0, 3300, 33)]))
+    for rep in range(2):
+        t = timed(lambda: lm.KeyFrameCulling(30, True, first_kf=0), 50, warm=5)
+        assert not lm.KeyFrameCulling(30, True)[1].any()
+        jrow("cull_keyframes_none", "calls/s", 1, t,
+             f"repeat {rep}: orbfe_map_cull_keyframes, 30 listed keyframes of 1000 slots, rows of {rows:.1f}, "
+             f"nothing culled: 1 decide launch, 1 host wait; comparator: {comp[-2]}")
+        recent = np.arange(100, 600, dtype=np.int32)
+        t = timed(lambda: lm.MapPointCulling(recent, 0, True), 100, warm=5)
+        assert len(lm.MapPointCulling(recent, 0, True)[0]) == 500
+        jrow("cull_points_none", "calls/s", 1, t,
+             f"repeat {rep}: orbfe_map_cull_points, 500 listed points, none culled: 1 launch, 1 host wait; "
+             f"comparator: {comp[-1]}")
+    ts, culled = [], []
+    for rep in range(5):
+        w = world((10, 20))
+        w.KeyFrameCulling(30, True, kf_slots=[30])        # warm: buffers, code objects
+        t, out = clock(lambda: w.KeyFrameCulling(30, True, first_kf=0))
+        ts.append(t)
+        culled.append(int((out[1] == native.MAP_CULL_CULLED).sum()))
+        w.close()
+    jrow("cull_keyframes_two", "calls/s", 1, float(np.median(ts)),
+         f"orbfe_map_cull_keyframes, the same map with two keyframes culled ({culled}): 3 decide launches and "
+         f"2 SetBadFlags; median of 5 single calls on fresh maps, min {min(ts) * 1e3:.3f} max {max(ts) * 1e3:.3f} ms; "
+         f"comparator: {comp[-2]}")
+    lm.set_point_counters(np.arange(100, 600, 3, dtype=np.int32), found=np.zeros(167, np.int32),
+                          visible=np.full(167, 5, np.int32))
+    t, out = clock(lambda: lm.MapPointCulling(np.arange(100, 600, dtype=np.int32), 0, True))
+    jrow("cull_points_third", "calls/s", 1, t,
+         f"orbfe_map_cull_points, 500 listed points, {len(out[1])} culled: 2 launches, 2 host waits; one call")
+    lm.close()
+
+
 if __name__ == "__main__":
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         rows = {"single": row_single, "color": row_color, "stereo": row_stereo, "reloc": row_reloc, "fuse": row_fuse, "triangulation": row_triangulation, "track": row_track,
                 "distinctive": row_distinctive, "bow": lambda: row_bow(td),
                 "loop": row_loop, "kfdb": lambda: row_kfdb(td), "rgbd": row_rgbd,
-                "localmap": row_localmap, "covis": row_covis}
+                "localmap": row_localmap, "covis": row_covis, "culling": row_culling}
         for name in (sys.argv[1:] or list(rows)):
             rows[name]()
