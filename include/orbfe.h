@@ -259,6 +259,15 @@ int orbfe_pyramid_path(const orbfe_extractor* h, int nframes);
 #define ORBFE_TAIL_GATHER 1
 #define ORBFE_TAIL_TABLE  2
 int orbfe_pyramid_tail(const orbfe_extractor* h, int nframes);
+/* Describe's matrix-core window blur, host side (a test hook as well; no device): the seven
+ * blur taps of these parameters (taps7), the six constant MFMA fragments as the kernel loads
+ * them (frags: 384 lanes x 16 bytes — H_0..H_2, lane n + 16 g, byte j = raw column 16 g + j ->
+ * window column 16 s + n; then V_0..V_2, lane n + 16 g, byte j = 4 t + i = R row 16 t + 4 g + i
+ * -> window row 16 u + n) and the constant bytes of the column pass's spare K slots j = 12..14
+ * (pads: hi plane scalar, hi plane x86, lo plane scalar, lo plane x86; byte i <-> j = 12 + i).
+ * ORBFE_ERR_UNSUPPORTED if a slot weight does not fit an i8 or a constant is not met exactly. */
+int orbfe_describe_blur_fragments(const orbfe_params* p, int32_t* taps7, uint8_t* frags,
+                                  uint32_t* pads);
 /* Measurement hook: relaunch the stages in `stage_mask` (bits 1 << ORBFE_STAGE_*) of the most
  * recent extraction on its own buffers, `reps` times, asynchronously on the handle's stream
  * (outputs meaningful only for a full mask). */

@@ -147,6 +147,7 @@ struct orbfe_extractor {
     bool planned = false;
     int frames_cap = 0;
     DevBuf cells, xtab, ytab, bslot, ptab;
+    DescPad desc_pad{};  // with bslot's fragments (blur_frags)
     DevBuf pyr, blur, cell_cnt, cell_keys, keys, act, oct_out, oct_cnt, oct_ord, level_keys;
     DevBuf out_kps, out_desc, out_n;  // staging for the host-pointer entry points
     DevBuf lk_snap;                   // orbfe_debug_replay: one FAST's per-level key totals
@@ -397,7 +398,7 @@ struct orbfe_extractor {
                                  hipMemcpyHostToDevice, stream));
         // blur_mfma_kernel: its constant fragments, then its work list
         std::vector<uint8_t> bb(kBlurFragBytes + g.bitems.size() * sizeof(uint32_t));
-        blur_frags(tab.taps, bb.data());
+        if (!blur_frags(tab.taps, bb.data(), desc_pad)) return ORBFE_ERR_UNSUPPORTED;
         std::memcpy(bb.data() + kBlurFragBytes, g.bitems.data(), g.bitems.size() * sizeof(uint32_t));
         ORBFE_HIP(hipMemcpyAsync(bslot.p, bb.data(), bb.size(), hipMemcpyHostToDevice, stream));
         ORBFE_HIP(hipStreamSynchronize(stream));
@@ -669,6 +670,7 @@ struct orbfe_extractor {
         // consecutive slots, sharing window lines in L2); ORBFE_DESC_STRIDE=0: grouped slots
         da.wave_stride = (group == kDescGroupSize || g16) && sw.desc_stride ? (int)dgrid.x * (kDescBlock / 64) : 0;
         da.frags = bslot.as<uint4>() + kDescFragOff;
+        da.pad_hi = desc_pad.hi[x86() ? 1 : 0], da.pad_lo = desc_pad.lo[x86() ? 1 : 0];
 #define ORBFE_DESC_LAUNCH(G, X, W) \
         ORBFE_LAUNCH(prof, ORBFE_STAGE_DESCRIBE, (describe_kernel<G, X, W>), dgrid, dim3(kDescBlock), 0, stream, da)
 #define ORBFE_DESC_CASE(V, G, W) \
@@ -859,6 +861,10 @@ orbfe_extractor* orbfe_create(const orbfe_params* params, int device, int max_wi
                 st = ORBFE_ERR_HIP;
             h->stream = h->own;
             if (st == ORBFE_OK && hipMemcpyToSymbol(HIP_SYMBOL(c_umax), h->tab.umax, sizeof(h->tab.umax)) != hipSuccess)
+                st = ORBFE_ERR_HIP;
+            uint32_t icm[64 * 8];
+            ic_masks(h->tab.umax, icm);
+            if (st == ORBFE_OK && hipMemcpyToSymbol(HIP_SYMBOL(c_icmask), icm, sizeof(icm)) != hipSuccess)
                 st = ORBFE_ERR_HIP;
             const int w = max_width > 0 ? max_width : 1920, hh = max_height > 0 ? max_height : 1080;
             if (st == ORBFE_OK) st = h->set_plan(w, hh);
@@ -1385,6 +1391,21 @@ int orbfe_pyramid_tail(const orbfe_extractor* h, int nframes) {
     if (!h || !h->planned || nframes < 1) return ORBFE_ERR_ARG;
     if (h->band_path(nframes) || h->tail_start(nframes) >= h->plan.geo.nlevels) return ORBFE_TAIL_NONE;
     return h->tail_table() ? ORBFE_TAIL_TABLE : ORBFE_TAIL_GATHER;
+}
+
+int orbfe_describe_blur_fragments(const orbfe_params* p, int32_t* taps7, uint8_t* frags,
+                                  uint32_t* pads) {
+    if (!p || !taps7 || !frags || !pads) return ORBFE_ERR_ARG;
+    HostTables t{};
+    const int st = make_tables(*p, t);
+    if (st != ORBFE_OK) return st;
+    std::vector<uint8_t> bb(kBlurFragBytes);
+    DescPad pad{};
+    const bool ok = blur_frags(t.taps, bb.data(), pad);
+    for (int i = 0; i < 7; ++i) taps7[i] = t.taps[i];
+    std::memcpy(frags, bb.data() + 16 * kDescFragOff, 16 * (512 - kDescFragOff));
+    pads[0] = pad.hi[0], pads[1] = pad.hi[1], pads[2] = pad.lo[0], pads[3] = pad.lo[1];
+    return ok ? ORBFE_OK : ORBFE_ERR_UNSUPPORTED;
 }
 
 int orbfe_set_stream(orbfe_extractor* h, void* s) {

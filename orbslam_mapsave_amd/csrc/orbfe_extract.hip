@@ -52,6 +52,31 @@ __constant__ int8_t c_pattern[1024] = {
 #include "../../include/orbfe_pattern.inc"
 };
 __constant__ int c_umax[16];
+// describe's IC-angle byte masks (ic_masks, from umax): lane's 8 dwords, the u + 16 weights of
+// its 16 pixels and then their 0 / 1 disc mask
+__constant__ uint4 c_icmask[64 * 2];
+
+// Host: c_icmask.  Lane (r = lane >> 1, hh = lane & 1) holds row v = r - 15 of the 31 x 31
+// disc, columns u = -15 + 16 hh + k (k < 16; u = 16 never lies in the disc, r = 31 is no row):
+// byte k of the first four dwords is u + 16 inside the disc (|u| <= umax[|v|]) and 0 outside,
+// byte k of the last four 1 inside and 0 outside.
+void ic_masks(const int umax[16], uint32_t out[64 * 8]) {
+    for (int lane = 0; lane < 64; ++lane) {
+        const int r = lane >> 1, hh = lane & 1, v = r - 15, av = v < 0 ? -v : v;
+        const int ulim = r < 31 ? umax[std::min(av, 15)] : -1;
+        for (int d = 0; d < 4; ++d) {
+            uint32_t x = 0, y = 0;
+            for (int b = 0; b < 4; ++b) {
+                const int u = -15 + 16 * hh + 4 * d + b;
+                const bool in = (u < 0 ? -u : u) <= ulim;
+                x |= (in ? (uint32_t)(u + 16) : 0u) << (8 * b);
+                y |= (in ? 1u : 0u) << (8 * b);
+            }
+            out[8 * lane + d] = x;
+            out[8 * lane + 4 + d] = y;
+        }
+    }
+}
 
 constexpr int kEdge = kEdgeThreshold;   // EDGE_THRESHOLD (ORBextractor.cc:73)
 constexpr int kMinBorder = kEdge - 3;    // EDGE_THRESHOLD - 3 (772)
@@ -647,6 +672,12 @@ __device__ __forceinline__ unsigned long long tie_lanes(uint32_t v) {
     unsigned long long m;
     asm("v_cmp_eq_u16_e64 %0, -1, %1" : "=s"(m) : "v"(v));
     return m;
+}
+// max of three values' low halves (v_max3_u16; the high half of the result is not used)
+__device__ __forceinline__ uint32_t max3_lo16(uint32_t x, uint32_t y, uint32_t z) {
+    uint32_t r;
+    asm("v_max3_u16 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(z));
+    return r;
 }
 __device__ __forceinline__ uint32_t blur_round_bit(uint32_t v, bool even) {
     return even ? ((v - 0x7fffu) >> 16) & 1u : 1u;
@@ -2216,6 +2247,11 @@ struct DescArgs {
     LevelPtr blur[kMaxLevels];  // blurred levels (K4 output), read by the pre-blurred variant
     uint32_t pre_mask;          // levels whose blurred plane exists (bit l): windows read from it
     const uint4* frags;         // the matrix-core window blur: H / V fragments (blur_frags, 128..)
+    uint32_t pad_hi, pad_lo;    // its column pass's constant K-slot bytes (DescPad, this reading's)
+};
+// the constant bytes of the column pass's spare K slots (blur_frags): [0] scalar, [1] x86
+struct DescPad {
+    uint32_t hi[2], lo[2];
 };
 // constant MFMA fragments: [0, 128) blur_mfma_kernel's, [128, 512) describe's window blur
 constexpr size_t kBlurFragBytes = 512 * 16;
@@ -2432,12 +2468,48 @@ void blur_items(const Geo& geo, std::vector<uint32_t>& s) {
 // [128, 512): describe's window blur (v_mfma_i32_16x16x64_i8), lane l = n + 16 g, byte j:
 // [128 + 64 s, ...) s < 3: H_s[k = raw column 16 g + j][window column 16 s + n]
 //                          = tap(16 g + j - 16 s - n - 4)   (raw column = window column + 4)
+//                          for g < 3, the spare slots' weights for g = 3 (below)
 // [320 + 64 u, ...) u < 3: V_u[window row 16 u + n][k = R row 16 t + 4 g + i], j = 4 t + i
-//                          = tap(16 t + 4 g + i - 16 u - n - 3) for t < 3, 0 for j >= 12
+//                          = tap(16 t + 4 g + i - 16 u - n - 3) for t < 3, the spare slots'
+//                          weights for j >= 12 (below)
 //                          (R row = window row + 3; the R rows are the row pass's accumulator
 //                          rows held in register i of tile t, in that K order)
-void blur_frags(const int taps[4], uint8_t out[512 * 16]) {
+//
+// describe's unused K slots carry the passes' additive constants, so that every MFMA's C
+// operand is the inline 0 (no accumulator copy in front of it):
+//   row pass: the raw-column slots 48..63 (g = 3) hold -128 in every A fragment (zero bytes
+//     ^ 0x80); H_s there holds weights p_j, sum p_j = -(S + 256), so the slots add
+//     128 S + 2^15 to every output column (S = the taps' sum);
+//   column pass: the R-row slots j = 12..15 of B (Blo[3] / Bhi[3]) hold constant bytes, the
+//     same in every lane; V_u there holds -128 at j = 12 (all g), 1 at j = 13 (all g), 1 at
+//     j = 14 (g = 0): per-byte sums (-512, 4, 1).  DescPad gives the bytes with which the hi
+//     plane's slots add Kc >> 8 and the lo plane's Kc & 0xff, Kc = 128 * 257 S + the reading's
+//     rounding constant ([0] scalar 0x8000, [1] x86 0x7fff).
+// False if a weight or a byte does not fit an i8 or a sum is not exact (never for a 7-tap
+// kernel of sum <= 257).
+bool blur_frags(const int taps[4], uint8_t out[512 * 16], DescPad& pad) {
     auto tap = [&](int d) { return d < -3 || d > 3 ? 0 : taps[3 - (d < 0 ? -d : d)]; };
+    const int S = 2 * (taps[0] + taps[1] + taps[2]) + taps[3];
+    bool ok = true;
+    int rowp[16], rem = -(S + 256);
+    for (int j = 0; j < 16; ++j) {
+        rowp[j] = std::max(rem, -128);
+        rem -= rowp[j];
+    }
+    ok = ok && rem == 0;
+    constexpr int kColW[3] = {-512, 4, 1};
+    auto solve = [&](int target, uint32_t& bytes) {  // bytes b: -512 b0 + 4 b1 + b2 = target
+        const int b0 = -((target + 256) >> 9), r0 = target + 512 * b0;  // r0 in [-256, 255]
+        const int b1 = (r0 + 2) >> 2, b2 = r0 - 4 * b1;
+        ok = ok && b0 >= -128 && b0 <= 127 && b1 >= -128 && b1 <= 127 && b2 >= -128 && b2 <= 127 &&
+             kColW[0] * b0 + kColW[1] * b1 + kColW[2] * b2 == target;
+        bytes = (uint32_t)(uint8_t)b0 | ((uint32_t)(uint8_t)b1 << 8) | ((uint32_t)(uint8_t)b2 << 16);
+    };
+    for (int x = 0; x < 2; ++x) {
+        const int kc = 128 * 257 * S + (x ? 0x7fff : 0x8000);
+        solve(kc >> 8, pad.hi[x]);
+        solve(kc & 0xff, pad.lo[x]);
+    }
     for (int l = 0; l < 64; ++l) {
         const int col = l & 31, hh = l >> 5;
         for (int j = 0; j < 16; ++j) {
@@ -2451,11 +2523,14 @@ void blur_frags(const int taps[4], uint8_t out[512 * 16]) {
         for (int q = 0; q < 3; ++q)
             for (int j = 0; j < 16; ++j) {
                 const int t = j >> 2, i = j & 3;
-                out[16 * (kDescFragOff + 64 * q + l) + j] = (uint8_t)tap(16 * g + j - 16 * q - n - 4);
+                // (g = 3: no sampled column has a tap there — window columns >= 41 only)
+                out[16 * (kDescFragOff + 64 * q + l) + j] = (uint8_t)(g < 3 ? tap(16 * g + j - 16 * q - n - 4) : rowp[j]);
+                const int colp = i == 0 ? -128 : i == 1 ? 1 : i == 2 && g == 0 ? 1 : 0;
                 out[16 * (kDescFragOff + 192 + 64 * q + l) + j] =
-                    (uint8_t)(t < 3 ? tap(16 * t + 4 * g + i - 16 * q - n - 3) : 0);
+                    (uint8_t)(t < 3 ? tap(16 * t + 4 * g + i - 16 * q - n - 3) : colp);
             }
     }
+    return ok;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2709,6 +2784,9 @@ __global__ __launch_bounds__(kDescBlock, kWin == kWinMfma ? (kDescGroup < 8 ? OR
     const us2 T01 = us2{k0, k1}, T23 = us2{k2, k3}, T21 = us2{k2, k1}, T0L = us2{k0, 0},
               T0H = us2{0, k0}, T12 = us2{k1, k2}, T32 = us2{k3, k2}, T10 = us2{k1, k0};
     // raw chunk c = lane + 64 i (i < 3, c < 43 * 3): row c / 3, 16-byte part c % 3
+    // (kWinMfma: rv is zeroed once per wave and only load_frag_to may write it — the lanes it
+    // never loads, g = 3 and rows >= 43, must stay zero: blur_frags' row-pass weights count on
+    // -128 there after the ^ 0x80.  load_raw / load_win write every lane.)
     uint4 rv[3];
     auto load_raw = [&](int j) __attribute__((always_inline)) {
         const int kl = __builtin_amdgcn_readlane(my_l, j);
@@ -2757,8 +2835,9 @@ __global__ __launch_bounds__(kDescBlock, kWin == kWinMfma ? (kDescGroup < 8 ? OR
     // was blurred by the pyramid kernels); the others blur a raw window here.  The choice is
     // wave-uniform per keypoint.
     // kMfma: A fragment t of the row pass = raw row 16 t + (lane & 15), raw columns 16 g .. 16 g
-    // + 15 (g = lane >> 4 < 3; the g = 3 K slots meet zero weights for every sampled column,
-    // rows 43.. feed only window rows >= 37): one 16-byte load per tile straight into registers
+    // + 15 (g = lane >> 4 < 3; the g = 3 lanes stay zero, -128 after the ^ 0x80: the constant
+    // side of the row pass's spare K slots; rows 43.. feed only window rows >= 37): one 16-byte
+    // load per tile straight into registers
     // (staging them in LDS with global_load_lds instead measured no faster: describe 0.2488 vs
     // 0.2467 ms, profiles/r03/experiments/describe_mfma.json)
     auto load_frag_to = [&](int j, uint4 (&dst)[3]) __attribute__((always_inline)) {
@@ -2771,13 +2850,17 @@ __global__ __launch_bounds__(kDescBlock, kWin == kWinMfma ? (kDescGroup < 8 ? OR
         const bool fast = x0 - 4 >= 0 && x0 + 44 <= pp.pitch && x - 21 >= 0 && x + 21 < lw &&
                           y - 21 >= 0 && y + 21 < lh;
         const int g = lane >> 4;
+        // one wave-uniform base per tile plus one 32-bit lane offset for all three (row
+        // lane & 15 of the tile, 16-byte part g): the address arithmetic is scalar
+        const uint8_t* tb = fb + (long long)(y - 21) * pp.pitch + (x0 - 4);
+        const uint32_t lo = (uint32_t)(lane & 15) * (uint32_t)pp.pitch + 16u * (uint32_t)g;
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             const int r = 16 * t + (lane & 15);
-            dst[t] = make_uint4(0u, 0u, 0u, 0u);
+            // (these lanes never load: they keep the zeros rv starts with)
             if (r >= kRawRows - 1 || g == 3 || (kDescSkip & 8)) continue;
             if (fast) {
-                dst[t] = load16_a4(fb + (long long)(y - 21 + r) * pp.pitch + x0 - 4 + 16 * g);
+                dst[t] = load16_a4(tb + (long long)(16 * t) * pp.pitch + lo);
             } else {
                 // keypoints lie >= 19 px inside their level (>= 39 px wide and high), so the
                 // window overshoots an edge by at most 2 rows / 6 columns: one reflection
@@ -2826,34 +2909,22 @@ __global__ __launch_bounds__(kDescBlock, kWin == kWinMfma ? (kDescGroup < 8 ? OR
         return i32x4m{(int)h.x, (int)h.y, (int)h.z, (int)h.w};
     };
     unsigned long long dacc = 0;
+    if constexpr (kMfma) rv[0] = rv[1] = rv[2] = make_uint4(0u, 0u, 0u, 0u);
     load_kp(__ffsll((long long)vmask) - 1);
     // (the first window's loads are in flight during the IC moments and the trig)
     // 1. IC moments.  Lane (r = lane >> 1, hh = lane & 1): row v = r - 15, columns
     //    u = -15 + 16 hh .. +15 (u = 16 never lies in the disc).
     const int r = lane >> 1, hh = lane & 1, v = r - 15;
-    const int av = v < 0 ? -v : v;
-    const int ulim = r < 31 ? c_umax[min(av, 15)] : -1;
-    uint32_t wu[4], w1[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        uint32_t x = 0, y = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int u = -15 + 16 * hh + 4 * d + b;
-            const bool in = (u < 0 ? -u : u) <= ulim;
-            x |= (in ? (uint32_t)(u + 16) : 0u) << (8 * b);
-            y |= (in ? 1u : 0u) << (8 * b);
-        }
-        wu[d] = x;
-        w1[d] = y;
-    }
+    // (the disc's byte masks, per lane: ic_masks on the host)
+    const uint4 mu = c_icmask[2 * lane], m1 = c_icmask[2 * lane + 1];
+    const uint32_t wu[4] = {mu.x, mu.y, mu.z, mu.w}, w1[4] = {m1.x, m1.y, m1.z, m1.w};
     // the 16-byte row loads of kIcBatch keypoints are issued before their first reduction
     // (4 at a time: 16 VGPRs of loads in flight, not 32)
     constexpr int kIcBatch = kDescGroup < 4 ? kDescGroup : 4;
     int M10 = 0, M01 = 0;
     // the rows of up to 8 keypoints in flight before the first reduction, every load
     // unconditional (an empty slot re-reads the first keypoint's rows, lanes past row 30 row
-    // 15; both zeroed): a load under a branch made the compiler wait for it on the spot
+    // 15): a load under a branch made the compiler wait for it on the spot
     constexpr int kIcAhead = kDescGroup < 8 ? kDescGroup : 8;
     const int j_first = __ffsll((long long)vmask) - 1;
 #pragma unroll
@@ -2867,10 +2938,11 @@ __global__ __launch_bounds__(kDescBlock, kWin == kWinMfma ? (kDescGroup < 8 ? OR
         const int kl = __builtin_amdgcn_readlane(my_l, js);
         const uint32_t kk = (uint32_t)__builtin_amdgcn_readlane(my_key, js);
         const LevelPtr pp = a.pyr[kl];
-        const uint8_t* row = pp.base + f * pp.fpitch + (long long)(key_y(kk) + (r < 31 ? v : 0)) * pp.pitch +
-                             key_x(kk) - 15 + 16 * hh;
-        const uint4 q = load16_a1(row);
-        pxa[jb] = use && r < 31 ? q : make_uint4(0u, 0u, 0u, 0u);
+        // a wave-uniform base (the disc's top row) plus a 32-bit lane offset.  No lane is
+        // zeroed: an empty slot's moments are never used, and lanes 62 / 63 have empty masks
+        const uint8_t* top = pp.base + f * pp.fpitch + (long long)(key_y(kk) - 15) * pp.pitch + (key_x(kk) - 15);
+        const uint4 q = load16_a1(top + ((uint32_t)(r < 31 ? r : 15) * (uint32_t)pp.pitch + 16u * (uint32_t)hh));
+        pxa[jb] = (kDescSkip & 2) ? make_uint4(0u, 0u, 0u, 0u) : q;
     }
 #pragma unroll
     for (int j0 = ja; j0 < ja + kIcAhead; j0 += kIcBatch) {
@@ -2954,77 +3026,92 @@ __global__ __launch_bounds__(kDescBlock, kWin == kWinMfma ? (kDescGroup < 8 ? OR
                 fbase = lane;
                 asm volatile("" : "+v"(fbase));
             }
-            const int S = 2 * (a.taps[0] + a.taps[1] + a.taps[2]) + a.taps[3];
-            constexpr uint32_t kRndM = kX86 ? 0x7fffu : 0x8000u;
-            const int ci = 128 * S + 0x8000;
-            const uint32_t kC2 = 128u * 257u * (uint32_t)S + kRndM;
-            const i32x4m Ci = i32x4m{ci, ci, ci, ci}, Z = i32x4m{0, 0, 0, 0};
-            const i32x4m Kc = i32x4m{(int)kC2, (int)kC2, (int)kC2, (int)kC2};
+            // The additive constants (128 S + 2^15; 128 * 257 S + rnd, split over the planes)
+            // come out of the passes' spare K slots (blur_frags), so every C operand is 0.
+            const i32x4m Z = i32x4m{0, 0, 0, 0};
             i32x4m A[3];
             const int n = lane & 15, g = lane >> 4;
 #pragma unroll
             for (int t = 0; t < 3; ++t)
                 A[t] = i32x4m{(int)(rv[t].x ^ 0x80808080u), (int)(rv[t].y ^ 0x80808080u),
                               (int)(rv[t].z ^ 0x80808080u), (int)(rv[t].w ^ 0x80808080u)};
+            // A is made here, before the next window's loads are issued into rv: left to
+            // itself the compiler sinks the xors below the loads and copies rv out of their
+            // way first (12 v_mov_b32 per keypoint)
+            asm volatile("" : "+v"(A[0]), "+v"(A[1]), "+v"(A[2]));
             const unsigned long long rest = m & (m - 1);
             if (rest) load_kp(__ffsll((long long)rest) - 1);  // next keypoint's window in flight
-            const int xs = kX86 ? (int)__builtin_amdgcn_readlane(my_x0, j) + (lane & 15) -
-                                      a.simd_xb[(int)__builtin_amdgcn_readlane(my_l, j)]
-                                : 0;
+            const int x0j = (int)__builtin_amdgcn_readlane(my_x0, j);
+            const int xbj = kX86 ? a.simd_xb[(int)__builtin_amdgcn_readlane(my_l, j)] : 0;
+            const int xs = x0j + n - xbj;
+            // x86: the window's sums take the half-to-even fix-up (kFix) only where it can change
+            // a byte: a sum that is a tie, or a column in the scalar tail.  The pass without it
+            // keeps the 16-bit maximum of every sum's low half (0xffff = a tie; two v_max3_u16
+            // per tile, no branch inside the window), and the rare window with a tie (1 sum in
+            // 65,536) or a tail column is blurred again with the fix-up on every sum.
+            auto blur_win = [&](auto fixc) __attribute__((always_inline)) {
+                constexpr bool kFix = decltype(fixc)::value;
+                uint32_t tmax = 0u;
 #pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                i32x4m Blo, Bhi;
-                const i32x4m Hs = frag(s, Hf[s], (kFragLds & 1) != 0);
+                for (int s = 0; s < 3; ++s) {
+                    i32x4m Blo, Bhi;
+                    const i32x4m Hs = frag(s, Hf[s], (kFragLds & 1) != 0);
 #pragma unroll
-                for (int t = 0; t < 3; ++t) {
-                    const i32x4m R = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t], Hs, Ci, 0, 0, 0);
-                    const uint32_t x01 = __builtin_amdgcn_perm((uint32_t)R[1], (uint32_t)R[0], 0x05010400u);
-                    const uint32_t x23 = __builtin_amdgcn_perm((uint32_t)R[3], (uint32_t)R[2], 0x05010400u);
-                    Blo[t] = (int)(__builtin_amdgcn_perm(x23, x01, 0x05040100u) ^ 0x80808080u);
-                    Bhi[t] = (int)__builtin_amdgcn_perm(x23, x01, 0x07060302u);
-                }
-                Blo[3] = 0;
-                Bhi[3] = 0;
-                // x86: 1 where the column is in the SIMD body (round half to even), else 0
-                const uint32_t em = xs + 16 * s < 0 ? 1u : 0u, nem = 1u - em;
-                // the tile's columns all in the SIMD body (wave-uniform): then only a tie needs
-                // the fix-up below
-                const bool body = !kX86 || __ballot(em == 0u) == 0ull;
-                i32x4m Vs[3];  // (kFragLds & 4: the three V fragments read once per N-tile)
-                if constexpr ((kFragLds & 4) != 0) {
+                    for (int t = 0; t < 3; ++t) {
+                        const i32x4m R = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t], Hs, Z, 0, 0, 0);
+                        const uint32_t x01 = __builtin_amdgcn_perm((uint32_t)R[1], (uint32_t)R[0], 0x05010400u);
+                        const uint32_t x23 = __builtin_amdgcn_perm((uint32_t)R[3], (uint32_t)R[2], 0x05010400u);
+                        Blo[t] = (int)(__builtin_amdgcn_perm(x23, x01, 0x05040100u) ^ 0x80808080u);
+                        Bhi[t] = (int)__builtin_amdgcn_perm(x23, x01, 0x07060302u);
+                    }
+                    Blo[3] = (int)a.pad_lo;
+                    Bhi[3] = (int)a.pad_hi;
+                    // x86: 1 where the column is in the SIMD body (round half to even), else 0
+                    const uint32_t em = xs + 16 * s < 0 ? 1u : 0u, nem = 1u - em;
+                    i32x4m Vs[3];  // (kFragLds & 4: the three V fragments read once per N-tile)
+                    if constexpr ((kFragLds & 4) != 0) {
 #pragma unroll
-                    for (int u = 0; u < 3; ++u) Vs[u] = frag(3 + u, Vf[u], true);
-                }
+                        for (int u = 0; u < 3; ++u) Vs[u] = frag(3 + u, Vf[u], true);
+                    }
 #pragma unroll
-                for (int u = 0; u < 3; ++u) {
-                    const i32x4m Vu = (kFragLds & 4) ? Vs[u] : frag(3 + u, Vf[u], (kFragLds & 2) != 0);
-                    // the two planes' products are independent; the hi one shifted in after
-                    const i32x4m Dh = __builtin_amdgcn_mfma_i32_16x16x64_i8(Vu, Bhi, Z, 0, 0, 0);
-                    const i32x4m Dl = __builtin_amdgcn_mfma_i32_16x16x64_i8(Vu, Blo, Kc, 0, 0, 0);
-                    uint32_t s4[4];
+                    for (int u = 0; u < 3; ++u) {
+                        const i32x4m Vu = (kFragLds & 4) ? Vs[u] : frag(3 + u, Vf[u], (kFragLds & 2) != 0);
+                        // the two planes' products are independent; the hi one shifted in after
+                        const i32x4m Dh = __builtin_amdgcn_mfma_i32_16x16x64_i8(Vu, Bhi, Z, 0, 0, 0);
+                        const i32x4m Dl = __builtin_amdgcn_mfma_i32_16x16x64_i8(Vu, Blo, Z, 0, 0, 0);
+                        uint32_t s4[4];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) s4[i] = ((uint32_t)Dh[i] << 8) + (uint32_t)Dl[i];
-                    if constexpr (kX86) {
-                        // x86 (kRndM = 0x7fff): + bit 16 of the sum in the SIMD body, + 1 past
-                        // it.  The bit of sum + 0x7fff equals the true sum's bit 16 in the only
-                        // case it matters (a tie, low half 0x8000 -> 0xffff), and adding it
-                        // elsewhere changes no carry: v_bfe with width em (0 or 1), then one
-                        // v_add3 — run only when some lane's sum is a tie or the tile reaches
-                        // the scalar tail (one v_cmp_eq_u16 per sum instead of the two VALU of
-                        // the fix-up; ties are ~1 in 65,536 sums)
-                        if (!body || (tie_lanes(s4[0]) | tie_lanes(s4[1]) | tie_lanes(s4[2]) | tie_lanes(s4[3]))) {
+                        for (int i = 0; i < 4; ++i) s4[i] = ((uint32_t)Dh[i] << 8) + (uint32_t)Dl[i];
+                        if constexpr (kX86 && kFix) {
+                            // x86 (rnd = 0x7fff): + bit 16 of the sum in the SIMD body, + 1 past
+                            // it.  The bit of sum + 0x7fff equals the true sum's bit 16 in the only
+                            // case it matters (a tie, low half 0x8000 -> 0xffff), and adding it
+                            // elsewhere changes no carry: v_bfe with width em (0 or 1), then one
+                            // v_add3
 #pragma unroll
                             for (int i = 0; i < 4; ++i) s4[i] = s4[i] + __builtin_amdgcn_ubfe(s4[i], 16u, em) + nem;
+                        } else if constexpr (kX86) {
+                            tmax = max3_lo16(tmax, s4[0], s4[1]);
+                            tmax = max3_lo16(tmax, s4[2], s4[3]);
                         }
+                        // min(sum >> 16, 255) of two sums at once (sum >> 16 <= 257 < 2^16)
+                        const us2 sat = us2{255, 255};
+                        const us2 h01 = __builtin_elementwise_min(__builtin_bit_cast(us2, __builtin_amdgcn_perm(s4[1], s4[0], 0x07060302u)), sat);
+                        const us2 h23 = __builtin_elementwise_min(__builtin_bit_cast(us2, __builtin_amdgcn_perm(s4[3], s4[2], 0x07060302u)), sat);
+                        if ((s < 2 || n < 8) && (u < 2 || g < 2))  // window columns / rows < 40
+                            *reinterpret_cast<uint32_t*>(wb + (16 * s + n) * kMwP + 16 * u + 4 * g) =
+                                __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, h23), __builtin_bit_cast(uint32_t, h01), 0x06040200u);
                     }
-                    // min(sum >> 16, 255) of two sums at once (sum >> 16 <= 257 < 2^16)
-                    const us2 sat = us2{255, 255};
-                    const us2 h01 = __builtin_elementwise_min(__builtin_bit_cast(us2, __builtin_amdgcn_perm(s4[1], s4[0], 0x07060302u)), sat);
-                    const us2 h23 = __builtin_elementwise_min(__builtin_bit_cast(us2, __builtin_amdgcn_perm(s4[3], s4[2], 0x07060302u)), sat);
-                    if ((s < 2 || n < 8) && (u < 2 || g < 2))  // window columns / rows < 40
-                        *reinterpret_cast<uint32_t*>(wb + (16 * s + n) * kMwP + 16 * u + 4 * g) =
-                            __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, h23), __builtin_bit_cast(uint32_t, h01), 0x06040200u);
                 }
+                return tmax;
+            };
+            if constexpr (kX86) {
+                // the window's 48 columns all in the SIMD body (wave-uniform)
+                bool fix = x0j + 48 > xbj;
+                if (!fix) fix = tie_lanes(blur_win(std::false_type{})) != 0ull;
+                if (fix) blur_win(std::true_type{});
+            } else {
+                blur_win(std::false_type{});
             }
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -3198,6 +3285,8 @@ __global__ __launch_bounds__(kDescBlock, kWin == kWinMfma ? (kDescGroup < 8 ? OR
         const float sj = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sa), j));
         const uint32_t kc = (uint32_t)__builtin_amdgcn_readlane((int)my_kc, j);
         const float2v SC = float2v{sj, cj}, CSn = float2v{cj, -sj};
+        typedef __attribute__((address_space(3))) const uint8_t lds_u8;
+        const uint32_t wk = (uint32_t)(uintptr_t)(lds_u8*)wb + kc;
         int i0[4], i1[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -3231,9 +3320,9 @@ __global__ __launch_bounds__(kDescBlock, kWin == kWinMfma ? (kDescGroup < 8 ? OR
                 i0[q] = (int)(__float_as_uint(r0y) ^ __float_as_uint(r1x));
                 i1[q] = (int)(__float_as_uint(r1y) + kc);
             } else {
-            if constexpr (kMfma) {  // column-major window
-            i0[q] = wb[__umul24(__float_as_uint(r0x), (uint32_t)kMwP) + __float_as_uint(r0y) + kc];
-            i1[q] = wb[__umul24(__float_as_uint(r1x), (uint32_t)kMwP) + __float_as_uint(r1y) + kc];
+            if constexpr (kMfma) {  // column-major window (wk: its LDS address + kc, one add less)
+            i0[q] = *reinterpret_cast<lds_u8*>((uintptr_t)(__umul24(__float_as_uint(r0x), (uint32_t)kMwP) + __float_as_uint(r0y) + wk));
+            i1[q] = *reinterpret_cast<lds_u8*>((uintptr_t)(__umul24(__float_as_uint(r1x), (uint32_t)kMwP) + __float_as_uint(r1y) + wk));
             } else {
             i0[q] = wb[__umul24(__float_as_uint(r0y), (uint32_t)kDescWinP) + __float_as_uint(r0x) + kc];
             i1[q] = wb[__umul24(__float_as_uint(r1y), (uint32_t)kDescWinP) + __float_as_uint(r1x) + kc];

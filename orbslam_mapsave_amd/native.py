@@ -42,7 +42,7 @@ EXPORTED = [
     "orbfe_extract_color", "orbfe_human_mask_rect", "orbfe_extract_batch",
     "orbfe_extract_batch_device", "orbfe_extract_color_batch_device", "orbfe_set_stream",
     "orbfe_synchronize", "orbfe_compute_stereo_matches", "orbfe_compute_stereo_matches_device",
-    "orbfe_stereo_status", "orbfe_profile", "orbfe_profile_read", "orbfe_pyramid_path", "orbfe_pyramid_tail", "orbfe_debug_replay", "orbfe_set_stage_mask", "orbfe_get_level", "orbfe_get_blurred_level", "orbfe_get_fast_keys",
+    "orbfe_stereo_status", "orbfe_profile", "orbfe_profile_read", "orbfe_pyramid_path", "orbfe_pyramid_tail", "orbfe_describe_blur_fragments", "orbfe_debug_replay", "orbfe_set_stage_mask", "orbfe_get_level", "orbfe_get_blurred_level", "orbfe_get_fast_keys",
     "orbfe_matcher_create", "orbfe_matcher_destroy", "orbfe_matcher_set_stream",
     "orbfe_matcher_profile", "orbfe_matcher_profile_read", "orbfe_matcher_profile_read_stages", "orbfe_hamming",
     "orbfe_bf_match", "orbfe_bf_match_batch_device", "orbfe_search_for_initialization",
@@ -289,6 +289,21 @@ def keypoint_capacity(nfeatures: int, scaleFactor: float, nlevels: int, iniThFAS
     c = lib().orbfe_keypoint_capacity_params(C.byref(p), int(w), int(h))
     _check("orbfe_keypoint_capacity_params", min(c, 0))
     return c
+
+
+def describe_blur_fragments(nfeatures: int, scaleFactor: float, nlevels: int, iniThFAST: int,
+                            minThFAST: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Describe's matrix-core window blur as the host builds it, without a device
+    (orbfe_describe_blur_fragments): the 7 taps, the fragments as int8 [6, 64, 16] (H_0..H_2,
+    V_0..V_2; lane; byte) and the spare K slots' constant bytes as int8 [2, 2, 4]
+    (plane hi / lo; reading scalar / x86; byte i <-> slot j = 12 + i)."""
+    p = Params(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST)
+    taps = np.zeros(7, np.int32)
+    frags = np.zeros(384 * 16, np.uint8)
+    pads = np.zeros(4, np.uint32)
+    _check("orbfe_describe_blur_fragments",
+           lib().orbfe_describe_blur_fragments(C.byref(p), ptr(taps), ptr(frags), ptr(pads)))
+    return taps, frags.view(np.int8).reshape(6, 64, 16), pads.view(np.int8).reshape(2, 2, 4)
 
 
 # ORBFE_PIX_* (include/orbfe.h): the cvtColor codes of Tracking::GrabImage*
