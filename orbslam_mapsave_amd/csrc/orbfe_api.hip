@@ -146,7 +146,7 @@ struct orbfe_extractor {
     Plan plan;
     bool planned = false;
     int frames_cap = 0;
-    DevBuf cells, xtab, ytab, bslot, ptab;
+    DevBuf cells, xtab, ytab, bslot, ptab, ftab;  // ftab: fast_kernel's lane layouts, then the cells' indices
     DescPad desc_pad{};  // with bslot's fragments (blur_frags)
     DevBuf pyr, blur, cell_cnt, cell_keys, keys, act, oct_out, oct_cnt, oct_ord, level_keys;
     DevBuf out_kps, out_desc, out_n;  // staging for the host-pointer entry points
@@ -259,6 +259,9 @@ struct orbfe_extractor {
         // ORBFE_DESC_G16=1 (opt-in): 16 keypoints per describe wave (launch_describe)
         int desc_g16 = (int)env_int("ORBFE_DESC_G16", 0);
         bool no_graph = env_is("ORBFE_NO_GRAPH");  // the single-frame call keeps to plain launches
+        // ORBFE_FAST_LIST_CAP: entries of fast_kernel's survivor list, [322, kFastListCap]; a low
+        // cap makes ordinary small frames flush in most cells (tests/test_gpu_fast_lean.py)
+        int fast_list_cap = (int)std::min<long>(std::max<long>(env_int("ORBFE_FAST_LIST_CAP", kFastListCap), 322), kFastListCap);
     } sw;
     // run(): the pyramid kernel reads level 0 from l0_stage and writes it to the slab level 0
     LevelPtr l0_stage{};
@@ -373,13 +376,20 @@ struct orbfe_extractor {
     int set_plan(int w, int h) {
         if (planned && plan.w == w && plan.h == h) return ORBFE_OK;
         Plan g;
-        int st = plan_geometry(tab, w, h, g, sw.pyr_lds_kb);
+        int st = plan_geometry(tab, w, h, g, sw.pyr_lds_kb, sw.fast_list_cap);
         if (st != ORBFE_OK) return st;
         if ((st = cells.ensure(std::max<size_t>(1, g.cells.size()) * sizeof(CellDesc)))) return st;
         if ((st = xtab.ensure(std::max<size_t>(1, g.xtab.size()) * sizeof(int)))) return st;
         if ((st = ytab.ensure(std::max<size_t>(1, g.ytab.size()) * sizeof(int)))) return st;
         if ((st = bslot.ensure(kBlurFragBytes + g.bitems.size() * sizeof(uint32_t)))) return st;
         if ((st = ptab.ensure(std::max<size_t>(16, g.pyr.tab.size() * sizeof(uint32_t))))) return st;
+        const size_t shape_b = g.fast.shapes.size() * sizeof(uint2);
+        if ((st = ftab.ensure(std::max<size_t>(16, shape_b + g.fast.cell_shape.size() * sizeof(int))))) return st;
+        if (!g.cells.empty()) {
+            ORBFE_HIP(hipMemcpyAsync(ftab.p, g.fast.shapes.data(), shape_b, hipMemcpyHostToDevice, stream));
+            ORBFE_HIP(hipMemcpyAsync(ftab.as<uint8_t>() + shape_b, g.fast.cell_shape.data(),
+                                     g.fast.cell_shape.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        }
         if (!g.pyr.tab.empty())
             ORBFE_HIP(hipMemcpyAsync(ptab.p, g.pyr.tab.data(), g.pyr.tab.size() * sizeof(uint32_t),
                                      hipMemcpyHostToDevice, stream));
@@ -585,6 +595,8 @@ struct orbfe_extractor {
         fa.roi_pitch = p.roi_pitch, fa.roi_rows = p.roi_rows, fa.cand_max = p.cand_max;
         fa.cell_cnt = cell_cnt.as<int>(), fa.cell_keys = cell_keys.as<uint32_t>();
         fa.level_keys = level_keys.as<int>();
+        fa.lane_tab = ftab.as<uint2>();
+        fa.cell_shape = reinterpret_cast<const int*>(fa.lane_tab + p.shapes.size());
         for (int l = 0; l < plan.geo.nlevels; ++l) fa.pyr[l] = lp[l];
         if (p.roi_pitch == kFastPitch)
             ORBFE_LAUNCH(prof, ORBFE_STAGE_FAST, fast_kernel<kFastPitch>, dim3(ncells, n), dim3(kFastBlock), p.lds, stream, fa);
@@ -792,7 +804,7 @@ struct orbfe_extractor {
     }
 
     ~orbfe_extractor() {
-        for (DevBuf* b : {&cells, &xtab, &ytab, &bslot, &ptab, &pyr, &blur, &cell_cnt, &cell_keys, &keys, &act,
+        for (DevBuf* b : {&cells, &xtab, &ytab, &bslot, &ptab, &ftab, &pyr, &blur, &cell_cnt, &cell_keys, &keys, &act,
                           &oct_out, &oct_cnt, &oct_ord, &level_keys, &lk_snap, &out_kps, &out_desc, &out_n, &stage, &rects, &st_off, &st_items,
                           &st_sad, &st_status, &st_ur, &rg_depth, &rg_in, &rg_out, &rg_status})
             b->release();

@@ -1003,9 +1003,40 @@ struct FastArgs {
     int* cell_cnt;         // [frame][cell]
     uint32_t* cell_keys;   // [frame][cell_cap_total]
     int* level_keys;       // [frame][kMaxLevels] keys per level (atomic sums; 0 on entry)
+    const int* cell_shape;   // [cell] index of the cell's lane layout
+    const uint2* lane_tab;   // [shape][kFastShapeStride] (fast_shape)
     LevelPtr pyr[kMaxLevels];
 };
 constexpr int kFastPitch = 48;  // fast_kernel<kFastPitch>: ROI pitch known at compile time
+
+// The pre-test's lane layout of a cell.  A lane tests one 4-pixel group (candidate row lr,
+// group lg) per sweep.  Group g holds ROI-row bytes [4g, 4g + 4) of the staged ROI (dword
+// aligned, P % 16 == 0); candidate columns are X0 .. X0 + nc - 1 (X0 = shift + 3, shift =
+// x0 & 3), so a row spans gpr <= 18 groups (nc <= 66) and a sweep takes rps = 64 / gpr rows.
+// The layout depends on (shift, nc) and the plan's pitch only, so the plan holds one table per
+// distinct pair: a header {gpr, rps, rps * nc, 0} (wave-uniform loads) and per lane
+//   x  0x80 in every byte whose pixel is a candidate column (only a row's first and last
+//      group are partial); 0 for a lane without a group
+//   y  bits 0..15: ROI offset of the group's dword three rows above its centres in sweep 0
+//      (lr * P + 4 * (X0 / 4 + lg): the first dword the pre-test reads, so its other four sit
+//      at non-negative LDS immediates); bits 16..23: lr, or 255 for a lane without a group
+constexpr int kFastShapeStride = 2 + 64;  // uint2 units: 16-byte header, 64 lanes
+inline void fast_shape(int P, int shift, int nc, uint2* out) {
+    const int X0 = shift + 3, g0 = X0 >> 2;
+    const int gpr = nc > 0 ? ((X0 + nc - 1) >> 2) - g0 + 1 : 1;
+    const int rps = 64 / gpr;
+    out[0] = make_uint2((uint32_t)gpr, (uint32_t)rps);
+    out[1] = make_uint2((uint32_t)(rps * std::max(nc, 0)), 0u);
+    for (int lane = 0; lane < 64; ++lane) {
+        const int lr = lane / gpr, lg = lane - lr * gpr;
+        const int gx = 4 * (g0 + lg);  // ROI column of the group's byte 0
+        uint32_t vmask = lr < rps && nc > 0 ? 0x80808080u : 0u;
+        if (lg == 0) vmask &= 0x80808080u << (8 * (X0 - gx));
+        if (lg == gpr - 1) vmask &= 0x80808080u >> (8 * (4 - std::min(X0 + nc - gx, 4)));
+        out[2 + lane] = vmask ? make_uint2(vmask, (uint32_t)(lr * P + gx) | (uint32_t)lr << 16)
+                              : make_uint2(0u, 255u << 16);
+    }
+}
 // FAST survivor-list entries per cell (>= 322: a pre-test sweep adds <= 256 entries and a
 // flush keeps <= 66).  512 covers the ~22 % pre-test pass rate of textured cells without a
 // flush and brings the kernel's LDS to ~4.8 KB per wave (32 waves per CU, from ~25)
@@ -1119,6 +1150,22 @@ __device__ __forceinline__ int fast_S(const uint8_t* p, int st) {
 // Necessary condition for a corner at t (the pre-test): a 9-arc always holds two consecutive
 // cardinal points (0/4/8/12), so both must be brighter than v + t or both darker than v - t.
 
+// LDS accesses by 32-bit address, for the pre-test's per-lane address that advances by a
+// uniform step: a constant added to `addr` becomes the instruction's offset field.
+#define ORBFE_LDS __attribute__((address_space(3)))
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+    return (uint32_t)(uintptr_t)(ORBFE_LDS const void*)p;
+}
+__device__ __forceinline__ uint32_t lds_u32(uint32_t addr) {
+    return *(ORBFE_LDS const uint32_t*)(uintptr_t)addr;
+}
+__device__ __forceinline__ const uint8_t* lds_ptr(uint32_t addr) {
+    return (const uint8_t*)(ORBFE_LDS const uint8_t*)(uintptr_t)addr;
+}
+__device__ __forceinline__ void lds_store_u16(uint32_t addr, uint32_t v) {
+    *(ORBFE_LDS uint16_t*)(uintptr_t)addr = (uint16_t)v;
+}
+
 __device__ __forceinline__ int lane_prefix(unsigned long long mask) {
     return __popcll(mask & ((1ull << (threadIdx.x & 63)) - 1));
 }
@@ -1141,6 +1188,12 @@ __device__ __forceinline__ unsigned long long byte_ballot(uint32_t fl) {
 }
 // b where this lane's bit of m is set, else a: one v_cndmask on the lane mask itself (a
 // ballot's SGPR pair), no per-lane compare to rebuild the condition.
+// a + 1 where this lane's bit of m is set, else a: the mask is the add's carry-in.
+__device__ __forceinline__ uint32_t lane_inc(unsigned long long m, uint32_t a) {
+    uint32_t r;
+    asm("v_addc_co_u32 %0, vcc, 0, %1, %2" : "=v"(r) : "v"(a), "s"(m) : "vcc");
+    return r;
+}
 __device__ __forceinline__ int lane_select(unsigned long long m, int a, int b) {
     int r;
     asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(m));
@@ -1161,8 +1214,12 @@ __device__ __forceinline__ int lane_select(unsigned long long m, int a, int b) {
 #ifndef ORBFE_FAST_EMIT2
 #define ORBFE_FAST_EMIT2 1
 #endif
+//
+// fast_kernel's entries are o + o0: offsets from the staged ROI's dword-aligned origin (c
+// carries the cell's x0 & 3) as LDS addresses; it passes S and the key origin (kx, ky) shifted
+// to match.
 __device__ __forceinline__ int fast_emit(const uint8_t* S, uint16_t* list, int cnt, int P,
-                                         unsigned inv_p, int t, const CellDesc& cell,
+                                         unsigned inv_p, int t, int kx, int ky, uint32_t o0,
                                          uint32_t* out, int cap) {
     const int tb = max(t, 1) + 1;
     if (ORBFE_FAST_EMIT2) {
@@ -1197,10 +1254,9 @@ __device__ __forceinline__ int fast_emit(const uint8_t* S, uint16_t* list, int c
         const unsigned long long m = __ballot(keep);
         if (keep) {
             const int slot = o + lane_prefix(m);
-            const int r = (int)__umulhi((unsigned)off, inv_p), cc = off - r * P;
+            const int o = off - (int)o0, r = (int)__umulhi((unsigned)o, inv_p), cc = o - r * P;
             // key relative to (minBorderX, minBorderY): pt + (j*wCell, i*hCell) (819-824)
-            if (slot < cap)
-                out[slot] = pack_key(cell.x0 + 3 + cc - kMinBorder, cell.y0 + 3 + r - kMinBorder, sb - 1);
+            if (slot < cap) out[slot] = pack_key(kx + cc, ky + r, sb - 1);
         }
         o += __popcll(m);
     }
@@ -1243,6 +1299,10 @@ __global__ __launch_bounds__(kFastBlock) void fast_kernel(FastArgs a) {
     long long ftc = ft_start;
 #endif
     const CellDesc cell = a.cells[c];
+    // the lane's pre-test layout (fast_shape), loaded ahead of the ROI rows
+    const uint2* shape = a.lane_tab + a.cell_shape[c] * kFastShapeStride;
+    const uint2 le = shape[2 + lane];
+    const int rps = (int)shape[0].y;  // candidate rows per sweep
     const LevelPtr lp = a.pyr[cell.level];
     const int rows = cell.y1 - cell.y0, cols = cell.x1 - cell.x0;
     const int P = kP ? kP : a.roi_pitch;
@@ -1256,44 +1316,50 @@ __global__ __launch_bounds__(kFastBlock) void fast_kernel(FastArgs a) {
     const int x0a = cell.x0 & ~3, shift = cell.x0 - x0a;
     const int nq = (shift + cols + 15) >> 4;
     const uint8_t* img = lp.base + f * lp.fpitch + (long long)cell.y0 * lp.pitch + x0a;
-    for (int r0 = 0; r0 < rows; r0 += 64) {
-        const int r = r0 + lane;
-        if (r < rows) {
-            const uint8_t* src = img + (long long)r * lp.pitch;
-            uint4 v[5];
+    // One uniform base plus a 32-bit lane offset per row, and the chunk count as a uniform
+    // switch around the row loop: inside it the count would become a per-lane predicate.
+    auto stage = [&](auto chunks) {
+        constexpr int kQ = decltype(chunks)::value;
+#pragma unroll 1
+        for (int r0 = 0; r0 < rows; r0 += 64) {
+            const int r = r0 + lane;
+            if (r < rows) {
+                const uint8_t* src = img + (uint32_t)(r * lp.pitch);
+                uint4 v[kQ];
 #pragma unroll
-            for (int q = 0; q < 5; ++q)
-                if (q < nq) v[q] = load16_a4(src + 16 * q);
+                for (int q = 0; q < kQ; ++q) v[q] = load16_a4(src + 16 * q);
 #pragma unroll
-            for (int q = 0; q < 5; ++q)
-                if (q < nq) *reinterpret_cast<uint4*>(roi_base + r * P + 16 * q) = v[q];
+                for (int q = 0; q < kQ; ++q) *reinterpret_cast<uint4*>(roi_base + r * P + 16 * q) = v[q];
+            }
         }
+    };
+    switch (nq) {
+        case 1: stage(std::integral_constant<int, 1>{}); break;
+        case 2: stage(std::integral_constant<int, 2>{}); break;
+        case 3: stage(std::integral_constant<int, 3>{}); break;
+        case 4: stage(std::integral_constant<int, 4>{}); break;
+        default: stage(std::integral_constant<int, 5>{}); break;
     }
-    const uint8_t* roi = roi_base + shift;
     const int nr = rows - 6, nc = cols - 6;  // candidates: ROI rows/cols 3 .. n-4
     const int ncand = (nr > 0 && nc > 0) ? nr * nc : 0;
     // score plane: ROI pitch, rows -1 .. nr of the candidates, zero border
     // (16-byte stores: S is 16-byte aligned and (nr + 2) * P a multiple of 16)
     for (int i = lane; i < (ncand ? ((nr + 2) * P) >> 4 : 0); i += 64) reinterpret_cast<uint4*>(S)[i] = make_uint4(0u, 0u, 0u, 0u);
     const unsigned inv_p = 0xffffffffu / (unsigned)P + 1u;  // r = umulhi(o, inv_p) for o < 2^16
-    // Pre-test lanes: (candidate row lr, 4-pixel group lg).  Group g holds ROI-row bytes
-    // [4g, 4g + 4) of roi_base (dword aligned, P % 16 == 0); candidate columns are
-    // X0 .. X0 + nc - 1 (X0 = shift + 3), so a row spans gpr <= 18 groups (nc <= 66).
-    const int X0 = shift + 3, g0 = X0 >> 2;
-    const int gpr = ncand ? ((X0 + nc - 1) >> 2) - g0 + 1 : 1;
-    const int rps = 64 / gpr;  // candidate rows per sweep
-    // lane / gpr through the float reciprocal of the (wave-uniform) gpr <= 18: floor((lane +
-    // 0.5) / gpr) is at least 0.5 / gpr from an integer, far above rcp's error (the integer
-    // division cost ~20 VALU per cell)
-    const int lr = (int)(((float)lane + 0.5f) * __builtin_amdgcn_rcpf((float)gpr)), lg = lane - lr * gpr;
-    const int gx = 4 * (g0 + lg);  // roi_base column of the group's byte 0
-    // 0x80 in every byte whose pixel is a candidate column: only the row's first group (bytes
-    // before X0) and last group (bytes from X0 + nc) are partial
-    uint32_t vmask = lr < rps && ncand ? 0x80808080u : 0u;
-    if (lg == 0) vmask &= 0x80808080u << (8 * (X0 - gx));
-    if (lg == gpr - 1) vmask &= 0x80808080u >> (8 * (4 - min(X0 + nc - gx, 4)));
-    const uint32_t* lds32 = reinterpret_cast<const uint32_t*>(roi_base);
-    const int P4 = P >> 2;
+    // A list entry is the LDS address lds0 + o, o = r * P + shift + c, of candidate (r, c)'s
+    // 7 x 7 window's top-left byte (the whole carve lies below 64 KB): the circle's 16 offsets
+    // and the centre are non-negative LDS immediates from it, c + shift < P keeps r = o / P,
+    // and the pre-test has it without a multiply (the lane's dword address less 3).  The score
+    // plane and the keys' origin shift to match.
+    const uint32_t lds0 = lds_addr(roi_base), list0 = lds_addr(list);
+    uint8_t* Sk = S - shift - lds0;  // candidate (r, c) scores at Sk[entry + P + 1]
+    const int kx = x0a + 3 - kMinBorder, ky = cell.y0 + 3 - kMinBorder;
+    const uint32_t vmask = le.x;
+    const int lre = (int)(le.y >> 16);  // the lane's candidate row in sweep 0; 255: no group
+    const uint32_t u0 = lds0 + (le.y & 0xffffu);  // LDS address of the lane's first dword, sweep 0
+    const int step = rps * P;                     // a sweep's advance
+    // a byte that is not a survivor writes the lane's trash slot past the list
+    const uint32_t tr = list0 + 2u * (uint32_t)(a.cand_max + lane);
     fast_sync();
 #ifdef ORBFE_FAST_TIMING
     FT_ADD(0, ftc);
@@ -1311,7 +1377,7 @@ __global__ __launch_bounds__(kFastBlock) void fast_kernel(FastArgs a) {
         for (int i = from + lane; i < to; i += 64) {
             const int o = list[i];
             // S < 0 is never a corner for t >= 0: clamp to -1 so S + 1 fits a byte
-            S[o + P + 1] = (uint8_t)(max(fast_S(roi + o + 3 * P + 3, P), -1) + 1);
+            Sk[o + P + 1] = (uint8_t)(max(fast_S(lds_ptr(o) + 3 * P + 3, P), -1) + 1);
         }
     };
     // The list holds cand_max entries (not one per candidate pixel: ~22 % pass the pre-test on
@@ -1319,8 +1385,10 @@ __global__ __launch_bounds__(kFastBlock) void fast_kernel(FastArgs a) {
     // sweep that could overflow it, the entries so far are scored and those of rows up to
     // r0 - 2 — whose 3 x 3 neighbourhoods are complete — are emitted; the last pre-tested row's
     // entries move to the front (<= nc <= 66 of them; a sweep adds <= rps * nc <= 256, so
-    // cand_max >= 322 always makes progress).
-    const int sweep_max = rps * nc;
+    // cand_max >= 322 always makes progress).  (Flushing only when the sweep's counted
+    // survivors overflow, and compacting the corners inside the score loop, cut instructions
+    // and cost time: DESIGN.md §5k.)
+    const int sweep_max = (int)shape[1].x;  // rps * nc
     int total = 0;
     for (int pass = 0; pass < 2 && total == 0; ++pass) {
         const int t = pass ? a.min_th : a.ini_th;  // rerun at minThFAST when empty (811-815)
@@ -1340,36 +1408,38 @@ __global__ __launch_bounds__(kFastBlock) void fast_kernel(FastArgs a) {
         // t = 255 the byte 256 - M wraps to 0 and every pixel passes, but no score reaches 255
         const uint32_t M2 = (uint32_t)(128 + ((t + 1) >> 1)) * 0x01010101u;
         int cnt = 0, scored = 0, emitted = 0;
-        for (int r0 = 0; r0 < nr; r0 += rps) {
-            if (cnt + sweep_max > a.cand_max) {  // wave-uniform
+        auto flush = [&](int rp) {  // before the sweep at candidate row r0 = rp / P
 #ifdef ORBFE_FAST_TIMING
-                FT_CNT(11, 1);
-                FT_CNT(9, cnt - scored);
+            FT_CNT(11, 1);
+            FT_CNT(9, cnt - scored);
 #endif
-                fast_sync();
-                score(scored, cnt);
-                fast_sync();
-                const int lim = (r0 - 1) * P;  // entries of rows <= r0 - 2 lie below
-                int k = 0;
-                for (int i0 = 0; i0 < cnt; i0 += 64)
-                    k += __popcll(__ballot(i0 + lane < cnt && list[i0 + lane] < lim));
-                emitted += fast_emit(S, list, k, P, inv_p, t, cell, out + emitted, cell.cap - emitted);
-                const int n1 = cnt - k;
-                const int e0 = lane < n1 ? list[k + lane] : 0, e1 = lane + 64 < n1 ? list[k + 64 + lane] : 0;
-                fast_sync();
-                if (lane < n1) list[lane] = (uint16_t)e0;
-                if (lane + 64 < n1) list[lane + 64] = (uint16_t)e1;
-                cnt = scored = n1;
+            fast_sync();
+            score(scored, cnt);
+            fast_sync();
+            const int lim = (int)lds0 + rp - P;  // entries of rows <= r0 - 2 lie below
+            int k = 0;
+            for (int i0 = 0; i0 < cnt; i0 += 64)
+                k += __popcll(__ballot(i0 + lane < cnt && list[i0 + lane] < lim));
+            emitted += fast_emit(Sk, list, k, P, inv_p, t, kx, ky, lds0, out + emitted, cell.cap - emitted);
+            const int n1 = cnt - k;
+            const int e0 = lane < n1 ? list[k + lane] : 0, e1 = lane + 64 < n1 ? list[k + 64 + lane] : 0;
+            fast_sync();
+            if (lane < n1) list[lane] = (uint16_t)e0;
+            if (lane + 64 < n1) list[lane + 64] = (uint16_t)e1;
+            cnt = scored = n1;
 #ifdef ORBFE_FAST_TIMING
-                FT_ADD(5, ftc);
+            FT_ADD(5, ftc);
 #endif
-            }
-            const int cr = r0 + lr;
+        };
+        // rp = r0 * P and the rows left advance by uniform steps; u is the lane's dword three
+        // rows above its centres, so a sweep's five dwords sit at fixed offsets from it
+        for (int rp = 0, left = nr; left > 0; rp += step, left -= rps) {
+            if (cnt + sweep_max > a.cand_max) flush(rp);  // wave-uniform
+            const uint32_t u = u0 + (uint32_t)rp;
             uint32_t fl = 0;
-            if (vmask && cr < nr) {
-                const int w = (cr + 3) * P4 + (gx >> 2);  // dword of the group's centres
-                const uint32_t cur = lds32[w], prv = lds32[w - 1], nxt = lds32[w + 1];
-                const uint32_t up = lds32[w - 3 * P4], dn = lds32[w + 3 * P4];
+            if (lre < left) {
+                const uint32_t up = lds_u32(u), dn = lds_u32(u + 6 * P);
+                const uint32_t prv = lds_u32(u + 3 * P - 4), cur = lds_u32(u + 3 * P), nxt = lds_u32(u + 3 * P + 4);
                 const uint32_t c4 = __builtin_amdgcn_alignbyte(nxt, cur, 3);   // column + 3
                 const uint32_t c12 = __builtin_amdgcn_alignbyte(cur, prv, 1);  // column - 3
                 const uint32_t ncur = ~cur;
@@ -1389,39 +1459,41 @@ __global__ __launch_bounds__(kFastBlock) void fast_kernel(FastArgs a) {
             FT_ADD(1, ftc);
             FT_CNT(8, 1);
 #endif
-            if (fl) {  // row-major: earlier lanes, then this lane's lower bytes
+            const int add = __popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3);
+            if (add) {  // wave-uniform; row-major: earlier lanes, then this lane's lower bytes
                 auto below = [](unsigned long long b, uint32_t acc) {  // popc(b & lanes below)
                     return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32),
                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)b, acc));
                 };
-                int pos = (int)below(b3, below(b2, below(b1, below(b0, (uint32_t)cnt))));
-                const int ob = cr * P + gx - X0;  // ROI offset of byte 0's window
+                uint32_t pos = below(b3, below(b2, below(b1, below(b0, (uint32_t)cnt))));
+                auto at = [&](uint32_t i) { return list0 + 2u * i; };  // LDS address of entry i
+                const uint32_t ob = u - 3u;  // byte 0's window
                 // unconditional stores (no exec-mask branch per byte): a byte that is not a
                 // survivor writes the lane's trash slot past the list; the slot is chosen by the
                 // byte's ballot mask directly
-                const int tr = a.cand_max + lane;
-                const int f0 = (fl >> 7) & 1, f1 = (fl >> 15) & 1, f2 = (fl >> 23) & 1;
-                list[lane_select(b0, tr, pos)] = (uint16_t)ob;
-                pos += f0;
-                list[lane_select(b1, tr, pos)] = (uint16_t)(ob + 1);
-                pos += f1;
-                list[lane_select(b2, tr, pos)] = (uint16_t)(ob + 2);
-                pos += f2;
-                list[lane_select(b3, tr, pos)] = (uint16_t)(ob + 3);
+                lds_store_u16(lane_select(b0, tr, at(pos)), ob);
+                pos = lane_inc(b0, pos);
+                lds_store_u16(lane_select(b1, tr, at(pos)), ob + 1);
+                pos = lane_inc(b1, pos);
+                lds_store_u16(lane_select(b2, tr, at(pos)), ob + 2);
+                pos = lane_inc(b2, pos);
+                lds_store_u16(lane_select(b3, tr, at(pos)), ob + 3);
             }
-            cnt += __popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3);
+            cnt += add;
 #ifdef ORBFE_FAST_TIMING
             FT_ADD(2, ftc);
 #endif
         }
         fast_sync();
+#ifdef ORBFE_FAST_TIMING
+        FT_CNT(9, cnt - scored);
+#endif
         score(scored, cnt);
         fast_sync();
 #ifdef ORBFE_FAST_TIMING
         FT_ADD(3, ftc);
-        FT_CNT(9, cnt - scored);
 #endif
-        total = emitted + fast_emit(S, list, cnt, P, inv_p, t, cell, out + emitted, cell.cap - emitted);
+        total = emitted + fast_emit(Sk, list, cnt, P, inv_p, t, kx, ky, lds0, out + emitted, cell.cap - emitted);
         fast_sync();
 #ifdef ORBFE_FAST_TIMING
         FT_ADD(4, ftc);
@@ -3704,8 +3776,9 @@ static int plan_pyramid(Plan& g, int lds_cap_kb) {
     return ORBFE_OK;
 }
 
-// fast_kernel's dynamic LDS for the largest cell ROI of the plan's cell list.
-static int plan_fast(Plan& g) {
+// fast_kernel's dynamic LDS for the largest cell ROI of the plan's cell list, and the cells'
+// lane layouts.  list_cap: the survivor list's entries (ORBFE_FAST_LIST_CAP; kFastListCap).
+static int plan_fast(Plan& g, int list_cap) {
     Plan::Fast& p = g.fast;
     int rmax = 7, cmax = 7;
     for (const CellDesc& c : g.cells) {
@@ -3715,11 +3788,25 @@ static int plan_fast(Plan& g) {
     p.roi_rows = rmax;
     p.roi_pitch = (cmax + 3 + 15) & ~15;  // + alignment shift, 16-byte rows for b128 LDS writes
     // FAST survivor list: every candidate pixel up to kFastListCap, else flushed (fast_kernel)
-    p.cand_max = std::min((rmax - 6) * (cmax - 6), kFastListCap);
+    p.cand_max = std::min((rmax - 6) * (cmax - 6), std::min(std::max(list_cap, 322), kFastListCap));
     // ROI + zero-bordered score plane at the ROI pitch + candidate list of u16 ROI offsets
     if ((long long)rmax * p.roi_pitch >= 65536) return ORBFE_ERR_UNSUPPORTED;
     p.lds = (size_t)rmax * p.roi_pitch + (((rmax - 4) * p.roi_pitch + 15) & ~15) +
             2 * (size_t)p.cand_max + 16 + 128;  // + a trash slot per lane
+    p.shapes.clear();
+    p.cell_shape.clear();
+    std::vector<int> seen(4 * (cmax + 1), -1);  // shape index by (shift, nc)
+    for (const CellDesc& c : g.cells) {
+        const int shift = c.x0 & 3;
+        const int nc = c.y1 - c.y0 > 6 ? std::max(c.x1 - c.x0 - 6, 0) : 0;
+        int& s = seen[shift * (cmax + 1) + nc];
+        if (s < 0) {
+            s = (int)(p.shapes.size() / kFastShapeStride);
+            p.shapes.resize(p.shapes.size() + kFastShapeStride);
+            fast_shape(p.roi_pitch, shift, nc, &p.shapes[(size_t)s * kFastShapeStride]);
+        }
+        p.cell_shape.push_back(s);
+    }
     return ORBFE_OK;
 }
 
@@ -3746,12 +3833,14 @@ static void plan_octree(Plan& g) {
 }
 
 // Plans every size-dependent table for a w x h input (cached per extractor).  pyr_lds_kb: the
-// LDS cap of pyramid_kernel's band plans (the extractor passes its ORBFE_PYR_LDS_KB).
-int plan_geometry(const HostTables& t, int w, int h, Plan& g, int pyr_lds_kb = kPyrLdsCapKB) {
+// LDS cap of pyramid_kernel's band plans (the extractor passes its ORBFE_PYR_LDS_KB);
+// fast_list_cap: fast_kernel's survivor-list entries (its ORBFE_FAST_LIST_CAP).
+int plan_geometry(const HostTables& t, int w, int h, Plan& g, int pyr_lds_kb = kPyrLdsCapKB,
+                  int fast_list_cap = kFastListCap) {
     int st;
     if ((st = plan_levels(t, w, h, g))) return st;
     if ((st = plan_pyramid(g, pyr_lds_kb))) return st;
-    if ((st = plan_fast(g))) return st;
+    if ((st = plan_fast(g, fast_list_cap))) return st;
     plan_octree(g);
     blur_items(g.geo, g.bitems);
     return ORBFE_OK;

@@ -140,6 +140,10 @@ struct Plan {
     struct Fast {  // plan_fast: the dynamic-LDS carve of fast_kernel
         int roi_pitch = 0, roi_rows = 0, cand_max = 0;
         size_t lds = 0;
+        // the pre-test's lane layouts, one per distinct (x0 & 3, candidate columns) of the
+        // cells: kFastShapeStride uint2 each (fast_shape), and each cell's index into them
+        std::vector<uint2> shapes;
+        std::vector<int> cell_shape;
     } fast;
     struct Oct {  // plan_octree
         int ncap_max = 0, sort_cap = 0;
