@@ -16,6 +16,9 @@
 //   cov_move_kernel / cov_set_ordered_kernel / cov_pos_kernel   rows that outgrow their region,
 //                      the plain assignment of an ordered list, the batch positions
 //
+// The graph's columns, its row table (four lanes of cap ints per row) and pool are the store's
+// (orbfe_map_store.hip): cov_ready() there makes them cover the map, CovDev is their view.
+//
 // A sequential batch has a closed form (tests/test_covis.py proves it against the literal loop on
 // built and seeded maps): the counter C_i of keyframe i depends on points and
 // observations only; i tells j when C_i[j] >= 15, or when no count of i reaches 15 and j is i's
@@ -226,11 +229,11 @@ __global__ __launch_bounds__(kCovBlock) void cov_count_kernel(CovCountArgs a) {
 
 struct CovMergeArgs {
     MapDev d;
+    CovDev g;
     int op, apply, single;   // single >= 0: the one keyframe the launch is about
     // kCovOpBatch
     int n;
     const int* batch;
-    const int* pos;          // [n_kf] position in the batch or -1
     const uint8_t* allow;    // [n] or NULL
     const int* c_n;
     const long long* c_off;
@@ -240,18 +243,7 @@ struct CovMergeArgs {
     int slot, other, weight;
     int n_staged;
     const int* staged;       // kCovOpSetWeights: n_staged slots, then their weights
-    // the graph: row j is 4 arrays of cap[j] ints at pool + off[j]
-    int* pool;
-    const long long* off;
-    const int* cap;
-    int* nw;
-    int* no;
-    uint8_t* first;
-    int* res;                // [3 n_kf] deciding: the weight map's and the list's new length, act
     int* parent_out;         // [n]
-    int* kf_neigh;
-    int* kf_parent;
-    int* err;
 };
 
 __global__ __launch_bounds__(kCovBlock) void cov_merge_kernel(CovMergeArgs a) {
@@ -264,15 +256,15 @@ __global__ __launch_bounds__(kCovBlock) void cov_merge_kernel(CovMergeArgs a) {
     const MapDev& d = a.d;
     const int tid = threadIdx.x;
     const int j = a.single >= 0 ? a.single : (int)blockIdx.x;
-    int* const res = a.res + 3 * (size_t)j;
+    int* const res = a.g.res + 3 * (size_t)j;
     if (a.apply && res[2] == 0) return;
     const unsigned long long key_j = d.kf_key[j];
-    const int cap = a.cap[j];
-    int* const w_slot = a.pool + a.off[j];
+    const int cap = a.g.cap[j];
+    int* const w_slot = a.g.pool + a.g.off[j];
     int* const w_weight = w_slot + cap;
     int* const o_slot = w_slot + 2 * (size_t)cap;
     int* const o_weight = w_slot + 3 * (size_t)cap;
-    const int old_nw = min(a.nw[j], min(cap, kCovMax)), old_no = a.no[j];
+    const int old_nw = min(a.g.nw[j], min(cap, kCovMax)), old_no = a.g.no[j];
     if (tid == 0) s_nt = s_changed = s_cnt = 0;
     __syncthreads();
 
@@ -280,14 +272,14 @@ __global__ __launch_bounds__(kCovBlock) void cov_merge_kernel(CovMergeArgs a) {
         if (!a.apply) {
             if (tid == 0) res[0] = 0, res[1] = 0, res[2] = 1;
         } else {
-            if (tid == 0) a.nw[j] = 0, a.no[j] = 0;
-            if (tid < kMapNeigh) a.kf_neigh[j * kMapNeigh + tid] = -1;
+            if (tid == 0) a.g.nw[j] = 0, a.g.no[j] = 0;
+            if (tid < kMapNeigh) d.kf_neigh[j * kMapNeigh + tid] = -1;
         }
         return;
     }
 
     // ---- the base row: the keyframe's new counter (:1088), else its weights as they are
-    const int pj = a.op == kCovOpBatch ? a.pos[j] : -1;
+    const int pj = a.op == kCovOpBatch ? a.g.pos[j] : -1;
     const bool own = pj >= 0 && a.c_n[pj] > 0;  // an empty counter returns with nothing changed (:1044)
     int nb = 0, n_told = 0;
     if (own) {
@@ -320,7 +312,7 @@ __global__ __launch_bounds__(kCovBlock) void cov_merge_kernel(CovMergeArgs a) {
         n_told = s_cnt;
         if (a.apply) {
             if (n_told > cap) {
-                if (tid == 0) atomicOr(a.err, kCovErrInternal);
+                if (tid == 0) atomicOr(&d.ctl[kCtlCallErr], kCovErrInternal);
                 return;
             }
             for (int k = tid; k < n_told; k += kCovBlock) {
@@ -328,17 +320,17 @@ __global__ __launch_bounds__(kCovBlock) void cov_merge_kernel(CovMergeArgs a) {
                 cov_list_entry(ok, P, k, r, w);
                 o_slot[k] = bs[r];
                 o_weight[k] = w;
-                if (k < kMapNeigh) a.kf_neigh[j * kMapNeigh + k] = bs[r];
+                if (k < kMapNeigh) d.kf_neigh[j * kMapNeigh + k] = bs[r];
             }
-            if (tid >= n_told && tid < kMapNeigh) a.kf_neigh[j * kMapNeigh + tid] = -1;
+            if (tid >= n_told && tid < kMapNeigh) d.kf_neigh[j * kMapNeigh + tid] = -1;
             if (tid == 0) {
                 int parent = -1;
-                if (a.first[j] && (!a.allow || a.allow[pj])) {
+                if (a.g.first[j] && (!a.allow || a.allow[pj])) {
                     int r, w;
                     cov_list_entry(ok, P, 0, r, w);
                     parent = bs[r];  // the front: highest weight, highest key among ties
-                    a.kf_parent[j] = parent;
-                    a.first[j] = 0;
+                    d.kf_parent[j] = parent;
+                    a.g.first[j] = 0;
                 }
                 a.parent_out[pj] = parent;
             }
@@ -379,8 +371,8 @@ __global__ __launch_bounds__(kCovBlock) void cov_merge_kernel(CovMergeArgs a) {
         if (tid == 0) {
             bool told = a.apply != 0;  // applying: decided already; the erased row is being cleared
             if (!a.apply) {            // :1188: every key of the erased keyframe's weight map
-                const int sn = min(a.nw[a.slot], a.cap[a.slot]);
-                const int* sp = a.pool + a.off[a.slot];
+                const int sn = min(a.g.nw[a.slot], a.g.cap[a.slot]);
+                const int* sp = a.g.pool + a.g.off[a.slot];
                 const int lo = cov_lower_bound_slots(sp, sn, d.kf_key, key_j);
                 told = lo < sn && sp[lo] == j;
             }
@@ -402,7 +394,7 @@ __global__ __launch_bounds__(kCovBlock) void cov_merge_kernel(CovMergeArgs a) {
     const int nt = s_nt;
     if (nt > kCovMax) {  // as many distinct keys: the weight map would pass kCovMax
         if (tid == 0) {
-            atomicOr(a.err, kCovErrCapacity);
+            atomicOr(&d.ctl[kCtlCallErr], kCovErrCapacity);
             res[0] = old_nw, res[1] = old_no, res[2] = 0;
         }
         return;
@@ -464,7 +456,7 @@ __global__ __launch_bounds__(kCovBlock) void cov_merge_kernel(CovMergeArgs a) {
     const bool act = own || s_changed || resort || a.op == kCovOpSetWeights;
     if (n_new > kCovMax) {
         if (tid == 0) {
-            atomicOr(a.err, kCovErrCapacity);
+            atomicOr(&d.ctl[kCtlCallErr], kCovErrCapacity);
             res[0] = old_nw, res[1] = old_no, res[2] = 0;
         }
         return;
@@ -479,7 +471,7 @@ __global__ __launch_bounds__(kCovBlock) void cov_merge_kernel(CovMergeArgs a) {
     }
     if (!act) return;
     if (n_new > cap) {
-        if (tid == 0) atomicOr(a.err, kCovErrInternal);
+        if (tid == 0) atomicOr(&d.ctl[kCtlCallErr], kCovErrInternal);
         return;
     }
     // ---- the merged row, in key order; the raw tells in ms / mw are dead
@@ -499,8 +491,8 @@ __global__ __launch_bounds__(kCovBlock) void cov_merge_kernel(CovMergeArgs a) {
         w_weight[t] = mw[t];
     }
     if (tid == 0) {
-        a.nw[j] = n_new;
-        if (own && !resort) a.no[j] = n_told;
+        a.g.nw[j] = n_new;
+        if (own && !resort) a.g.no[j] = n_told;
     }
     if (!resort) return;
     // ---- UpdateBestCovisibles (:859-878): the whole row
@@ -515,10 +507,10 @@ __global__ __launch_bounds__(kCovBlock) void cov_merge_kernel(CovMergeArgs a) {
         cov_list_entry(ok, P, k, r, w);
         o_slot[k] = ms[r];
         o_weight[k] = w;
-        if (k < kMapNeigh) a.kf_neigh[j * kMapNeigh + k] = ms[r];
+        if (k < kMapNeigh) d.kf_neigh[j * kMapNeigh + k] = ms[r];
     }
-    if (tid >= n_new && tid < kMapNeigh) a.kf_neigh[j * kMapNeigh + tid] = -1;
-    if (tid == 0) a.no[j] = n_new;
+    if (tid >= n_new && tid < kMapNeigh) d.kf_neigh[j * kMapNeigh + tid] = -1;
+    if (tid == 0) a.g.no[j] = n_new;
 }
 
 // A row that outgrew its region moves to a new one: both lists copied, then (off, cap).
@@ -527,8 +519,12 @@ struct CovMoveItem {
     int j, new_cap;
 };
 
-__global__ __launch_bounds__(256) void cov_move_kernel(const CovMoveItem* items, int* pool, long long* off,
-                                                       int* cap, const int* nw, const int* no) {
+__global__ __launch_bounds__(256) void cov_move_kernel(const CovMoveItem* items, CovDev g) {
+    int* const pool = g.pool;
+    long long* const off = g.off;
+    int* const cap = g.cap;
+    const int* const nw = g.nw;
+    const int* const no = g.no;
     const CovMoveItem it = items[blockIdx.x];
     const long long oo = off[it.j];
     const int oc = cap[it.j];
@@ -549,12 +545,12 @@ __global__ __launch_bounds__(256) void cov_move_kernel(const CovMoveItem* items,
 }
 
 // mvpOrderedConnectedKeyFrames / mvOrderedWeights assigned: staged = n slots, then n weights.
-__global__ __launch_bounds__(256) void cov_set_ordered_kernel(int j, int n, const int* staged, int* pool,
-                                                              const long long* off, const int* cap, int* no,
+__global__ __launch_bounds__(256) void cov_set_ordered_kernel(int j, int n, const int* staged, CovDev g,
                                                               int* kf_neigh) {
-    const int c = cap[j];
+    int* const no = g.no;
+    const int c = g.cap[j];
     if (n > c) return;
-    int* const o_slot = pool + off[j] + 2ll * c;
+    int* const o_slot = g.pool + g.off[j] + 2ll * c;
     int* const o_weight = o_slot + c;
     for (int t = threadIdx.x; t < n; t += 256) {
         o_slot[t] = staged[t];
@@ -573,170 +569,84 @@ __global__ __launch_bounds__(256) void cov_pos_kernel(int n, const int* batch, i
 
 namespace {
 
-struct MapCovis {
-    int n_known = 0, alloc = 0;            // keyframes the per-keyframe arrays cover / hold
-    DevBuf pool, off, cap, nw, no, first;  // the graph
-    std::vector<long long> h_off;          // the host keeps where the rows are and how long
-    std::vector<int> h_cap, h_nw, h_no;
-    long long used = 0, pool_alloc = 0;
-    DevBuf batch, pos, allow, c_n, c_off, c_slot, c_w, res, pout, err, stage, items;  // scratch
-};
-
-void map_covis_free(MapCovis* c) { delete c; }
-
-void map_covis_reset(MapCovis* c) {
-    if (!c) return;
-    c->n_known = 0;
-    c->used = 0;
-    c->h_off.clear();
-    c->h_cap.clear();
-    c->h_nw.clear();
-    c->h_no.clear();
-}
-
-// The state covers every keyframe of the map: a new one has no connections and the flag set.
-int cov_ready(orbfe_map* m) {
-    if (!m->covis) m->covis = new MapCovis();
-    MapCovis* c = m->covis;
-    int st;
-    if (m->n_kf > c->alloc) {
-        int n = std::max(2 * c->alloc, 16);
-        while (n < m->n_kf) n *= 2;
-        const size_t k = (size_t)c->n_known;
-        if ((st = map_regrow(m, c->off, 8, k, n))) return st;
-        if ((st = map_regrow(m, c->cap, sizeof(int), k, n))) return st;
-        if ((st = map_regrow(m, c->nw, sizeof(int), k, n))) return st;
-        if ((st = map_regrow(m, c->no, sizeof(int), k, n))) return st;
-        if ((st = map_regrow(m, c->first, 1, k, n))) return st;
-        if ((st = c->res.ensure(3 * sizeof(int) * (size_t)n))) return st;
-        if ((st = c->pos.ensure(sizeof(int) * (size_t)n))) return st;
-        c->alloc = n;
-    }
-    if ((st = c->err.ensure(sizeof(int)))) return st;
-    if (m->n_kf > c->n_known) {
-        const size_t o = (size_t)c->n_known, k = (size_t)(m->n_kf - c->n_known);
-        ORBFE_HIP(hipMemsetAsync(c->off.as<long long>() + o, 0, 8 * k, m->stream));
-        ORBFE_HIP(hipMemsetAsync(c->cap.as<int>() + o, 0, sizeof(int) * k, m->stream));
-        ORBFE_HIP(hipMemsetAsync(c->nw.as<int>() + o, 0, sizeof(int) * k, m->stream));
-        ORBFE_HIP(hipMemsetAsync(c->no.as<int>() + o, 0, sizeof(int) * k, m->stream));
-        ORBFE_HIP(hipMemsetAsync(c->first.as<uint8_t>() + o, 1, k, m->stream));  // KeyFrame.cc:41
-        ORBFE_HIP(hipStreamSynchronize(m->stream));
-        c->h_off.resize((size_t)m->n_kf, 0);
-        c->h_cap.resize((size_t)m->n_kf, 0);
-        c->h_nw.resize((size_t)m->n_kf, 0);
-        c->h_no.resize((size_t)m->n_kf, 0);
-        c->n_known = m->n_kf;
-    }
-    return ORBFE_OK;
-}
-
-// Rows `need` = (keyframe, entries) get regions of at least that many entries: a new region of
-// a power of two at the pool's end (the old one is not reused), the pool doubling, one launch.
+// Rows `need` = (keyframe, entries) get regions of at least that many entries, their contents
+// kept: the table's plan, the pool's growth, one launch.
 int cov_reserve(orbfe_map* m, const std::vector<std::pair<int, int>>& need) {
-    MapCovis* c = m->covis;
+    std::vector<RowNeed> rows;
+    for (const auto& x : need) rows.push_back({x.first, x.second, -1});
+    const RowPlan plan = m->cov.plan(rows);
+    if (plan.moves.empty()) return ORBFE_OK;
     std::vector<CovMoveItem> items;
-    long long used = c->used;
-    for (const auto& x : need) {
-        if (x.second <= c->h_cap[x.first]) continue;
-        int cap = 8;
-        while (cap < x.second) cap <<= 1;
-        items.push_back({used, x.first, cap});
-        used += 4ll * cap;
-    }
-    if (items.empty()) return ORBFE_OK;
+    for (const RowMove& v : plan.moves) items.push_back({v.new_off, v.row, v.new_cap});
     int st;
-    if (used > c->pool_alloc) {
-        long long n = std::max<long long>(2 * c->pool_alloc, 1 << 16);
-        while (n < used) n *= 2;
-        if ((st = map_regrow(m, c->pool, sizeof(int), (size_t)c->used, (size_t)n))) return st;
-        c->pool_alloc = n;
-    }
-    if ((st = c->items.ensure(sizeof(CovMoveItem) * items.size()))) return st;
-    ORBFE_HIP(hipMemcpyAsync(c->items.p, items.data(), sizeof(CovMoveItem) * items.size(),
-                             hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(cov_move_kernel, dim3((unsigned)items.size()), dim3(256), 0, m->stream,
-                       c->items.as<CovMoveItem>(), c->pool.as<int>(), c->off.as<long long>(),
-                       c->cap.as<int>(), c->nw.as<int>(), c->no.as<int>());
+    if ((st = store_grow_pool(m, m->cov_pool, sizeof(int), m->cov.used, plan.alloc, kFillZero))) return st;
+    m->cov.commit(plan);
+    CovMoveItem* d_items;
+    if ((st = store_borrow(m, kStageItems, items.size(), d_items))) return st;
+    ORBFE_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(CovMoveItem) * items.size(), hipMemcpyHostToDevice,
+                             m->stream));
+    hipLaunchKernelGGL(cov_move_kernel, dim3((unsigned)items.size()), dim3(256), 0, m->stream, d_items, cov_dev(m));
     ORBFE_HIP(hipGetLastError());
     ORBFE_HIP(hipStreamSynchronize(m->stream));
-    for (const CovMoveItem& it : items) {
-        c->h_off[it.j] = it.new_off;
-        c->h_cap[it.j] = it.new_cap;
-    }
-    c->used = used;
     return ORBFE_OK;
 }
 
-CovMergeArgs cov_args(orbfe_map* m, int op, int single) {
-    MapCovis* c = m->covis;
+CovMergeArgs cov_args(int op, int single) {
     CovMergeArgs a{};
-    a.d = m->dev();
     a.op = op;
     a.single = single;
     a.slot = single;
-    a.pool = c->pool.as<int>();
-    a.off = c->off.as<long long>();
-    a.cap = c->cap.as<int>();
-    a.nw = c->nw.as<int>();
-    a.no = c->no.as<int>();
-    a.first = c->first.as<uint8_t>();
-    a.res = c->res.as<int>();
-    a.parent_out = c->pout.as<int>();
-    a.kf_neigh = m->kf_neigh.as<int>();
-    a.kf_parent = m->kf_parent.as<int>();
-    a.err = c->err.as<int>();
     return a;
 }
 
 // Decides (sizes and the capacity check, nothing written), grows the rows that need it, applies.
-// single >= 0: one workgroup for that keyframe; else one per keyframe of the map.
+// single >= 0: one workgroup for that keyframe; else one per keyframe of the map.  The views are
+// taken ahead of each launch: the rows' growth between the two may move the graph's pool.
 int cov_run(orbfe_map* m, CovMergeArgs a) {
-    MapCovis* c = m->covis;
     const int grid = a.single >= 0 ? 1 : m->n_kf;
     if (grid <= 0) return ORBFE_OK;
     const int first = a.single >= 0 ? a.single : 0;
     std::vector<int> res(3 * (size_t)grid);
-    int err = 0;
-    ORBFE_HIP(hipMemsetAsync(c->err.p, 0, sizeof(int), m->stream));
+    int st, err = 0;
+    if ((st = store_clear_err(m))) return st;
     a.apply = 0;
+    a.d = m->dev();
+    a.g = cov_dev(m);
+    a.parent_out = m->pout.as<int>();
     hipLaunchKernelGGL(cov_merge_kernel, dim3(grid), dim3(kCovBlock), 0, m->stream, a);
     ORBFE_HIP(hipGetLastError());
-    ORBFE_HIP(hipMemcpyAsync(res.data(), c->res.as<int>() + 3 * (size_t)first, sizeof(int) * res.size(),
+    ORBFE_HIP(hipMemcpyAsync(res.data(), a.g.res + 3 * (size_t)first, sizeof(int) * res.size(),
                              hipMemcpyDeviceToHost, m->stream));
-    ORBFE_HIP(hipMemcpyAsync(&err, c->err.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    ORBFE_HIP(hipStreamSynchronize(m->stream));
+    if ((st = store_read_err(m, err))) return st;
     if (err & kCovErrCapacity) return ORBFE_ERR_CAPACITY;
     if (err) return ORBFE_ERR_HIP;
     std::vector<std::pair<int, int>> need;
     for (int g = 0; g < grid; ++g)
         if (res[3 * g + 2]) need.push_back({first + g, std::max(res[3 * g], res[3 * g + 1])});
     if (need.empty()) return ORBFE_OK;
-    int st;
     if ((st = cov_reserve(m, need))) return st;
     a.apply = 1;
-    a.pool = c->pool.as<int>();  // the pool may have moved
+    a.d = m->dev();
+    a.g = cov_dev(m);
     hipLaunchKernelGGL(cov_merge_kernel, dim3(grid), dim3(kCovBlock), 0, m->stream, a);
     ORBFE_HIP(hipGetLastError());
-    ORBFE_HIP(hipMemcpyAsync(&err, c->err.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    ORBFE_HIP(hipStreamSynchronize(m->stream));
+    if ((st = store_read_err(m, err))) return st;
     if (err) return ORBFE_ERR_HIP;
     for (int g = 0; g < grid; ++g)
         if (res[3 * g + 2]) {
-            c->h_nw[first + g] = res[3 * g];
-            c->h_no[first + g] = res[3 * g + 1];
+            m->h_nw[first + g] = res[3 * g];
+            m->h_no[first + g] = res[3 * g + 1];
         }
     return ORBFE_OK;
 }
 
 // n slots then n weights staged on the device.
-int cov_stage(orbfe_map* m, int n, const int32_t* slots, const int32_t* weights) {
-    MapCovis* c = m->covis;
+int cov_stage(orbfe_map* m, int n, const int32_t* slots, const int32_t* weights, int*& staged) {
     int st;
-    if ((st = c->stage.ensure(2 * sizeof(int) * std::max<size_t>((size_t)n, 1)))) return st;
+    if ((st = store_borrow(m, kStageVals, 2 * (size_t)n, staged))) return st;
     if (n) {
-        ORBFE_HIP(hipMemcpyAsync(c->stage.p, slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, m->stream));
-        ORBFE_HIP(hipMemcpyAsync(c->stage.as<int>() + n, weights, sizeof(int) * (size_t)n,
-                                 hipMemcpyHostToDevice, m->stream));
+        ORBFE_HIP(hipMemcpyAsync(staged, slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+        ORBFE_HIP(hipMemcpyAsync(staged + n, weights, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, m->stream));
     }
     return ORBFE_OK;
 }
@@ -749,10 +659,11 @@ int cov_add_children(orbfe_map* m, int n, const int32_t* kf_slots, const int* pa
         if (parents[i] >= 0) pc.push_back({parents[i], kf_slots[i]});
     if (pc.empty()) return ORBFE_OK;
     std::sort(pc.begin(), pc.end());
-    MapRagged& r = m->kf_ch;
+    const RowTable& r = m->kf_ch;
     std::vector<int> pool((size_t)r.used);
     if (r.used) {
-        ORBFE_HIP(hipMemcpyAsync(pool.data(), r.pool.p, sizeof(int) * (size_t)r.used, hipMemcpyDeviceToHost, m->stream));
+        ORBFE_HIP(hipMemcpyAsync(pool.data(), m->kf_ch_pool.buf.p, sizeof(int) * (size_t)r.used,
+                                 hipMemcpyDeviceToHost, m->stream));
         ORBFE_HIP(hipStreamSynchronize(m->stream));
     }
     std::vector<std::vector<int>> rows;
@@ -760,7 +671,7 @@ int cov_add_children(orbfe_map* m, int n, const int32_t* kf_slots, const int* pa
     for (size_t b = 0; b < pc.size();) {
         const int p = pc[b].first;
         std::vector<int> ch;
-        if ((size_t)p < r.h_n.size()) ch.assign(pool.begin() + r.h_off[p], pool.begin() + r.h_off[p] + r.h_n[p]);
+        if (r.length(p)) ch.assign(pool.begin() + r.off[p], pool.begin() + r.off[p] + r.len[p]);
         for (; b < pc.size() && pc[b].first == p; ++b) ch.push_back(pc[b].second);
         std::sort(ch.begin(), ch.end(), [&](int x, int y) { return m->h_key[x] < m->h_key[y]; });
         ch.erase(std::unique(ch.begin(), ch.end()), ch.end());
@@ -769,8 +680,8 @@ int cov_add_children(orbfe_map* m, int n, const int32_t* kf_slots, const int* pa
     }
     std::vector<MapRowWrite> w;
     for (size_t k = 0; k < rows.size(); ++k)
-        w.push_back({who[k], 0, (int)rows[k].size(), (int)rows[k].size(), rows[k].data()});
-    return map_put_rows(m, m->kf_ch, w);
+        w.push_back({who[k], 0, (int)rows[k].size(), (int)rows[k].size(), rows[k].data(), nullptr});
+    return map_put_kf_ch(m, w);
 }
 
 int cov_get_row(orbfe_map* m, int slot, bool ordered, int32_t* kf_slots, int32_t* weights, int cap, int32_t* n) {
@@ -779,14 +690,14 @@ int cov_get_row(orbfe_map* m, int slot, bool ordered, int32_t* kf_slots, int32_t
     return map_guarded(m, [&]() {
         int st;
         if ((st = cov_ready(m))) return st;
-        MapCovis* c = m->covis;
-        *n = ordered ? c->h_no[slot] : c->h_nw[slot];
+        const RowTable& r = m->cov;
+        *n = ordered ? m->h_no[slot] : m->h_nw[slot];
         if (*n > cap) return (int)ORBFE_ERR_CAPACITY;
         if (!*n) return (int)ORBFE_OK;
-        const int* row = c->pool.as<int>() + c->h_off[slot] + (ordered ? 2ll * c->h_cap[slot] : 0ll);
+        const int* row = m->cov_pool.buf.as<int>() + r.off[slot] + (ordered ? 2ll * r.cap[slot] : 0ll);
         ORBFE_HIP(hipMemcpyAsync(kf_slots, row, sizeof(int) * (size_t)*n, hipMemcpyDeviceToHost, m->stream));
         if (weights)
-            ORBFE_HIP(hipMemcpyAsync(weights, row + c->h_cap[slot], sizeof(int) * (size_t)*n,
+            ORBFE_HIP(hipMemcpyAsync(weights, row + r.cap[slot], sizeof(int) * (size_t)*n,
                                      hipMemcpyDeviceToHost, m->stream));
         ORBFE_HIP(hipStreamSynchronize(m->stream));
         return (int)ORBFE_OK;
@@ -798,7 +709,7 @@ int cov_single(orbfe_map* m, int op, int slot, int other, int weight) {
     return map_guarded(m, [&]() {
         int st;
         if ((st = cov_ready(m))) return st;
-        CovMergeArgs a = cov_args(m, op, op == kCovOpEraseKf ? -1 : slot);
+        CovMergeArgs a = cov_args(op, op == kCovOpEraseKf ? -1 : slot);
         a.slot = slot;
         a.other = other;
         a.weight = weight;
@@ -823,29 +734,28 @@ int orbfe_map_update_connections(orbfe_map* m, int n, const int32_t* kf_slots, c
     return map_guarded(m, [&]() {
         int st;
         if ((st = cov_ready(m))) return st;
-        MapCovis* c = m->covis;
         const size_t ni = sizeof(int) * (size_t)n;
-        if ((st = c->batch.ensure(ni))) return st;
-        if ((st = c->c_n.ensure(ni))) return st;
-        if ((st = c->c_off.ensure(8 * (size_t)n))) return st;
-        if ((st = c->pout.ensure(ni))) return st;
-        if ((st = c->allow.ensure((size_t)n))) return st;
-        ORBFE_HIP(hipMemcpyAsync(c->batch.p, kf_slots, ni, hipMemcpyHostToDevice, m->stream));
-        if (allow_parent) ORBFE_HIP(hipMemcpyAsync(c->allow.p, allow_parent, (size_t)n, hipMemcpyHostToDevice, m->stream));
-        ORBFE_HIP(hipMemsetAsync(c->pos.p, 0xff, sizeof(int) * (size_t)m->n_kf, m->stream));
-        ORBFE_HIP(hipMemsetAsync(c->pout.p, 0xff, ni, m->stream));
+        if ((st = m->batch.ensure(ni))) return st;
+        if ((st = m->c_n.ensure(ni))) return st;
+        if ((st = m->c_off.ensure(8 * (size_t)n))) return st;
+        if ((st = m->pout.ensure(ni))) return st;
+        if ((st = m->allow.ensure((size_t)n))) return st;
+        ORBFE_HIP(hipMemcpyAsync(m->batch.p, kf_slots, ni, hipMemcpyHostToDevice, m->stream));
+        if (allow_parent) ORBFE_HIP(hipMemcpyAsync(m->allow.p, allow_parent, (size_t)n, hipMemcpyHostToDevice, m->stream));
+        ORBFE_HIP(hipMemsetAsync(m->at<int>(kColCovPos), 0xff, sizeof(int) * (size_t)m->n_kf, m->stream));
+        ORBFE_HIP(hipMemsetAsync(m->pout.p, 0xff, ni, m->stream));
         hipLaunchKernelGGL(cov_pos_kernel, dim3((n + 255) / 256), dim3(256), 0, m->stream, n,
-                           c->batch.as<int>(), c->pos.as<int>());
+                           m->batch.as<int>(), m->at<int>(kColCovPos));
         // the counters: their sizes, then rows of exactly those sizes
         CovCountArgs k{};
         k.d = m->dev();
         k.n = n;
-        k.batch = c->batch.as<int>();
-        k.c_n = c->c_n.as<int>();
+        k.batch = m->batch.as<int>();
+        k.c_n = m->c_n.as<int>();
         hipLaunchKernelGGL(cov_count_kernel, dim3(n), dim3(kCovBlock), 0, m->stream, k);
         ORBFE_HIP(hipGetLastError());
         std::vector<int> cn((size_t)n);
-        ORBFE_HIP(hipMemcpyAsync(cn.data(), c->c_n.p, ni, hipMemcpyDeviceToHost, m->stream));
+        ORBFE_HIP(hipMemcpyAsync(cn.data(), m->c_n.p, ni, hipMemcpyDeviceToHost, m->stream));
         ORBFE_HIP(hipStreamSynchronize(m->stream));
         std::vector<long long> coff((size_t)n);
         long long total = 0;
@@ -854,32 +764,31 @@ int orbfe_map_update_connections(orbfe_map* m, int n, const int32_t* kf_slots, c
             coff[i] = total;
             total += cn[i];
         }
-        if ((st = c->c_slot.ensure(sizeof(int) * (size_t)std::max<long long>(total, 1)))) return st;
-        if ((st = c->c_w.ensure(sizeof(int) * (size_t)std::max<long long>(total, 1)))) return st;
-        ORBFE_HIP(hipMemcpyAsync(c->c_off.p, coff.data(), 8 * (size_t)n, hipMemcpyHostToDevice, m->stream));
+        if ((st = m->c_slot.ensure(sizeof(int) * (size_t)std::max<long long>(total, 1)))) return st;
+        if ((st = m->c_w.ensure(sizeof(int) * (size_t)std::max<long long>(total, 1)))) return st;
+        ORBFE_HIP(hipMemcpyAsync(m->c_off.p, coff.data(), 8 * (size_t)n, hipMemcpyHostToDevice, m->stream));
         k.fill = 1;
-        k.c_off = c->c_off.as<long long>();
-        k.c_slot = c->c_slot.as<int>();
-        k.c_w = c->c_w.as<int>();
+        k.c_off = m->c_off.as<long long>();
+        k.c_slot = m->c_slot.as<int>();
+        k.c_w = m->c_w.as<int>();
         hipLaunchKernelGGL(cov_count_kernel, dim3(n), dim3(kCovBlock), 0, m->stream, k);
         ORBFE_HIP(hipGetLastError());
-        CovMergeArgs a = cov_args(m, kCovOpBatch, -1);
+        CovMergeArgs a = cov_args(kCovOpBatch, -1);
         a.n = n;
         a.batch = k.batch;
-        a.pos = c->pos.as<int>();
-        a.allow = allow_parent ? c->allow.as<uint8_t>() : nullptr;
+        a.allow = allow_parent ? m->allow.as<uint8_t>() : nullptr;
         a.c_n = k.c_n;
         a.c_off = k.c_off;
         a.c_slot = k.c_slot;
         a.c_w = k.c_w;
         if ((st = cov_run(m, a))) return st;
         std::vector<int> par((size_t)n);
-        ORBFE_HIP(hipMemcpyAsync(par.data(), c->pout.p, ni, hipMemcpyDeviceToHost, m->stream));
+        ORBFE_HIP(hipMemcpyAsync(par.data(), m->pout.p, ni, hipMemcpyDeviceToHost, m->stream));
         ORBFE_HIP(hipStreamSynchronize(m->stream));
         if ((st = cov_add_children(m, n, kf_slots, par.data()))) return st;
         for (int i = 0; i < n; ++i) {
             if (parent_out) parent_out[i] = par[i];
-            if (n_ordered_out) n_ordered_out[i] = c->h_no[kf_slots[i]];
+            if (n_ordered_out) n_ordered_out[i] = m->h_no[kf_slots[i]];
         }
         return (int)ORBFE_OK;
     });
@@ -923,10 +832,11 @@ int orbfe_map_set_connections(orbfe_map* m, int slot, int n, const int32_t* kf_s
     return map_guarded(m, [&]() {
         int st;
         if ((st = cov_ready(m))) return st;
-        if ((st = cov_stage(m, n, kf_slots, weights))) return st;
-        CovMergeArgs a = cov_args(m, kCovOpSetWeights, slot);
+        CovMergeArgs a = cov_args(kCovOpSetWeights, slot);
+        int* staged;
+        if ((st = cov_stage(m, n, kf_slots, weights, staged))) return st;
         a.n_staged = n;
-        a.staged = m->covis->stage.as<int>();
+        a.staged = staged;
         return cov_run(m, a);
     });
 }
@@ -937,15 +847,14 @@ int orbfe_map_set_ordered_connections(orbfe_map* m, int slot, int n, const int32
     return map_guarded(m, [&]() {
         int st;
         if ((st = cov_ready(m))) return st;
-        MapCovis* c = m->covis;
-        if ((st = cov_stage(m, n, kf_slots, weights))) return st;
+        int* staged;
+        if ((st = cov_stage(m, n, kf_slots, weights, staged))) return st;
         if ((st = cov_reserve(m, {{slot, n}}))) return st;
-        hipLaunchKernelGGL(cov_set_ordered_kernel, dim3(1), dim3(256), 0, m->stream, slot, n,
-                           c->stage.as<int>(), c->pool.as<int>(), c->off.as<long long>(), c->cap.as<int>(),
-                           c->no.as<int>(), m->kf_neigh.as<int>());
+        hipLaunchKernelGGL(cov_set_ordered_kernel, dim3(1), dim3(256), 0, m->stream, slot, n, staged, cov_dev(m),
+                           m->at<int>(kColKfNeigh));
         ORBFE_HIP(hipGetLastError());
         ORBFE_HIP(hipStreamSynchronize(m->stream));
-        c->h_no[slot] = n;
+        m->h_no[slot] = n;
         return (int)ORBFE_OK;
     });
 }
@@ -956,7 +865,7 @@ int orbfe_map_set_first_connection(orbfe_map* m, int slot, int flag) {
         int st;
         if ((st = cov_ready(m))) return st;
         const int32_t s = slot;
-        return map_set<uint8_t>(m, 1, &s, nullptr, flag ? 1 : 0, m->covis->first.as<uint8_t>());
+        return store_set<uint8_t>(m, m->at<uint8_t>(kColCovFirst), 1, &s, nullptr, flag ? 1 : 0);
     });
 }
 
@@ -975,16 +884,16 @@ int orbfe_map_get_spanning_tree(orbfe_map* m, int slot, int32_t* parent, int32_t
     return map_guarded(m, [&]() {
         int st;
         if ((st = cov_ready(m))) return st;
-        const MapRagged& r = m->kf_ch;
-        *n_children = (size_t)slot < r.h_n.size() ? r.h_n[slot] : 0;
+        const RowTable& r = m->kf_ch;
+        *n_children = r.length(slot);
         if (*n_children > cap) return (int)ORBFE_ERR_CAPACITY;
         int p = -1;
         uint8_t f = 0;
-        ORBFE_HIP(hipMemcpyAsync(&p, m->kf_parent.as<int>() + slot, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        ORBFE_HIP(hipMemcpyAsync(&f, m->covis->first.as<uint8_t>() + slot, 1, hipMemcpyDeviceToHost, m->stream));
+        ORBFE_HIP(hipMemcpyAsync(&p, m->at<int>(kColKfParent) + slot, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        ORBFE_HIP(hipMemcpyAsync(&f, m->at<uint8_t>(kColCovFirst) + slot, 1, hipMemcpyDeviceToHost, m->stream));
         if (*n_children)
-            ORBFE_HIP(hipMemcpyAsync(child_slots, r.pool.as<int>() + r.h_off[slot], sizeof(int) * (size_t)*n_children,
-                                     hipMemcpyDeviceToHost, m->stream));
+            ORBFE_HIP(hipMemcpyAsync(child_slots, m->kf_ch_pool.buf.as<int>() + r.off[slot],
+                                     sizeof(int) * (size_t)*n_children, hipMemcpyDeviceToHost, m->stream));
         ORBFE_HIP(hipStreamSynchronize(m->stream));
         if (parent) *parent = p;
         if (first_connection) *first_connection = f;

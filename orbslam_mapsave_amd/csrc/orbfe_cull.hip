@@ -16,12 +16,14 @@
 //                        tournament (:1201-1274) over the children's lists and weight rows, mbBad
 //   cull_decide_kernel   one workgroup per listed keyframe: nMPs and nRedundantObservations of
 //                        KeyFrameCulling, waves over the slots, lanes over a point's observers
-//   cull_add_kernel / cull_add_masked_kernel / cull_fill_kernel   the counters' mutators
+//   cull_add_masked_kernel   the counters' device-side mutator
 //
 // Per point: nObs (state: SetBadFlag clears the observations and leaves it), mnFound, mnVisible,
-// mnFirstKFid.  Per observation: the feature index, in a second ragged pool (orbfe_map::mp_idx)
-// row for row beside the keyframe slots, so that the rows map_vote_kernel and cov_count_kernel
-// read keep their layout.  Per keyframe keypoint: octave and `mvuRight >= 0` in one byte, mvDepth.
+// mnFirstKFid.  Per observation: the feature index, in a side pool of the observation rows
+// (orbfe_map::mp_idx_pool: same offsets, same lengths), so that the rows map_vote_kernel and
+// cov_count_kernel read keep their layout.  Per keyframe keypoint: octave and `mvuRight >= 0` in
+// one byte, mvDepth, in side pools of kf_mp.  The columns, pools and their views (CullDev) are
+// the store's (orbfe_map_store.hip); cull_ready() there makes them cover the map.
 // The host keeps the observation rows with their indices and the right flags, so every nObs
 // amount and every "index unknown" refusal is decided before a kernel writes.  Everything is
 // integer but the found ratio, one IEEE float division and one comparison.
@@ -36,43 +38,7 @@
 namespace orbfe {
 
 constexpr int kCullBlock = 1024;
-constexpr int kCullNoPos = 0x7f7f7f7f;   // mark of a point no list position has claimed
-constexpr int kCullRight = 0x80;         // the feature byte: octave | kCullRight
-// pinned result words beside kResDone
-enum { kCullResKept = 5, kCullResCulled, kCullResStatus, kCullResValue };
-static_assert(kCullResKept > kResDone && kCullResValue < kResList, "free words of the pinned block");
-
-struct CullDev {
-    int n_kf, n_mp;
-    const long long* kf_mp_off;
-    const int* kf_mp_n;
-    int* kf_mp;
-    uint8_t* mp_bad;
-    const long long* obs_off;
-    int* obs_n;
-    const int* obs;
-    const long long* idx_off;
-    int* idx_n;
-    const int* idx;
-    int* nobs;
-    int* found;
-    int* visible;
-    const long long* first;
-    int* mark;  // all kCullNoPos between calls
-};
-
-template <class T>
-__global__ __launch_bounds__(256) void cull_fill_kernel(long long n, T* dst, T v) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = v;
-}
-
-// dst[slots[i]] += amounts ? amounts[i] : amount; a repeated slot adds up.
-__global__ __launch_bounds__(256) void cull_add_kernel(int n, const int* slots, const int* amounts,
-                                                       int amount, int* dst) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) atomicAdd(&dst[slots[i]], amounts ? amounts[i] : amount);
-}
+constexpr int kCullNoPos = kMapNoPos;    // mark of a point no list position has claimed
 
 // The device form: entries of -1 and entries whose mask byte is 0 are skipped.  Run twice:
 // checking (an entry outside [-1, n_mp) raises *err, nothing written) and adding (nothing if *err).
@@ -90,7 +56,8 @@ __global__ __launch_bounds__(256) void cull_add_masked_kernel(int n, const int* 
 }
 
 struct CullPointsArgs {
-    CullDev d;
+    MapDev d;
+    CullDev c;
     int n, th_obs;
     int cur;            // nCurrentKFid, in [0, 2^31)
     const int* list;    // [n] point slots, all in range
@@ -103,11 +70,12 @@ struct CullPointsArgs {
 __global__ __launch_bounds__(kCullBlock) void cull_points_kernel(CullPointsArgs a) {
     __shared__ int tmp[kCullBlock / 64 + 1];
     __shared__ int s_err;
-    const CullDev& d = a.d;
+    const MapDev& d = a.d;
+    const CullDev& cu = a.c;
     const int tid = threadIdx.x;
     if (tid == 0) s_err = 0;
     // a point listed twice: the second occurrence sees what the first one did
-    for (int i = tid; i < a.n; i += kCullBlock) atomicMin(&d.mark[a.list[i]], i);
+    for (int i = tid; i < a.n; i += kCullBlock) atomicMin(&cu.mark[a.list[i]], i);
     __threadfence();
     __syncthreads();
     int n_kept = 0, n_culled = 0;
@@ -117,14 +85,14 @@ __global__ __launch_bounds__(kCullBlock) void cull_points_kernel(CullPointsArgs 
         bool keep = false, bad = false;
         if (i < a.n) {
             mp = a.list[i];
-            const bool first = __hip_atomic_load(&d.mark[mp], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == i;
+            const bool first = __hip_atomic_load(&cu.mark[mp], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == i;
             if (!d.mp_bad[mp]) {                                                   // :186
-                const float ratio = (float)d.found[mp] / (float)d.visible[mp];     // MapPoint.cc GetFoundRatio
-                const long long f = d.first[mp];
+                const float ratio = (float)cu.found[mp] / (float)cu.visible[mp];     // MapPoint.cc GetFoundRatio
+                const long long f = cu.first_kf[mp];
                 if (f < 0 || f > 0x7fffffffll) s_err = 1;
                 const int diff = a.cur - (int)f;
                 if (ratio < 0.25f) bad = true;                                     // :190
-                else if (diff >= 2 && d.nobs[mp] <= a.th_obs) bad = true;          // :195
+                else if (diff >= 2 && cu.nobs[mp] <= a.th_obs) bad = true;          // :195
                 else if (diff >= 3) keep = false;                                  // :200
                 else keep = true;
                 if (bad && !first) bad = false;  // made bad at its first position: dropped here (:186)
@@ -139,40 +107,39 @@ __global__ __launch_bounds__(kCullBlock) void cull_points_kernel(CullPointsArgs 
         n_culled += total;
     }
     __syncthreads();
-    for (int i = tid; i < a.n; i += kCullBlock) d.mark[a.list[i]] = kCullNoPos;
+    for (int i = tid; i < a.n; i += kCullBlock) cu.mark[a.list[i]] = kCullNoPos;
     __threadfence_system();
     __syncthreads();
     if (tid == 0) {
-        a.res[kCullResKept] = n_kept;
-        a.res[kCullResCulled] = n_culled;
-        a.res[kCullResStatus] = s_err ? ORBFE_ERR_ARG : ORBFE_OK;
+        a.res[kResKept] = n_kept;
+        a.res[kResCulled] = n_culled;
+        a.res[kResCullStatus] = s_err ? ORBFE_ERR_ARG : ORBFE_OK;
         __hip_atomic_store(&a.res[kResDone], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
 // MapPoint::SetBadFlag (MapPoint.cc:392-409) of n distinct points, one wave each.  nObs stays.
-__global__ __launch_bounds__(256) void cull_setbad_kernel(CullDev d, int n, const int* slots) {
+__global__ __launch_bounds__(256) void cull_setbad_kernel(MapDev d, int n, const int* slots) {
     const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= n) return;
     const int lane = threadIdx.x & 63;
     const int mp = slots[w];
     if (mp < 0 || mp >= d.n_mp) return;
-    const long long oo = d.obs_off[mp], xo = d.idx_off[mp];
-    const int no = min(d.obs_n[mp], d.idx_n[mp]);
+    const long long oo = d.mp_obs_off[mp];
+    const int no = d.mp_obs_n[mp];
     for (int j = lane; j < no; j += 64) {
-        const int kf = d.obs[oo + j], ix = d.idx[xo + j];
+        const int kf = d.mp_obs[oo + j], ix = d.mp_idx[oo + j];
         if (kf < 0 || kf >= d.n_kf || ix < 0 || ix >= d.kf_mp_n[kf]) continue;
         d.kf_mp[d.kf_mp_off[kf] + ix] = -1;   // EraseMapPointMatch(idx), :405: whatever it held
     }
     if (lane == 0) {
         d.mp_bad[mp] = 1;                     // :398
-        d.obs_n[mp] = 0;                      // :400
-        d.idx_n[mp] = 0;
+        d.mp_obs_n[mp] = 0;                      // :400
     }
 }
 
 // KeyFrame::TrackedMapPoints (KeyFrame.cc:971-996).
-__global__ __launch_bounds__(kCullBlock) void cull_tracked_kernel(CullDev d, int kf, int min_obs, int* res) {
+__global__ __launch_bounds__(kCullBlock) void cull_tracked_kernel(MapDev d, CullDev cu, int kf, int min_obs, int* res) {
     __shared__ int tmp[kCullBlock / 64 + 1];
     const long long off = d.kf_mp_off[kf];
     const int n = d.kf_mp_n[kf];
@@ -181,12 +148,12 @@ __global__ __launch_bounds__(kCullBlock) void cull_tracked_kernel(CullDev d, int
         const int mp = d.kf_mp[off + i];
         if (mp < 0 || mp >= d.n_mp) continue;      // :980
         if (d.mp_bad[mp]) continue;                // :982
-        if (min_obs > 0 && d.nobs[mp] < min_obs) continue;  // :984-987
+        if (min_obs > 0 && cu.nobs[mp] < min_obs) continue;  // :984-987
         ++cnt;
     }
     const int total = block_sum<kCullBlock>(cnt, tmp);
     if (threadIdx.x == 0) {
-        res[kCullResValue] = total;
+        res[kResValue] = total;
         __hip_atomic_store(&res[kResDone], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
@@ -202,36 +169,21 @@ __device__ __forceinline__ int cull_ld(const int* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-struct CullKfDev {
-    const uint8_t* feat;      // octave | kCullRight, at the offsets of kf_mp's pool
-    const float* depth;
-    const float* th_depth;    // [n_kf]
-    uint8_t* kf_bad;
-    int* kf_parent;
-    const unsigned long long* kf_key;
-    // the covisibility graph (orbfe_covis.hip): row j is 4 arrays of cap[j] ints at pool + off[j]
-    const int* cpool;
-    const long long* coff;
-    const int* ccap;
-    const int* cnw;
-    const int* cno;
-};
-
 // EraseObservation(this) of every entry of the keyframe's mvpMapPoints (:1191-1193), one wave per
 // slot, in three launches: marking (a point held at two indices is erased at the lower one, the
 // other finds nothing), checking (what each erase will do; a point that will go bad with an
 // observer whose index is unknown raises *err; nothing written but flag[]) and applying (nothing
 // if *err).  The writes of different waves are disjoint, or the same -1.
 struct CullKfObsArgs {
-    CullDev d;
-    CullKfDev k;
+    MapDev d;
+    CullDev c;
     int kf, mode;
     int* flag;  // [slots] 0: nothing, 1: the observation erased, 2: and the point set bad
-    int* err;
 };
 
 __global__ __launch_bounds__(kCullBlock) void cull_kf_obs_kernel(CullKfObsArgs a) {
-    const CullDev& d = a.d;
+    const MapDev& d = a.d;
+    const CullDev& cu = a.c;
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * kCullWaves + (threadIdx.x >> 6);
     const int n = d.kf_mp_n[a.kf];
@@ -240,42 +192,42 @@ __global__ __launch_bounds__(kCullBlock) void cull_kf_obs_kernel(CullKfObsArgs a
     const int mp = d.kf_mp[koff + i];
     const bool held = mp >= 0 && mp < d.n_mp;
     if (a.mode == kCullMark) {
-        if (held && lane == 0) atomicMin(&d.mark[mp], i);
+        if (held && lane == 0) atomicMin(&cu.mark[mp], i);
         return;
     }
     int fl = 0;
     if (a.mode == kCullApply) {
-        if (*a.err) return;
+        if (d.ctl[kCtlCallErr]) return;
         fl = a.flag[i];
         if (!fl) return;
-    } else if (!held || cull_ld(&d.mark[mp]) != i) {
+    } else if (!held || cull_ld(&cu.mark[mp]) != i) {
         if (lane == 0) a.flag[i] = 0;
         return;
     }
-    const long long oo = d.obs_off[mp], xo = d.idx_off[mp];
-    const int no = min(d.obs_n[mp], d.idx_n[mp]);
+    const long long oo = d.mp_obs_off[mp];
+    const int no = d.mp_obs_n[mp];
     int p = -1;  // where this keyframe stands in the row
     for (int c = 0; c < no && p < 0; c += 64) {
         const int j = c + lane;
-        const unsigned long long b = __ballot(j < no && d.obs[oo + j] == a.kf);
+        const unsigned long long b = __ballot(j < no && d.mp_obs[oo + j] == a.kf);
         if (b) p = c + __ffsll((long long)b) - 1;
     }
     if (p < 0) {  // a point that does not list this keyframe is untouched (MapPoint.cc:357)
         if (a.mode == kCullCheck && lane == 0) a.flag[i] = 0;
         return;
     }
-    const int ix = d.idx[xo + p];
-    const int by = ix >= 0 && ix < n && (a.k.feat[koff + ix] & kCullRight) ? 2 : 1;  // MapPoint.cc:360-363
+    const int ix = d.mp_idx[oo + p];
+    const int by = ix >= 0 && ix < n && (cu.feat[koff + ix] & kCullRight) ? 2 : 1;  // MapPoint.cc:360-363
     if (a.mode == kCullCheck) {
-        const bool bad = d.nobs[mp] - by <= 2;  // :371
+        const bool bad = cu.nobs[mp] - by <= 2;  // :371
         if (bad) {
             bool unknown = false;
             for (int j = lane; j < no; j += 64) {
                 if (j == p) continue;
-                const int kfj = d.obs[oo + j], x = d.idx[xo + j];
+                const int kfj = d.mp_obs[oo + j], x = d.mp_idx[oo + j];
                 if (kfj < 0 || kfj >= d.n_kf || x < 0 || x >= d.kf_mp_n[kfj]) unknown = true;
             }
-            if (__ballot(unknown) && lane == 0) atomicOr(a.err, 1);
+            if (__ballot(unknown) && lane == 0) atomicOr(&d.ctl[kCtlCallErr], 1);
         }
         if (lane == 0) a.flag[i] = bad ? 2 : 1;
         return;
@@ -283,21 +235,20 @@ __global__ __launch_bounds__(kCullBlock) void cull_kf_obs_kernel(CullKfObsArgs a
     if (fl == 2) {  // MapPoint::SetBadFlag of what is left (:392-409)
         for (int j = lane; j < no; j += 64) {
             if (j == p) continue;
-            const int kfj = d.obs[oo + j], x = d.idx[xo + j];
+            const int kfj = d.mp_obs[oo + j], x = d.mp_idx[oo + j];
             if (kfj < 0 || kfj >= d.n_kf || x < 0 || x >= d.kf_mp_n[kfj]) continue;
             d.kf_mp[d.kf_mp_off[kfj] + x] = -1;
         }
         if (lane == 0) {
             d.mp_bad[mp] = 1;
-            d.obs_n[mp] = 0;
-            d.idx_n[mp] = 0;
-            d.nobs[mp] -= by;
+            d.mp_obs_n[mp] = 0;
+            cu.nobs[mp] -= by;
         }
         return;
     }
     // the row closes over position p: every lane loads before any lane stores
-    int* const row = const_cast<int*>(d.obs) + oo;
-    int* const xrow = const_cast<int*>(d.idx) + xo;
+    int* const row = d.mp_obs + oo;
+    int* const xrow = d.mp_idx + oo;
     for (int c = p; c < no - 1; c += 64) {
         const int j = c + lane;
         const bool in = j < no - 1;
@@ -310,17 +261,16 @@ __global__ __launch_bounds__(kCullBlock) void cull_kf_obs_kernel(CullKfObsArgs a
         __builtin_amdgcn_wave_barrier();
     }
     if (lane == 0) {
-        d.obs_n[mp] = no - 1;
-        d.idx_n[mp] = no - 1;
-        d.nobs[mp] -= by;
+        d.mp_obs_n[mp] = no - 1;
+        cu.nobs[mp] -= by;
     }
 }
 
-__global__ __launch_bounds__(256) void cull_kf_unmark_kernel(CullDev d, int kf) {
+__global__ __launch_bounds__(256) void cull_kf_unmark_kernel(MapDev d, CullDev cu, int kf) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= d.kf_mp_n[kf]) return;
     const int mp = d.kf_mp[d.kf_mp_off[kf] + i];
-    if (mp >= 0 && mp < d.n_mp) d.mark[mp] = kCullNoPos;
+    if (mp >= 0 && mp < d.n_mp) cu.mark[mp] = kCullNoPos;
 }
 
 // The rest of SetBadFlag in one workgroup: what the erases did, as ordered lists; the spanning-tree
@@ -328,21 +278,22 @@ __global__ __launch_bounds__(256) void cull_kf_unmark_kernel(CullDev d, int kf) 
 // part left them; the leftover children (:1268-1274); mbBad (:1281).  The children rows
 // themselves (AddChild / EraseChild) are the host's: out[] tells it the pairs.
 struct CullKfFinishArgs {
-    CullDev d;
-    CullKfDev k;
+    MapDev d;
+    CovDev g;
+    CullDev c;
     int kf, nc;
     const int* flag;
     const int* ch;      // the keyframe's children in key order
-    int* cand;          // [n_kf] all 0 between calls; 1: parent candidate, 2: a child that has left
-    int* out;           // device-mapped pinned: kCullOut*, erased[slots], bad[slots], pairs[2 nc]
+                        // cu.cand: 1: parent candidate, 2: a child that has left
+    int* out;           // the pinned block's tail: kCullOut*, erased[slots], bad[slots], pairs[2 nc]
     int* res;
 };
 
 __global__ __launch_bounds__(kCullBlock) void cull_kf_finish_kernel(CullKfFinishArgs a) {
     __shared__ int tmp[kCullBlock / 64 + 1];
     __shared__ unsigned long long s_best;
-    const CullDev& d = a.d;
-    const CullKfDev& k = a.k;
+    const MapDev& d = a.d;
+    const CullDev& cu = a.c;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = d.kf_mp_n[a.kf];
     const long long koff = d.kf_mp_off[a.kf];
@@ -363,9 +314,9 @@ __global__ __launch_bounds__(kCullBlock) void cull_kf_finish_kernel(CullKfFinish
         n_bad += total;
     }
     // ---- the tournament
-    const int parent = k.kf_parent[a.kf];
+    const int parent = d.kf_parent[a.kf];
     const bool has_parent = parent >= 0 && parent < d.n_kf;
-    if (tid == 0 && has_parent) a.cand[parent] = 1;  // :1203-1204
+    if (tid == 0 && has_parent) cu.cand[parent] = 1;  // :1203-1204
     __threadfence();
     __syncthreads();
     int np = 0;
@@ -375,14 +326,14 @@ __global__ __launch_bounds__(kCullBlock) void cull_kf_finish_kernel(CullKfFinish
         for (int ci = wave; ci < a.nc; ci += kCullWaves) {  // :1216, pointer order
             const int c = a.ch[ci];
             if (c < 0 || c >= d.n_kf) continue;
-            if ((cull_ld(&a.cand[c]) & 2) || k.kf_bad[c]) continue;  // has left (:1261); :1222
-            const int cap = k.ccap[c];
-            const int* const row = k.cpool + k.coff[c];
-            const int nw = min(k.cnw[c], cap), no = min(k.cno[c], cap);
+            if ((cull_ld(&cu.cand[c]) & 2) || d.kf_bad[c]) continue;  // has left (:1261); :1222
+            const int cap = a.g.cap[c];
+            const int* const row = a.g.pool + a.g.off[c];
+            const int nw = min(a.g.nw[c], cap), no = min(a.g.no[c], cap);
             for (int e = lane; e < no; e += 64) {  // :1230, the ordered list as it stands
                 const int o = row[2ll * cap + e];
-                if (o < 0 || o >= d.n_kf || !(cull_ld(&a.cand[o]) & 1)) continue;  // :1238
-                const int lo = cov_lower_bound_slots(row, nw, k.kf_key, k.kf_key[o]);
+                if (o < 0 || o >= d.n_kf || !(cull_ld(&cu.cand[o]) & 1)) continue;  // :1238
+                const int lo = cov_lower_bound_slots(row, nw, d.kf_key, d.kf_key[o]);
                 const int w = lo < nw && row[lo] == o ? row[cap + lo] : 0;  // GetWeight: the weight map
                 // `w > max` from -1 (:1243): the largest weight at the first (child, position)
                 atomicMax(&s_best, ((unsigned long long)(w + 1) << 40) |
@@ -396,11 +347,11 @@ __global__ __launch_bounds__(kCullBlock) void cull_kf_finish_kernel(CullKfFinish
         const int ci = 0xffffff - (int)((best >> 12) & 0xffffff), e = 4095 - (int)(best & 4095);
         if (tid == 0) {
             const int c = a.ch[ci];
-            const int pp = (k.cpool + k.coff[c])[2ll * k.ccap[c] + e];
+            const int pp = (a.g.pool + a.g.off[c])[2ll * a.g.cap[c] + e];
             pairs[2 * np] = c;  // :1259-1261
             pairs[2 * np + 1] = pp;
-            k.kf_parent[c] = pp;
-            a.cand[c] = 3;
+            d.kf_parent[c] = pp;
+            cu.cand[c] = 3;
         }
         ++np;
         __threadfence();
@@ -411,13 +362,13 @@ __global__ __launch_bounds__(kCullBlock) void cull_kf_finish_kernel(CullKfFinish
         for (int c0 = 0; c0 < a.nc; c0 += kCullBlock) {
             const int ci = c0 + tid;
             const int c = ci < a.nc ? a.ch[ci] : -1;
-            const bool left = c >= 0 && c < d.n_kf && !(cull_ld(&a.cand[c]) & 2);
+            const bool left = c >= 0 && c < d.n_kf && !(cull_ld(&cu.cand[c]) & 2);
             int total;
             const int ex = block_exclusive_scan<kCullBlock>(left, tmp, total);
             if (left) {
                 pairs[2 * (np + ex)] = c;
                 pairs[2 * (np + ex) + 1] = parent;
-                k.kf_parent[c] = parent;
+                d.kf_parent[c] = parent;
             }
             np += total;
         }
@@ -425,11 +376,11 @@ __global__ __launch_bounds__(kCullBlock) void cull_kf_finish_kernel(CullKfFinish
     __syncthreads();
     for (int ci = tid; ci < a.nc; ci += kCullBlock) {
         const int c = a.ch[ci];
-        if (c >= 0 && c < d.n_kf) a.cand[c] = 0;
+        if (c >= 0 && c < d.n_kf) cu.cand[c] = 0;
     }
     if (tid == 0) {
-        if (has_parent) a.cand[parent] = 0;
-        k.kf_bad[a.kf] = 1;  // :1281
+        if (has_parent) cu.cand[parent] = 0;
+        d.kf_bad[a.kf] = 1;  // :1281
         a.out[kCullOutErased] = n_erased;
         a.out[kCullOutBad] = n_bad;
         a.out[kCullOutRounds] = n_rounds;
@@ -444,17 +395,17 @@ __global__ __launch_bounds__(kCullBlock) void cull_kf_finish_kernel(CullKfFinish
 // One decision of KeyFrameCulling (LocalMapping.cc:643-695) per workgroup: waves stride the
 // keyframe's slots, lanes a point's observers.
 struct CullDecideArgs {
-    CullDev d;
-    CullKfDev k;
+    MapDev d;
+    CullDev c;
     int n, first_slot, mono;
     const int* list;
     int* res;   // [n] 1: nRedundantObservations > 0.9 * nMPs
-    int* err;
 };
 
 __global__ __launch_bounds__(kCullBlock) void cull_decide_kernel(CullDecideArgs a) {
     __shared__ int s_n, s_r;
-    const CullDev& d = a.d;
+    const MapDev& d = a.d;
+    const CullDev& cu = a.c;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kf = a.list[blockIdx.x];
     if (kf == a.first_slot) {  // :643
@@ -465,35 +416,35 @@ __global__ __launch_bounds__(kCullBlock) void cull_decide_kernel(CullDecideArgs 
     __syncthreads();
     const int n = d.kf_mp_n[kf];
     const long long koff = d.kf_mp_off[kf];
-    const float th = a.k.th_depth[kf];
+    const float th = cu.th_depth[kf];
     int n_mps = 0, n_red = 0;
     for (int i = wave; i < n; i += kCullWaves) {  // :653, as a vector
         const int mp = d.kf_mp[koff + i];
         if (mp < 0 || mp >= d.n_mp) continue;     // :656
         if (d.mp_bad[mp]) continue;               // :658
         if (!a.mono) {
-            const float z = a.k.depth[koff + i];
+            const float z = cu.depth[koff + i];
             if (z > th || z < 0) continue;        // :662
         }
         ++n_mps;                                  // :666
-        if (d.nobs[mp] <= 3) continue;            // :667
-        const int level = a.k.feat[koff + i] & (kCullRight - 1);
-        const long long oo = d.obs_off[mp], xo = d.idx_off[mp];
-        const int no = min(d.obs_n[mp], d.idx_n[mp]);
+        if (cu.nobs[mp] <= 3) continue;            // :667
+        const int level = cu.feat[koff + i] & (kCullRight - 1);
+        const long long oo = d.mp_obs_off[mp];
+        const int no = d.mp_obs_n[mp];
         int cnt = 0;
         bool unknown = false;
         for (int j = lane; j < no; j += 64) {     // :672: counting to a threshold, any order
-            const int kfj = d.obs[oo + j];
+            const int kfj = d.mp_obs[oo + j];
             if (kfj == kf) continue;              // :675
-            const int x = d.idx[xo + j];
+            const int x = d.mp_idx[oo + j];
             if (kfj < 0 || kfj >= d.n_kf || x < 0 || x >= d.kf_mp_n[kfj]) {
                 unknown = true;
                 continue;
             }
-            const int level_j = a.k.feat[d.kf_mp_off[kfj] + x] & (kCullRight - 1);
+            const int level_j = cu.feat[d.kf_mp_off[kfj] + x] & (kCullRight - 1);
             if (level_j <= level + 1) ++cnt;      // :679
         }
-        if (__ballot(unknown) && lane == 0) atomicOr(a.err, 1);
+        if (__ballot(unknown) && lane == 0) atomicOr(&d.ctl[kCtlCallErr], 1);
         if (wave_sum(cnt) >= 3) ++n_red;          // :686
     }
     if (lane == 0) {
@@ -508,183 +459,6 @@ __global__ __launch_bounds__(kCullBlock) void cull_decide_kernel(CullDecideArgs 
 }  // namespace orbfe
 
 namespace {
-
-struct MapCull {
-    int n_mp_known = 0, mp_alloc = 0;        // points the counters cover / hold
-    DevBuf nobs, found, visible, first, mark;
-    DevBuf feat, depth;                      // per keypoint, at the offsets of kf_mp's pool
-    long long feat_n = 0, feat_alloc = 0;    // pool entries that hold defaults or data / allocated
-    std::vector<std::vector<uint8_t>> h_feat;  // per keyframe; empty: never set
-    std::vector<float> h_th_depth;
-    int n_kf_known = 0, kf_alloc = 0;        // keyframes th_depth and cand cover / hold
-    DevBuf th_depth, cand, flag, list, res;
-    std::vector<uint8_t> h_not_erase, h_to_erase;  // mbNotErase, mbToBeErased
-    DevBuf stage_a, stage_b, stage_c, err;
-    int* pin = nullptr;                      // the lists a call reports: device-mapped pinned
-    int* pin_dev = nullptr;
-    size_t pin_n = 0;
-    ~MapCull() {
-        if (pin) hipHostFree(pin);
-    }
-};
-
-void map_cull_free(MapCull* c) { delete c; }
-
-void map_cull_reset(MapCull* c) {
-    if (!c) return;
-    c->n_mp_known = 0;
-    c->n_kf_known = 0;
-    c->h_not_erase.clear();
-    c->h_to_erase.clear();
-    c->feat_n = 0;
-    c->h_feat.clear();
-    c->h_th_depth.clear();
-}
-
-template <class T>
-int cull_fill(orbfe_map* m, T* dst, long long n, T v) {
-    if (n <= 0) return ORBFE_OK;
-    hipLaunchKernelGGL(cull_fill_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, n, dst, v);
-    ORBFE_HIP(hipGetLastError());
-    return ORBFE_OK;
-}
-
-// The counters cover every point of the map: a new one has nObs 0, mnFound = mnVisible = 1
-// (MapPoint.cc:37-38), mnFirstKFid 0; the per-keyframe host rows cover every keyframe.
-int cull_ready(orbfe_map* m) {
-    if (!m->cull) m->cull = new MapCull();
-    MapCull* c = m->cull;
-    int st;
-    if (m->n_mp > c->mp_alloc) {
-        const int n = m->mp_alloc;
-        const size_t k = (size_t)c->n_mp_known;
-        if ((st = map_regrow(m, c->nobs, sizeof(int), k, n))) return st;
-        if ((st = map_regrow(m, c->found, sizeof(int), k, n))) return st;
-        if ((st = map_regrow(m, c->visible, sizeof(int), k, n))) return st;
-        if ((st = map_regrow(m, c->first, 8, k, n))) return st;
-        if ((st = map_regrow(m, c->mark, sizeof(int), 0, n, 0x7f))) return st;  // kCullNoPos
-        c->mp_alloc = n;
-    }
-    if ((st = c->err.ensure(sizeof(int)))) return st;
-    if (m->n_mp > c->n_mp_known) {
-        const size_t o = (size_t)c->n_mp_known;
-        const long long k = m->n_mp - c->n_mp_known;
-        ORBFE_HIP(hipMemsetAsync(c->nobs.as<int>() + o, 0, sizeof(int) * (size_t)k, m->stream));
-        ORBFE_HIP(hipMemsetAsync(c->first.as<long long>() + o, 0, 8 * (size_t)k, m->stream));
-        if ((st = cull_fill<int>(m, c->found.as<int>() + o, k, 1))) return st;
-        if ((st = cull_fill<int>(m, c->visible.as<int>() + o, k, 1))) return st;
-        ORBFE_HIP(hipStreamSynchronize(m->stream));
-        c->n_mp_known = m->n_mp;
-    }
-    if (m->n_kf > c->kf_alloc) {
-        const int n = m->kf_alloc;
-        if ((st = map_regrow(m, c->th_depth, sizeof(float), (size_t)c->n_kf_known, n))) return st;
-        if ((st = map_regrow(m, c->cand, sizeof(int), 0, n))) return st;  // all 0 between calls
-        c->kf_alloc = n;
-    }
-    if (m->n_kf > c->n_kf_known) {
-        ORBFE_HIP(hipMemsetAsync(c->th_depth.as<float>() + c->n_kf_known, 0,
-                                 sizeof(float) * (size_t)(m->n_kf - c->n_kf_known), m->stream));
-        ORBFE_HIP(hipStreamSynchronize(m->stream));
-        c->n_kf_known = m->n_kf;
-    }
-    c->h_feat.resize((size_t)m->n_kf);
-    c->h_th_depth.resize((size_t)m->n_kf, 0.f);
-    c->h_not_erase.resize((size_t)m->n_kf, 0);
-    c->h_to_erase.resize((size_t)m->n_kf, 0);
-    return ORBFE_OK;
-}
-
-// The keypoint pools cover kf_mp's pool; what no set_keyframe_features wrote reads octave 0, no
-// right coordinate, depth -1.
-int cull_feat_ready(orbfe_map* m) {
-    MapCull* c = m->cull;
-    const MapRagged& r = m->kf_mp;
-    int st;
-    if (r.alloc > c->feat_alloc) {
-        if ((st = map_regrow(m, c->feat, 1, (size_t)c->feat_n, (size_t)r.alloc))) return st;
-        if ((st = map_regrow(m, c->depth, sizeof(float), (size_t)c->feat_n, (size_t)r.alloc))) return st;
-        c->feat_alloc = r.alloc;
-    }
-    if (r.used > c->feat_n) {
-        const long long k = r.used - c->feat_n;
-        ORBFE_HIP(hipMemsetAsync(c->feat.as<uint8_t>() + c->feat_n, 0, (size_t)k, m->stream));
-        if ((st = cull_fill<float>(m, c->depth.as<float>() + c->feat_n, k, -1.f))) return st;
-        ORBFE_HIP(hipStreamSynchronize(m->stream));
-        c->feat_n = r.used;
-    }
-    return ORBFE_OK;
-}
-
-CullDev cull_dev(orbfe_map* m) {
-    MapCull* c = m->cull;
-    CullDev d;
-    d.n_kf = m->n_kf;
-    d.n_mp = m->n_mp;
-    d.kf_mp_off = m->kf_mp.off.as<long long>();
-    d.kf_mp_n = m->kf_mp.len.as<int>();
-    d.kf_mp = m->kf_mp.pool.as<int>();
-    d.mp_bad = m->mp_bad.as<uint8_t>();
-    d.obs_off = m->mp_obs.off.as<long long>();
-    d.obs_n = m->mp_obs.len.as<int>();
-    d.obs = m->mp_obs.pool.as<int>();
-    d.idx_off = m->mp_idx.off.as<long long>();
-    d.idx_n = m->mp_idx.len.as<int>();
-    d.idx = m->mp_idx.pool.as<int>();
-    d.nobs = c->nobs.as<int>();
-    d.found = c->found.as<int>();
-    d.visible = c->visible.as<int>();
-    d.first = c->first.as<long long>();
-    d.mark = c->mark.as<int>();
-    return d;
-}
-
-bool map_cull_right(const orbfe_map* m, int kf, int idx) {
-    const MapCull* c = m->cull;
-    if (!c || kf < 0 || (size_t)kf >= c->h_feat.size()) return false;
-    const std::vector<uint8_t>& f = c->h_feat[kf];
-    return idx >= 0 && (size_t)idx < f.size() && (f[idx] & kCullRight);
-}
-
-// dst[slots[i]] += amounts[i] (or `amount`), slots in range; synchronous.
-int cull_add(orbfe_map* m, int n, const int* slots, const int* amounts, int amount, int* dst) {
-    if (!n) return ORBFE_OK;
-    MapCull* c = m->cull;
-    int st;
-    if ((st = c->stage_a.ensure(sizeof(int) * (size_t)n))) return st;
-    ORBFE_HIP(hipMemcpyAsync(c->stage_a.p, slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, m->stream));
-    if (amounts) {
-        if ((st = c->stage_b.ensure(sizeof(int) * (size_t)n))) return st;
-        ORBFE_HIP(hipMemcpyAsync(c->stage_b.p, amounts, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, m->stream));
-    }
-    hipLaunchKernelGGL(cull_add_kernel, dim3((n + 255) / 256), dim3(256), 0, m->stream, n, c->stage_a.as<int>(),
-                       amounts ? c->stage_b.as<int>() : nullptr, amount, dst);
-    ORBFE_HIP(hipGetLastError());
-    ORBFE_HIP(hipStreamSynchronize(m->stream));
-    return ORBFE_OK;
-}
-
-int map_cull_add_nobs(orbfe_map* m, const std::vector<int>& mp_slots, const std::vector<int>& amounts) {
-    int st;
-    if ((st = cull_ready(m))) return st;
-    return cull_add(m, (int)mp_slots.size(), mp_slots.data(), amounts.data(), 0, m->cull->nobs.as<int>());
-}
-
-template <class T>
-int cull_get(orbfe_map* m, int n, const int32_t* slots, const T* src, T* out) {
-    if (!n) return ORBFE_OK;
-    MapCull* c = m->cull;
-    int st;
-    if ((st = c->stage_a.ensure(sizeof(int) * (size_t)n))) return st;
-    if ((st = c->stage_c.ensure(sizeof(T) * (size_t)n))) return st;
-    ORBFE_HIP(hipMemcpyAsync(c->stage_a.p, slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(map_get_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, m->stream, n,
-                       c->stage_a.as<int>(), src, c->stage_c.as<T>());
-    ORBFE_HIP(hipGetLastError());
-    ORBFE_HIP(hipMemcpyAsync(out, c->stage_c.p, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
-    ORBFE_HIP(hipStreamSynchronize(m->stream));
-    return ORBFE_OK;
-}
 
 bool cull_points_ok(const orbfe_map* m, int n, const int32_t* slots) {
     if (n < 0 || (n && !slots)) return false;
@@ -703,73 +477,33 @@ bool cull_idx_known(const orbfe_map* m, int mp) {
 // MapPoint::SetBadFlag of distinct points whose indices are all known: one launch; the host rows follow.
 int cull_apply_bad(orbfe_map* m, const std::vector<int>& slots) {
     if (slots.empty()) return ORBFE_OK;
-    MapCull* c = m->cull;
     const int n = (int)slots.size();
     int st;
-    if ((st = c->stage_a.ensure(sizeof(int) * (size_t)n))) return st;
-    ORBFE_HIP(hipMemcpyAsync(c->stage_a.p, slots.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(cull_setbad_kernel, dim3((n + 3) / 4), dim3(256), 0, m->stream, cull_dev(m), n,
-                       c->stage_a.as<int>());
+    int* d_slots;
+    if ((st = store_stage_slots(m, n, slots.data(), d_slots))) return st;
+    hipLaunchKernelGGL(cull_setbad_kernel, dim3((n + 3) / 4), dim3(256), 0, m->stream, m->dev(), n, d_slots);
     ORBFE_HIP(hipGetLastError());
     ORBFE_HIP(hipStreamSynchronize(m->stream));
     for (int p : slots) {
         m->h_obs[p].clear();
         m->h_idx[p].clear();
-        m->mp_obs.h_n[p] = m->mp_idx.h_n[p] = 0;
+        m->mp_obs.len[p] = 0;
     }
     return ORBFE_OK;
-}
-
-int cull_pin(MapCull* c, size_t n) {
-    if (n <= c->pin_n) return ORBFE_OK;
-    if (c->pin) hipHostFree(c->pin);
-    c->pin = c->pin_dev = nullptr;
-    c->pin_n = 0;
-    size_t a = 1024;
-    while (a < n) a *= 2;
-    void* p = nullptr;
-    void* dp = nullptr;
-    if (hipHostMalloc(&p, sizeof(int) * a, hipHostMallocDefault) != hipSuccess) return ORBFE_ERR_NOMEM;
-    if (hipHostGetDevicePointer(&dp, p, 0) != hipSuccess) {
-        hipHostFree(p);
-        return ORBFE_ERR_NOMEM;
-    }
-    c->pin = static_cast<int*>(p);
-    c->pin_dev = static_cast<int*>(dp);
-    c->pin_n = a;
-    return ORBFE_OK;
-}
-
-CullKfDev cull_kf_dev(orbfe_map* m) {
-    MapCull* c = m->cull;
-    MapCovis* g = m->covis;
-    CullKfDev k;
-    k.feat = c->feat.as<uint8_t>();
-    k.depth = c->depth.as<float>();
-    k.th_depth = c->th_depth.as<float>();
-    k.kf_bad = m->kf_bad.as<uint8_t>();
-    k.kf_parent = m->kf_parent.as<int>();
-    k.kf_key = m->kf_key.as<unsigned long long>();
-    k.cpool = g->pool.as<int>();
-    k.coff = g->off.as<long long>();
-    k.ccap = g->cap.as<int>();
-    k.cnw = g->nw.as<int>();
-    k.cno = g->no.as<int>();
-    return k;
 }
 
 // KeyFrame::EraseChild (KeyFrame.cc:1108-1112).
 int cull_erase_child(orbfe_map* m, int parent, int child) {
-    MapRagged& r = m->kf_ch;
-    if ((size_t)parent >= r.h_n.size() || !r.h_n[parent]) return ORBFE_OK;
-    std::vector<int> row((size_t)r.h_n[parent]);
-    ORBFE_HIP(hipMemcpyAsync(row.data(), r.pool.as<int>() + r.h_off[parent], sizeof(int) * row.size(),
+    const RowTable& r = m->kf_ch;
+    if (!r.length(parent)) return ORBFE_OK;
+    std::vector<int> row((size_t)r.len[parent]);
+    ORBFE_HIP(hipMemcpyAsync(row.data(), m->kf_ch_pool.buf.as<int>() + r.off[parent], sizeof(int) * row.size(),
                              hipMemcpyDeviceToHost, m->stream));
     ORBFE_HIP(hipStreamSynchronize(m->stream));
     const auto it = std::find(row.begin(), row.end(), child);
     if (it == row.end()) return ORBFE_OK;
     row.erase(it);
-    return map_put_rows(m, r, {{parent, 0, (int)row.size(), (int)row.size(), row.data()}});
+    return map_put_kf_ch(m, {{parent, 0, (int)row.size(), (int)row.size(), row.data(), nullptr}});
 }
 
 struct CullKfResult {
@@ -782,61 +516,60 @@ struct CullKfResult {
 int cull_kf_bad(orbfe_map* m, int slot, CullKfResult& out) {
     int st;
     if ((st = cull_ready(m))) return st;
-    if ((st = cull_feat_ready(m))) return st;
+    if ((st = store_side_pools(m))) return st;
     if ((st = cov_ready(m))) return st;
-    MapCull* c = m->cull;
-    const int ns = m->kf_mp.h_n[slot];
-    const int nc = (size_t)slot < m->kf_ch.h_n.size() ? m->kf_ch.h_n[slot] : 0;
+    const int ns = m->kf_mp.len[slot];
+    const int nc = m->kf_ch.length(slot);
     std::vector<int> children((size_t)nc);
     if (nc)
-        ORBFE_HIP(hipMemcpyAsync(children.data(), m->kf_ch.pool.as<int>() + m->kf_ch.h_off[slot],
+        ORBFE_HIP(hipMemcpyAsync(children.data(), m->kf_ch_pool.buf.as<int>() + m->kf_ch.off[slot],
                                  sizeof(int) * (size_t)nc, hipMemcpyDeviceToHost, m->stream));
-    if ((st = c->flag.ensure(sizeof(int) * (size_t)std::max(ns, 1)))) return st;
-    if ((st = cull_pin(c, (size_t)kCullOutLists + 2 * (size_t)ns + 2 * (size_t)nc))) return st;
-    ORBFE_HIP(hipMemsetAsync(c->err.p, 0, sizeof(int), m->stream));
-    CullKfObsArgs a{cull_dev(m), cull_kf_dev(m), slot, kCullMark, c->flag.as<int>(), c->err.as<int>()};
+    if ((st = m->flag.ensure(sizeof(int) * (size_t)std::max(ns, 1)))) return st;
+    if ((st = store_pin_reserve(m, (size_t)kCullOutLists + 2 * (size_t)ns + 2 * (size_t)nc))) return st;
+    if ((st = store_clear_err(m))) return st;
     const dim3 grid((unsigned)((ns + kCullWaves - 1) / kCullWaves));
     const dim3 ugrid((unsigned)((ns + 255) / 256));
     int err = 0;
     if (ns) {
+        CullKfObsArgs a{m->dev(), cull_dev(m), slot, kCullMark, m->flag.as<int>()};
         hipLaunchKernelGGL(cull_kf_obs_kernel, grid, dim3(kCullBlock), 0, m->stream, a);
         a.mode = kCullCheck;
         hipLaunchKernelGGL(cull_kf_obs_kernel, grid, dim3(kCullBlock), 0, m->stream, a);
         ORBFE_HIP(hipGetLastError());
     }
-    ORBFE_HIP(hipMemcpyAsync(&err, c->err.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    ORBFE_HIP(hipStreamSynchronize(m->stream));
+    if ((st = store_read_err(m, err))) return st;
     if (!err) err = cov_single(m, kCovOpEraseKf, slot, -1, 0) ? 2 : 0;  // :1188-1189, :1198-1199
+    // the views of what follows: the connection part may have moved the graph's pool
+    CullKfObsArgs a{m->dev(), cull_dev(m), slot, kCullApply, m->flag.as<int>()};
     if (err) {
-        if (ns) hipLaunchKernelGGL(cull_kf_unmark_kernel, ugrid, dim3(256), 0, m->stream, a.d, slot);
+        if (ns) hipLaunchKernelGGL(cull_kf_unmark_kernel, ugrid, dim3(256), 0, m->stream, a.d, a.c, slot);
         ORBFE_HIP(hipStreamSynchronize(m->stream));
         return err == 1 ? ORBFE_ERR_ARG : ORBFE_ERR_HIP;
     }
-    a.k = cull_kf_dev(m);  // the graph's pool may have moved
     if (ns) {
-        a.mode = kCullApply;
         hipLaunchKernelGGL(cull_kf_obs_kernel, grid, dim3(kCullBlock), 0, m->stream, a);  // :1191-1193
-        hipLaunchKernelGGL(cull_kf_unmark_kernel, ugrid, dim3(256), 0, m->stream, a.d, slot);
+        hipLaunchKernelGGL(cull_kf_unmark_kernel, ugrid, dim3(256), 0, m->stream, a.d, a.c, slot);
     }
     int* res = m->pin;
     __atomic_store_n(&res[kResDone], -1, __ATOMIC_RELEASE);
     CullKfFinishArgs f{};
     f.d = a.d;
-    f.k = a.k;
+    f.g = cov_dev(m);
+    f.c = a.c;
     f.kf = slot;
     f.nc = nc;
-    f.flag = c->flag.as<int>();
-    f.ch = nc ? m->kf_ch.pool.as<int>() + m->kf_ch.h_off[slot] : nullptr;
-    f.cand = c->cand.as<int>();
-    f.out = c->pin_dev;
+    f.flag = m->flag.as<int>();
+    f.ch = nc ? m->kf_ch_pool.buf.as<int>() + m->kf_ch.off[slot] : nullptr;
+    f.out = m->pin_dev + kResTail;
     f.res = m->pin_dev;
     hipLaunchKernelGGL(cull_kf_finish_kernel, dim3(1), dim3(kCullBlock), 0, m->stream, f);
     ORBFE_HIP(hipGetLastError());
     if ((st = wait_words(res + kResDone, 1, -1, m->stream, 20000))) return st;
-    const int ne = c->pin[kCullOutErased], nb = c->pin[kCullOutBad], nr = c->pin[kCullOutRounds];
-    const int np = c->pin[kCullOutPairs], parent = c->pin[kCullOutParent];
+    const int* rep = m->pin + kResTail;
+    const int ne = rep[kCullOutErased], nb = rep[kCullOutBad], nr = rep[kCullOutRounds];
+    const int np = rep[kCullOutPairs], parent = rep[kCullOutParent];
     if (ne < 0 || ne > ns || nb < 0 || nb > ne || nr < 0 || nr > np || np > nc) return ORBFE_ERR_HIP;
-    const int* erased = c->pin + kCullOutLists;
+    const int* erased = rep + kCullOutLists;
     const int* bad = erased + ns;
     const int* pairs = bad + ns;
     // the host rows follow the device's
@@ -850,13 +583,13 @@ int cull_kf_bad(orbfe_map* m, int slot, CullKfResult& out) {
         if (*xi < 0) --m->n_unknown;
         m->h_idx[p].erase(xi);
         o.erase(it);
-        m->mp_obs.h_n[p] = m->mp_idx.h_n[p] = (int)o.size();
+        m->mp_obs.len[p] = (int)o.size();
     }
     for (int i = 0; i < nb; ++i) {
         const int p = bad[i];
         m->h_obs[p].clear();
         m->h_idx[p].clear();
-        m->mp_obs.h_n[p] = m->mp_idx.h_n[p] = 0;
+        m->mp_obs.len[p] = 0;
         out.bad.push_back(p);
     }
     // AddChild of every ChangeParent (:1118), this keyframe's mspChildrens without the children
@@ -872,7 +605,7 @@ int cull_kf_bad(orbfe_map* m, int slot, CullKfResult& out) {
         std::vector<int> left;
         for (int ch : children)
             if (std::find(who.begin(), who.begin() + nr, ch) == who.begin() + nr) left.push_back(ch);
-        if ((st = map_put_rows(m, m->kf_ch, {{slot, 0, (int)left.size(), (int)left.size(), left.data()}}))) return st;
+        if ((st = map_put_kf_ch(m, {{slot, 0, (int)left.size(), (int)left.size(), left.data(), nullptr}}))) return st;
     }
     if (parent >= 0 && (st = cull_erase_child(m, parent, slot))) return st;
     return ORBFE_OK;
@@ -901,11 +634,10 @@ int cull_report(const CullKfResult& r, int32_t* bad_points, int bad_cap, int32_t
 
 // KeyFrame::SetBadFlag from its top (:1174-1186).
 int cull_kf_set_bad(orbfe_map* m, int slot, bool is_first, int& what, CullKfResult& r) {
-    MapCull* c = m->cull;
     what = ORBFE_MAP_BAD_NOTHING;
     if (is_first) return ORBFE_OK;     // :1179
-    if (c->h_not_erase[slot]) {        // :1181-1185
-        c->h_to_erase[slot] = 1;
+    if (m->h_not_erase[slot]) {        // :1181-1185
+        m->h_to_erase[slot] = 1;
         what = ORBFE_MAP_BAD_DEFERRED;
         return ORBFE_OK;
     }
@@ -927,7 +659,7 @@ int orbfe_map_set_not_erase(orbfe_map* m, int slot, int flag) {
     return map_guarded(m, [&]() {
         int st;
         if ((st = cull_ready(m))) return st;
-        m->cull->h_not_erase[slot] = flag ? 1 : 0;
+        m->h_not_erase[slot] = flag ? 1 : 0;
         return (int)ORBFE_OK;
     });
 }
@@ -937,8 +669,8 @@ int orbfe_map_get_erase_flags(orbfe_map* m, int slot, int32_t* not_erase, int32_
     return map_guarded(m, [&]() {
         int st;
         if ((st = cull_ready(m))) return st;
-        if (not_erase) *not_erase = m->cull->h_not_erase[slot];
-        if (to_be_erased) *to_be_erased = m->cull->h_to_erase[slot];
+        if (not_erase) *not_erase = m->h_not_erase[slot];
+        if (to_be_erased) *to_be_erased = m->h_to_erase[slot];
         return (int)ORBFE_OK;
     });
 }
@@ -965,13 +697,12 @@ int orbfe_map_set_erase(orbfe_map* m, int slot, int has_loop_edges, int is_first
         int st, w = ORBFE_MAP_BAD_NOTHING;
         CullKfResult r;
         if ((st = cull_ready(m))) return st;
-        MapCull* c = m->cull;
-        const uint8_t was = c->h_not_erase[slot];
-        if (!has_loop_edges) c->h_not_erase[slot] = 0;  // KeyFrame.cc:1162-1165
-        if (c->h_to_erase[slot]) st = cull_kf_set_bad(m, slot, is_first != 0, w, r);  // :1168-1171
+        const uint8_t was = m->h_not_erase[slot];
+        if (!has_loop_edges) m->h_not_erase[slot] = 0;  // KeyFrame.cc:1162-1165
+        if (m->h_to_erase[slot]) st = cull_kf_set_bad(m, slot, is_first != 0, w, r);  // :1168-1171
         if (what) *what = w;
         if (st) {
-            c->h_not_erase[slot] = was;  // refused: nothing has changed
+            m->h_not_erase[slot] = was;  // refused: nothing has changed
             return st;
         }
         return cull_report(r, bad_points, bad_cap, n_bad, pairs, pair_cap, n_pairs);
@@ -992,17 +723,15 @@ int orbfe_map_cull_keyframes(orbfe_map* m, int current_slot, int n, const int32_
     return map_guarded(m, [&]() {
         int st;
         if ((st = cull_ready(m))) return st;
-        if ((st = cull_feat_ready(m))) return st;
+        if ((st = store_side_pools(m))) return st;
         if ((st = cov_ready(m))) return st;
-        MapCull* c = m->cull;
         // vpLocalKeyFrames (LocalMapping.cc:638): a copy, taken before anything is culled
         std::vector<int> list;
         if (kf_slots) list.assign(kf_slots, kf_slots + n);
         else {
-            const MapCovis* g = m->covis;
-            list.resize((size_t)g->h_no[current_slot]);
+            list.resize((size_t)m->h_no[current_slot]);
             if (!list.empty()) {
-                ORBFE_HIP(hipMemcpyAsync(list.data(), g->pool.as<int>() + g->h_off[current_slot] + 2ll * g->h_cap[current_slot],
+                ORBFE_HIP(hipMemcpyAsync(list.data(), m->cov_pool.buf.as<int>() + m->cov.off[current_slot] + 2ll * m->cov.cap[current_slot],
                                          sizeof(int) * list.size(), hipMemcpyDeviceToHost, m->stream));
                 ORBFE_HIP(hipStreamSynchronize(m->stream));
             }
@@ -1012,9 +741,9 @@ int orbfe_map_cull_keyframes(orbfe_map* m, int current_slot, int n, const int32_
         if (nl > kCullMaxList || nl > result_cap) return (int)ORBFE_ERR_CAPACITY;
         if (m->n_unknown) return (int)ORBFE_ERR_ARG;  // an observer's octave could not be read
         if (!nl) return cull_report(CullKfResult(), bad_points, bad_cap, n_bad, pairs, pair_cap, n_pairs);
-        if ((st = c->list.ensure(sizeof(int) * (size_t)nl))) return st;
-        if ((st = c->res.ensure(sizeof(int) * (size_t)nl))) return st;
-        ORBFE_HIP(hipMemcpyAsync(c->list.p, list.data(), sizeof(int) * (size_t)nl, hipMemcpyHostToDevice, m->stream));
+        if ((st = m->list.ensure(sizeof(int) * (size_t)nl))) return st;
+        if ((st = m->decided.ensure(sizeof(int) * (size_t)nl))) return st;
+        ORBFE_HIP(hipMemcpyAsync(m->list.p, list.data(), sizeof(int) * (size_t)nl, hipMemcpyHostToDevice, m->stream));
         CullKfResult r;
         std::vector<int> dec((size_t)nl);
         bool changed = false;
@@ -1022,21 +751,19 @@ int orbfe_map_cull_keyframes(orbfe_map* m, int current_slot, int n, const int32_
             // every keyframe not yet passed decides on the map as it stands; the first that culls is
             // certain, the ones after it decide again once it is gone
             CullDecideArgs a{};
-            a.d = cull_dev(m);
-            a.k = cull_kf_dev(m);
+            a.d = m->dev();
+            a.c = cull_dev(m);
             a.n = nl - from;
             a.first_slot = first_kf_slot;
             a.mono = monocular ? 1 : 0;
-            a.list = c->list.as<int>() + from;
-            a.res = c->res.as<int>();
-            a.err = c->err.as<int>();
+            a.list = m->list.as<int>() + from;
+            a.res = m->decided.as<int>();
             int err = 0;
-            ORBFE_HIP(hipMemsetAsync(c->err.p, 0, sizeof(int), m->stream));
+            if ((st = store_clear_err(m))) return st;
             hipLaunchKernelGGL(cull_decide_kernel, dim3((unsigned)a.n), dim3(kCullBlock), 0, m->stream, a);
             ORBFE_HIP(hipGetLastError());
-            ORBFE_HIP(hipMemcpyAsync(dec.data(), c->res.p, sizeof(int) * (size_t)a.n, hipMemcpyDeviceToHost, m->stream));
-            ORBFE_HIP(hipMemcpyAsync(&err, c->err.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-            ORBFE_HIP(hipStreamSynchronize(m->stream));
+            ORBFE_HIP(hipMemcpyAsync(dec.data(), a.res, sizeof(int) * (size_t)a.n, hipMemcpyDeviceToHost, m->stream));
+            if ((st = store_read_err(m, err))) return st;
             if (err) return changed ? (int)ORBFE_ERR_HIP : (int)ORBFE_ERR_ARG;
             int i = from;
             for (; i < nl; ++i) {
@@ -1060,15 +787,14 @@ int orbfe_map_cull_keyframes(orbfe_map* m, int current_slot, int n, const int32_
 
 int orbfe_map_set_keyframe_features(orbfe_map* m, int slot, int n, const int32_t* octaves,
                                     const float* mvu_right, const float* depth, float th_depth) {
-    if (!m || !m->kf_ok(slot) || n != m->kf_mp.h_n[slot]) return ORBFE_ERR_ARG;
+    if (!m || !m->kf_ok(slot) || n != m->kf_mp.len[slot]) return ORBFE_ERR_ARG;
     if (octaves)
         for (int i = 0; i < n; ++i)
             if (octaves[i] < 0 || octaves[i] >= kCullRight) return ORBFE_ERR_ARG;
     return map_guarded(m, [&]() {
         int st;
         if ((st = cull_ready(m))) return st;
-        if ((st = cull_feat_ready(m))) return st;
-        MapCull* c = m->cull;
+        if ((st = store_side_pools(m))) return st;
         std::vector<uint8_t> f((size_t)n);
         std::vector<float> d((size_t)n);
         for (int i = 0; i < n; ++i) {
@@ -1076,15 +802,15 @@ int orbfe_map_set_keyframe_features(orbfe_map* m, int slot, int n, const int32_t
             d[i] = depth ? depth[i] : -1.f;
         }
         if (n) {
-            const long long off = m->kf_mp.h_off[slot];
-            ORBFE_HIP(hipMemcpyAsync(c->feat.as<uint8_t>() + off, f.data(), (size_t)n, hipMemcpyHostToDevice, m->stream));
-            ORBFE_HIP(hipMemcpyAsync(c->depth.as<float>() + off, d.data(), sizeof(float) * (size_t)n,
+            const long long off = m->kf_mp.off[slot];
+            ORBFE_HIP(hipMemcpyAsync(m->feat_pool.buf.as<uint8_t>() + off, f.data(), (size_t)n, hipMemcpyHostToDevice, m->stream));
+            ORBFE_HIP(hipMemcpyAsync(m->depth_pool.buf.as<float>() + off, d.data(), sizeof(float) * (size_t)n,
                                      hipMemcpyHostToDevice, m->stream));
         }
-        ORBFE_HIP(hipMemcpyAsync(c->th_depth.as<float>() + slot, &th_depth, sizeof(float), hipMemcpyHostToDevice, m->stream));
+        ORBFE_HIP(hipMemcpyAsync(m->at<float>(kColThDepth) + slot, &th_depth, sizeof(float), hipMemcpyHostToDevice, m->stream));
         ORBFE_HIP(hipStreamSynchronize(m->stream));
-        c->h_feat[slot] = std::move(f);
-        c->h_th_depth[slot] = th_depth;
+        m->h_feat[slot] = std::move(f);
+        m->h_th_depth[slot] = th_depth;
         return (int)ORBFE_OK;
     });
 }
@@ -1095,17 +821,16 @@ int orbfe_map_get_keyframe_features(orbfe_map* m, int slot, int cap, int32_t* oc
     return map_guarded(m, [&]() {
         int st;
         if ((st = cull_ready(m))) return st;
-        if ((st = cull_feat_ready(m))) return st;
-        MapCull* c = m->cull;
-        *n = m->kf_mp.h_n[slot];
-        if (th_depth) *th_depth = c->h_th_depth[slot];
+        if ((st = store_side_pools(m))) return st;
+        *n = m->kf_mp.len[slot];
+        if (th_depth) *th_depth = m->h_th_depth[slot];
         if (*n > cap) return (int)ORBFE_ERR_CAPACITY;
         if (!*n) return (int)ORBFE_OK;
         std::vector<uint8_t> f((size_t)*n);
-        const long long off = m->kf_mp.h_off[slot];
-        ORBFE_HIP(hipMemcpyAsync(f.data(), c->feat.as<uint8_t>() + off, (size_t)*n, hipMemcpyDeviceToHost, m->stream));
+        const long long off = m->kf_mp.off[slot];
+        ORBFE_HIP(hipMemcpyAsync(f.data(), m->feat_pool.buf.as<uint8_t>() + off, (size_t)*n, hipMemcpyDeviceToHost, m->stream));
         if (depth)
-            ORBFE_HIP(hipMemcpyAsync(depth, c->depth.as<float>() + off, sizeof(float) * (size_t)*n,
+            ORBFE_HIP(hipMemcpyAsync(depth, m->depth_pool.buf.as<float>() + off, sizeof(float) * (size_t)*n,
                                      hipMemcpyDeviceToHost, m->stream));
         ORBFE_HIP(hipStreamSynchronize(m->stream));
         for (int i = 0; i < *n; ++i) {
@@ -1122,12 +847,11 @@ int orbfe_map_set_point_counters(orbfe_map* m, int n, const int32_t* mp_slots, c
     return map_guarded(m, [&]() {
         int st;
         if ((st = cull_ready(m))) return st;
-        MapCull* c = m->cull;
-        if (n_obs && (st = map_set<int>(m, n, mp_slots, n_obs, 0, c->nobs.as<int>()))) return st;
-        if (found && (st = map_set<int>(m, n, mp_slots, found, 0, c->found.as<int>()))) return st;
-        if (visible && (st = map_set<int>(m, n, mp_slots, visible, 0, c->visible.as<int>()))) return st;
-        if (first_kf_id && (st = map_set<long long>(m, n, mp_slots, reinterpret_cast<const long long*>(first_kf_id),
-                                                    0ll, c->first.as<long long>())))
+        if (n_obs && (st = store_set<int>(m, m->at<int>(kColNobs), n, mp_slots, n_obs))) return st;
+        if (found && (st = store_set<int>(m, m->at<int>(kColFound), n, mp_slots, found))) return st;
+        if (visible && (st = store_set<int>(m, m->at<int>(kColVisible), n, mp_slots, visible))) return st;
+        if (first_kf_id && (st = store_set<long long>(m, m->at<long long>(kColFirstKf), n, mp_slots,
+                                                      reinterpret_cast<const long long*>(first_kf_id))))
             return st;
         return (int)ORBFE_OK;
     });
@@ -1139,12 +863,11 @@ int orbfe_map_get_point_counters(orbfe_map* m, int n, const int32_t* mp_slots, i
     return map_guarded(m, [&]() {
         int st;
         if ((st = cull_ready(m))) return st;
-        MapCull* c = m->cull;
-        if (n_obs && (st = cull_get<int>(m, n, mp_slots, c->nobs.as<int>(), n_obs))) return st;
-        if (found && (st = cull_get<int>(m, n, mp_slots, c->found.as<int>(), found))) return st;
-        if (visible && (st = cull_get<int>(m, n, mp_slots, c->visible.as<int>(), visible))) return st;
-        if (first_kf_id && (st = cull_get<long long>(m, n, mp_slots, c->first.as<long long>(),
-                                                     reinterpret_cast<long long*>(first_kf_id))))
+        if (n_obs && (st = store_get<int>(m, m->at<int>(kColNobs), n, mp_slots, n_obs))) return st;
+        if (found && (st = store_get<int>(m, m->at<int>(kColFound), n, mp_slots, found))) return st;
+        if (visible && (st = store_get<int>(m, m->at<int>(kColVisible), n, mp_slots, visible))) return st;
+        if (first_kf_id && (st = store_get<long long>(m, m->at<long long>(kColFirstKf), n, mp_slots,
+                                                      reinterpret_cast<long long*>(first_kf_id))))
             return st;
         return (int)ORBFE_OK;
     });
@@ -1156,8 +879,7 @@ int orbfe_map_increase_counters(orbfe_map* m, int kind, int n, const int32_t* mp
     return map_guarded(m, [&]() {
         int st;
         if ((st = cull_ready(m))) return st;
-        MapCull* c = m->cull;
-        return cull_add(m, n, mp_slots, amounts, 1, (kind == ORBFE_MAP_FOUND ? c->found : c->visible).as<int>());
+        return store_add(m, m->at<int>(kind == ORBFE_MAP_FOUND ? kColFound : kColVisible), n, mp_slots, amounts, 1);
     });
 }
 
@@ -1169,16 +891,14 @@ int orbfe_map_increase_counters_device(orbfe_map* m, int kind, int n, const int3
     return map_guarded(m, [&]() {
         int st;
         if ((st = cull_ready(m))) return st;
-        MapCull* c = m->cull;
-        int* dst = (kind == ORBFE_MAP_FOUND ? c->found : c->visible).as<int>();
+        int* dst = m->at<int>(kind == ORBFE_MAP_FOUND ? kColFound : kColVisible);
         int err = 0;
-        ORBFE_HIP(hipMemsetAsync(c->err.p, 0, sizeof(int), m->stream));
+        if ((st = store_clear_err(m))) return st;
         for (int apply = 0; apply < 2; ++apply)
             hipLaunchKernelGGL(cull_add_masked_kernel, dim3((n + 255) / 256), dim3(256), 0, m->stream, n,
-                               d_mp_slots, d_mask, m->n_mp, apply, dst, c->err.as<int>());
+                               d_mp_slots, d_mask, m->n_mp, apply, dst, m->call_err());
         ORBFE_HIP(hipGetLastError());
-        ORBFE_HIP(hipMemcpyAsync(&err, c->err.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        ORBFE_HIP(hipStreamSynchronize(m->stream));
+        if ((st = store_read_err(m, err))) return st;
         return err ? (int)ORBFE_ERR_ARG : (int)ORBFE_OK;
     });
 }
@@ -1206,11 +926,10 @@ int orbfe_map_erase_observation(orbfe_map* m, int mp_slot, int kf_slot, int32_t*
     return map_guarded(m, [&]() {
         int st;
         if ((st = cull_ready(m))) return st;
-        MapCull* c = m->cull;
         const int ix = m->h_idx[mp_slot][it - o.begin()];
-        const int by = ix >= 0 && map_cull_right(m, kf_slot, ix) ? 2 : 1;  // :360-363
+        const int by = ix >= 0 && map_has_right(m, kf_slot, ix) ? 2 : 1;  // :360-363
         int32_t nobs = 0, s = mp_slot, k = kf_slot;
-        if ((st = cull_get<int>(m, 1, &s, c->nobs.as<int>(), &nobs))) return st;
+        if ((st = store_get<int>(m, m->at<int>(kColNobs), 1, &s, &nobs))) return st;
         const bool bad = nobs - by <= 2;  // :371
         if (bad)
             for (size_t j = 0; j < o.size(); ++j)
@@ -1232,33 +951,34 @@ int orbfe_map_cull_points(orbfe_map* m, int64_t current_kf_id, int monocular, in
     return map_guarded(m, [&]() {
         int st;
         if ((st = cull_ready(m))) return st;
-        MapCull* c = m->cull;
-        if ((st = cull_pin(c, 2 * (size_t)n_in))) return st;
-        if ((st = c->stage_a.ensure(sizeof(int) * (size_t)n_in))) return st;
-        ORBFE_HIP(hipMemcpyAsync(c->stage_a.p, list, sizeof(int) * (size_t)n_in, hipMemcpyHostToDevice, m->stream));
+        if ((st = store_pin_reserve(m, 2 * (size_t)n_in))) return st;
+        int* d_list;
+        if ((st = store_stage_slots(m, n_in, list, d_list))) return st;
         int* res = m->pin;
-        res[kCullResStatus] = ORBFE_OK;
+        res[kResCullStatus] = ORBFE_OK;
         __atomic_store_n(&res[kResDone], -1, __ATOMIC_RELEASE);
         CullPointsArgs a{};
-        a.d = cull_dev(m);
+        a.d = m->dev();
+        a.c = cull_dev(m);
         a.n = n_in;
         a.th_obs = monocular ? 2 : 3;  // LocalMapping.cc:176-181
         a.cur = (int)current_kf_id;
-        a.list = c->stage_a.as<int>();
-        a.kept = c->pin_dev;
-        a.culled = c->pin_dev + n_in;
+        a.list = d_list;
+        a.kept = m->pin_dev + kResTail;
+        a.culled = m->pin_dev + kResTail + n_in;
         a.res = m->pin_dev;
         hipLaunchKernelGGL(cull_points_kernel, dim3(1), dim3(kCullBlock), 0, m->stream, a);
         ORBFE_HIP(hipGetLastError());
         if ((st = wait_words(res + kResDone, 1, -1, m->stream, 20000))) return st;
-        if (res[kCullResStatus] != ORBFE_OK) return res[kCullResStatus];
-        const int nk = res[kCullResKept], nc = res[kCullResCulled];
+        if (res[kResCullStatus] != ORBFE_OK) return res[kResCullStatus];
+        const int nk = res[kResKept], nc = res[kResCulled];
         if (nk < 0 || nc < 0 || nk + nc > n_in) return (int)ORBFE_ERR_HIP;
-        const std::vector<int> gone(c->pin + n_in, c->pin + n_in + nc);
+        const int* kept = m->pin + kResTail;
+        const std::vector<int> gone(kept + n_in, kept + n_in + nc);
         for (int p : gone)
             if (!m->mp_ok(p) || !cull_idx_known(m, p)) return (int)ORBFE_ERR_ARG;
         if ((st = cull_apply_bad(m, gone))) return st;
-        std::copy(c->pin, c->pin + nk, list);
+        std::copy(kept, kept + nk, list);
         std::copy(gone.begin(), gone.end(), culled);
         *n_out = nk;
         *n_culled = nc;
@@ -1273,22 +993,22 @@ int orbfe_map_tracked_map_points(orbfe_map* m, int slot, int min_obs, int32_t* n
         if ((st = cull_ready(m))) return st;
         int* res = m->pin;
         __atomic_store_n(&res[kResDone], -1, __ATOMIC_RELEASE);
-        hipLaunchKernelGGL(cull_tracked_kernel, dim3(1), dim3(kCullBlock), 0, m->stream, cull_dev(m), slot,
-                           min_obs, m->pin_dev);
+        hipLaunchKernelGGL(cull_tracked_kernel, dim3(1), dim3(kCullBlock), 0, m->stream, m->dev(), cull_dev(m),
+                           slot, min_obs, m->pin_dev);
         ORBFE_HIP(hipGetLastError());
         if ((st = wait_words(res + kResDone, 1, -1, m->stream, 20000))) return st;
-        *n = res[kCullResValue];
+        *n = res[kResValue];
         return (int)ORBFE_OK;
     });
 }
 
 int orbfe_map_get_keyframe_points(orbfe_map* m, int slot, int32_t* mp_slots, int cap, int32_t* n) {
     if (!m || !n || cap < 0 || (cap && !mp_slots) || !m->kf_ok(slot)) return ORBFE_ERR_ARG;
-    *n = m->kf_mp.h_n[slot];
+    *n = m->kf_mp.len[slot];
     if (*n > cap) return ORBFE_ERR_CAPACITY;
     if (!*n) return ORBFE_OK;
     return map_guarded(m, [&]() {
-        ORBFE_HIP(hipMemcpyAsync(mp_slots, m->kf_mp.pool.as<int>() + m->kf_mp.h_off[slot], sizeof(int) * (size_t)*n,
+        ORBFE_HIP(hipMemcpyAsync(mp_slots, m->kf_mp_pool.buf.as<int>() + m->kf_mp.off[slot], sizeof(int) * (size_t)*n,
                                  hipMemcpyDeviceToHost, m->stream));
         ORBFE_HIP(hipStreamSynchronize(m->stream));
         return (int)ORBFE_OK;
@@ -1298,19 +1018,19 @@ int orbfe_map_get_keyframe_points(orbfe_map* m, int slot, int32_t* mp_slots, int
 int orbfe_map_get_observations(orbfe_map* m, int mp_slot, int32_t* kf_slots, int32_t* idx, int cap, int32_t* n) {
     if (!m || !n || cap < 0 || (cap && !kf_slots) || !m->mp_ok(mp_slot)) return ORBFE_ERR_ARG;
     return map_guarded(m, [&]() {
-        int len[2] = {0, 0};
-        ORBFE_HIP(hipMemcpyAsync(&len[0], m->mp_obs.len.as<int>() + mp_slot, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        ORBFE_HIP(hipMemcpyAsync(&len[1], m->mp_idx.len.as<int>() + mp_slot, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        int len = 0;
+        ORBFE_HIP(hipMemcpyAsync(&len, m->at<int>(kColMpObsLen) + mp_slot, sizeof(int), hipMemcpyDeviceToHost, m->stream));
         ORBFE_HIP(hipStreamSynchronize(m->stream));
         const std::vector<int>& o = m->h_obs[mp_slot];
-        if (len[0] != (int)o.size() || len[1] != len[0]) return (int)ORBFE_ERR_HIP;  // the host rows are the device's
-        *n = len[0];
+        if (len != (int)o.size()) return (int)ORBFE_ERR_HIP;  // the host rows are the device's
+        *n = len;
         if (*n > cap) return (int)ORBFE_ERR_CAPACITY;
         if (!*n) return (int)ORBFE_OK;
         std::vector<int> x((size_t)*n);
-        ORBFE_HIP(hipMemcpyAsync(kf_slots, m->mp_obs.pool.as<int>() + m->mp_obs.h_off[mp_slot], sizeof(int) * (size_t)*n,
+        const long long off = m->mp_obs.off[mp_slot];
+        ORBFE_HIP(hipMemcpyAsync(kf_slots, m->mp_obs_pool.buf.as<int>() + off, sizeof(int) * (size_t)*n,
                                  hipMemcpyDeviceToHost, m->stream));
-        ORBFE_HIP(hipMemcpyAsync(x.data(), m->mp_idx.pool.as<int>() + m->mp_idx.h_off[mp_slot], sizeof(int) * (size_t)*n,
+        ORBFE_HIP(hipMemcpyAsync(x.data(), m->mp_idx_pool.buf.as<int>() + off, sizeof(int) * (size_t)*n,
                                  hipMemcpyDeviceToHost, m->stream));
         ORBFE_HIP(hipStreamSynchronize(m->stream));
         if (!std::equal(o.begin(), o.end(), kf_slots) || x != m->h_idx[mp_slot]) return (int)ORBFE_ERR_HIP;
@@ -1327,7 +1047,7 @@ int orbfe_map_get_bad_flags(orbfe_map* m, int kind, int n, const int32_t* slots,
     return map_guarded(m, [&]() {
         int st;
         if ((st = cull_ready(m))) return st;
-        return cull_get<uint8_t>(m, n, slots, (kind == ORBFE_MAP_KEYFRAMES ? m->kf_bad : m->mp_bad).as<uint8_t>(), bad);
+        return store_get<uint8_t>(m, m->at<uint8_t>(kind == ORBFE_MAP_KEYFRAMES ? kColKfBad : kColMpBad), n, slots, bad);
     });
 }
 

@@ -15,7 +15,10 @@
 //   map_write_kernel     the ordered point list, the points' stamps, the done word
 //   map_gather_kernel    the listed points' data into the contiguous inputs of
 //                        orbfe_search_local_points_device
-//   map_rows_kernel / map_set_kernel / map_kf_init_kernel   the mutators' scatters
+//   map_kf_key_kernel / map_neigh_kernel   a new keyframe's key, an assigned neighbour list
+//
+// The handle, its columns, row tables and staging are the store's (orbfe_map_store.hip); the
+// mutators here go through store_put_rows, store_set and store_get.
 //
 // Everything is integer-exact.  The vote counts are deterministic; the touched list's order is
 // not, and is used only as a set (it is sorted by key before anything reads it as an order).
@@ -23,8 +26,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/orbfe.h"
@@ -32,49 +33,9 @@
 
 namespace orbfe {
 
-constexpr int kMapBlock = 1024;
-constexpr int kMapMaxVoted = ORBFE_MAP_MAX_VOTED;        // keyframes map_local_kf_kernel sorts in LDS
-constexpr int kMapListCap = kMapMaxVoted + 8;            // phase 2 adds at most 3 to a list of <= 80
-constexpr int kMapMaxSlots = ORBFE_MAP_MAX_KF_SLOTS;     // mvpMapPoints of one keyframe; the pitch of a position
-constexpr int kMapNeigh = 10;                            // GetBestCovisibilityKeyFrames(10)
 constexpr int kMapLimit = 80;                            // :1545
-constexpr int kMapNoPos = 0x7f7f7f7f;                    // first_pos of a point no slot has claimed
-constexpr int kMapChunks = kMapMaxSlots / kMapBlock;
 constexpr int kMapMaxRankBlocks = 256;
-
-// device control words (ints)
-enum { kCtlTouched, kCtlErr, kCtlNKf, kCtlRef, kCtlNMp, kCtlRun, kCtlStatus, kCtlCountA, kCtlCountB,
-       kCtlWords = 16 };
-// pinned result words, then the keyframe list
-enum { kResNKf, kResRef, kResNMp, kResStatus, kResDone, kResList = 16 };
-
-struct MapDev {
-    int n_kf, n_mp;
-    const unsigned long long* kf_key;
-    const uint8_t* kf_bad;
-    unsigned long long* kf_stamp;
-    const long long* kf_mp_off;
-    const int* kf_mp_n;
-    const int* kf_mp;
-    const int* kf_neigh;
-    const long long* kf_ch_off;
-    const int* kf_ch_n;
-    const int* kf_ch;
-    const int* kf_parent;
-    const uint8_t* mp_bad;
-    unsigned long long* mp_stamp;
-    const long long* mp_obs_off;
-    const int* mp_obs_n;
-    const int* mp_obs;
-    // scratch: kf_cnt is all 0 and first_pos all kMapNoPos between queries
-    int* kf_cnt;
-    int* touched;
-    int* first_pos;
-    int* ctl;
-    int* local_kf;
-    int* local_mp;
-    int* blk;
-};
+constexpr int kResList = kResTail;                       // the keyframe list, in the pinned block's tail
 
 // True in every thread of the last of the grid's `nblocks` workgroups (any grid shape) to get
 // here; *counter is 0 before the launch.  The form of bow_pair_search (orbfe_bow.hip): barrier,
@@ -386,60 +347,13 @@ __global__ __launch_bounds__(256) void map_gather_kernel(MapGatherArgs a) {
     }
 }
 
-// One row write of a ragged table: n ints from staged[src ..) to pool[dst ..), and the row's
-// (offset, length) when row >= 0.  One wave per item.
-struct MapRowItem {
-    long long dst, new_off;
-    int src, n, row, new_n;
-};
-
-__global__ __launch_bounds__(256) void map_rows_kernel(int n_items, const MapRowItem* items,
-                                                       const int* staged, int* pool, long long* off,
-                                                       int* len) {
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= n_items) return;
-    const MapRowItem it = items[w];
-    const int lane = threadIdx.x & 63;
-    for (int j = lane; j < it.n; j += 64) pool[it.dst + j] = staged[it.src + j];
-    if (lane == 0 && it.row >= 0) {
-        off[it.row] = it.new_off;
-        len[it.row] = it.new_n;
-    }
-}
-
-// dst[slots[i]] = vals ? vals[i] : value
-template <class T>
-__global__ __launch_bounds__(256) void map_set_kernel(int n, const int* slots, const T* vals, T value,
-                                                      T* dst) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[slots[i]] = vals ? vals[i] : value;
-}
-
-template <class T>
-__global__ __launch_bounds__(256) void map_get_kernel(int n, const int* slots, const T* src, T* out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = src[slots[i]];
-}
-
 struct MapNeighList {
     int v[kMapNeigh];
 };
 
-// A new KeyFrame: not bad, stamp 0 (KeyFrame.cc:35), no neighbours, children or parent.
-__global__ void map_kf_init_kernel(int slot, unsigned long long key, unsigned long long* kf_key,
-                                   uint8_t* kf_bad, unsigned long long* kf_stamp, int* kf_neigh,
-                                   long long* ch_off, int* ch_n, int* kf_parent, int* kf_cnt) {
-    const int t = threadIdx.x;
-    if (t < kMapNeigh) kf_neigh[slot * kMapNeigh + t] = -1;
-    if (t == 0) {
-        kf_key[slot] = key;
-        kf_bad[slot] = 0;
-        kf_stamp[slot] = 0;
-        ch_off[slot] = 0;
-        ch_n[slot] = 0;
-        kf_parent[slot] = -1;
-        kf_cnt[slot] = 0;
-    }
+// A new KeyFrame's key; everything else of it is at the columns' defaults (kMapColumns).
+__global__ void map_kf_key_kernel(int slot, unsigned long long key, unsigned long long* kf_key) {
+    if (threadIdx.x == 0) kf_key[slot] = key;
 }
 
 __global__ void map_neigh_kernel(int slot, MapNeighList l, int* kf_neigh) {
@@ -451,245 +365,6 @@ __global__ void map_neigh_kernel(int slot, MapNeighList l, int* kf_neigh) {
 using namespace orbfe;
 
 namespace {
-
-// Rows of ints in one device pool.  A row that outgrows its region moves to a new one of twice
-// the size at the pool's end (the old region is not reused: the pool holds at most twice what
-// the rows do); the pool itself doubles.
-struct MapRagged {
-    DevBuf pool, off, len;
-    std::vector<long long> h_off;
-    std::vector<int> h_n, h_cap;
-    long long used = 0, alloc = 0;
-    void reset() {
-        h_off.clear();
-        h_n.clear();
-        h_cap.clear();
-        used = 0;
-    }
-};
-
-struct MapRowWrite {
-    int row, first, n;   // n ints at offset `first` of the row
-    int new_len;         // the row's length afterwards, or -1: unchanged
-    const int* data;
-};
-
-// The covisibility graph of the handle (orbfe_covis.hip): made by its first call there.
-struct MapCovis;
-void map_covis_free(MapCovis* c);
-void map_covis_reset(MapCovis* c);
-
-// What the culling calls add to the handle (orbfe_cull.hip): made by their first call.
-struct MapCull;
-void map_cull_free(MapCull* c);
-void map_cull_reset(MapCull* c);
-
-// nObs of the listed points changed by the listed amounts; whether mvuRight[idx] of a keyframe is
-// >= 0 as orbfe_map_set_keyframe_features left it (orbfe_cull.hip).
-int map_cull_add_nobs(orbfe_map* m, const std::vector<int>& mp_slots, const std::vector<int>& amounts);
-bool map_cull_right(const orbfe_map* m, int kf, int idx);
-
-}  // namespace
-
-struct orbfe_map {
-    int device = 0;
-    int n_kf = 0, n_mp = 0, kf_alloc = 0, mp_alloc = 0;
-    int max_slots = 0;  // the longest mvpMapPoints: the point kernels' grid
-    std::unordered_map<uint64_t, int> by_key;
-    std::vector<uint64_t> h_key;
-    std::vector<std::vector<int>> h_obs;  // sorted
-    std::vector<std::vector<int>> h_idx;  // mObservations[pKF] of h_obs' entries, or -1
-    long long n_unknown = 0;              // entries of h_idx that are -1
-    std::vector<int> h_local;             // the list as of the last query / set_local_keyframes
-    int h_ref = -1, h_n_local_mp = 0;
-    MapRagged kf_mp, kf_ch, mp_obs;
-    MapRagged mp_idx;  // the feature indices, row for row beside mp_obs
-    DevBuf kf_key, kf_bad, kf_stamp, kf_neigh, kf_parent, kf_cnt, mp_bad, mp_stamp, first_pos, touched,
-        ctl, local_kf, local_mp, blk, stage_i, stage_items, stage_v, frame;
-    hipStream_t own = nullptr, stream = nullptr;
-    int* pin = nullptr;
-    int* pin_dev = nullptr;
-    MapCovis* covis = nullptr;
-    MapCull* cull = nullptr;
-
-    MapDev dev() const {
-        MapDev d;
-        d.n_kf = n_kf;
-        d.n_mp = n_mp;
-        d.kf_key = kf_key.as<unsigned long long>();
-        d.kf_bad = kf_bad.as<uint8_t>();
-        d.kf_stamp = kf_stamp.as<unsigned long long>();
-        d.kf_mp_off = kf_mp.off.as<long long>();
-        d.kf_mp_n = kf_mp.len.as<int>();
-        d.kf_mp = kf_mp.pool.as<int>();
-        d.kf_neigh = kf_neigh.as<int>();
-        d.kf_ch_off = kf_ch.off.as<long long>();
-        d.kf_ch_n = kf_ch.len.as<int>();
-        d.kf_ch = kf_ch.pool.as<int>();
-        d.kf_parent = kf_parent.as<int>();
-        d.mp_bad = mp_bad.as<uint8_t>();
-        d.mp_stamp = mp_stamp.as<unsigned long long>();
-        d.mp_obs_off = mp_obs.off.as<long long>();
-        d.mp_obs_n = mp_obs.len.as<int>();
-        d.mp_obs = mp_obs.pool.as<int>();
-        d.kf_cnt = kf_cnt.as<int>();
-        d.touched = touched.as<int>();
-        d.first_pos = first_pos.as<int>();
-        d.ctl = ctl.as<int>();
-        d.local_kf = local_kf.as<int>();
-        d.local_mp = local_mp.as<int>();
-        d.blk = blk.as<int>();
-        return d;
-    }
-    bool kf_ok(int s) const { return s >= 0 && s < n_kf; }
-    bool mp_ok(int s) const { return s >= 0 && s < n_mp; }
-    ~orbfe_map() {
-        map_covis_free(covis);
-        map_cull_free(cull);
-        if (pin) hipHostFree(pin);
-        if (own) hipStreamDestroy(own);
-    }
-};
-
-namespace {
-
-constexpr size_t kMapPinBytes = sizeof(int) * (kResList + kMapListCap);
-
-// `b` regrown to n elements of `per` bytes: the first `keep` survive, the rest is filled with `fill`.
-int map_regrow(orbfe_map* m, DevBuf& b, size_t per, size_t keep, size_t n, int fill = 0) {
-    DevBuf nb;
-    int st = nb.ensure(per * n);
-    if (st) return st;
-    ORBFE_HIP(hipMemsetAsync(nb.p, fill, per * n, m->stream));
-    if (b.p && keep) ORBFE_HIP(hipMemcpyAsync(nb.p, b.p, per * keep, hipMemcpyDeviceToDevice, m->stream));
-    ORBFE_HIP(hipStreamSynchronize(m->stream));
-    b = std::move(nb);
-    return ORBFE_OK;
-}
-
-int map_grow_kf(orbfe_map* m, int n) {
-    int st;
-    const size_t k = (size_t)m->n_kf;
-    if ((st = map_regrow(m, m->kf_key, 8, k, n))) return st;
-    if ((st = map_regrow(m, m->kf_bad, 1, k, n))) return st;
-    if ((st = map_regrow(m, m->kf_stamp, 8, k, n))) return st;
-    if ((st = map_regrow(m, m->kf_neigh, sizeof(int) * kMapNeigh, k, n, 0xff))) return st;
-    if ((st = map_regrow(m, m->kf_parent, sizeof(int), k, n, 0xff))) return st;
-    if ((st = map_regrow(m, m->kf_cnt, sizeof(int), 0, n))) return st;  // all 0 between queries
-    if ((st = map_regrow(m, m->kf_mp.off, 8, k, n))) return st;
-    if ((st = map_regrow(m, m->kf_mp.len, sizeof(int), k, n))) return st;
-    if ((st = map_regrow(m, m->kf_ch.off, 8, k, n))) return st;
-    if ((st = map_regrow(m, m->kf_ch.len, sizeof(int), k, n))) return st;
-    m->kf_alloc = n;
-    return ORBFE_OK;
-}
-
-int map_grow_mp(orbfe_map* m, int n) {
-    int st;
-    const size_t k = (size_t)m->n_mp;
-    if ((st = map_regrow(m, m->mp_bad, 1, k, n))) return st;
-    if ((st = map_regrow(m, m->mp_stamp, 8, k, n))) return st;
-    if ((st = map_regrow(m, m->mp_obs.off, 8, k, n))) return st;
-    if ((st = map_regrow(m, m->mp_obs.len, sizeof(int), k, n))) return st;
-    if ((st = map_regrow(m, m->mp_idx.off, 8, k, n))) return st;
-    if ((st = map_regrow(m, m->mp_idx.len, sizeof(int), k, n))) return st;
-    if ((st = map_regrow(m, m->first_pos, sizeof(int), 0, n, 0x7f))) return st;  // kMapNoPos
-    if ((st = map_regrow(m, m->local_mp, sizeof(int), k, n))) return st;
-    m->mp_alloc = n;
-    return ORBFE_OK;
-}
-
-// The row writes `w` into table `r`: regions, the pool's growth, one upload, one scatter launch.
-int map_put_rows(orbfe_map* m, MapRagged& r, const std::vector<MapRowWrite>& w) {
-    if (w.empty()) return ORBFE_OK;
-    std::vector<MapRowItem> items(w.size());
-    std::vector<int> data;
-    long long used = r.used;
-    for (size_t i = 0; i < w.size(); ++i) {
-        const MapRowWrite& x = w[i];
-        if ((size_t)x.row >= r.h_off.size()) {
-            r.h_off.resize((size_t)x.row + 1, 0);
-            r.h_n.resize((size_t)x.row + 1, 0);
-            r.h_cap.resize((size_t)x.row + 1, 0);
-        }
-        const int len = x.new_len >= 0 ? x.new_len : r.h_n[x.row];
-        if (len > r.h_cap[x.row]) {  // whole-row writes only: nothing of the old region survives
-            int cap = 4;
-            while (cap < len) cap <<= 1;
-            r.h_off[x.row] = used;
-            r.h_cap[x.row] = cap;
-            used += cap;
-        }
-        r.h_n[x.row] = len;
-        items[i].dst = r.h_off[x.row] + x.first;
-        items[i].src = (int)data.size();
-        items[i].n = x.n;
-        items[i].row = x.row;
-        items[i].new_off = r.h_off[x.row];
-        items[i].new_n = len;
-        data.insert(data.end(), x.data, x.data + x.n);
-    }
-    int st;
-    if (used > r.alloc) {
-        long long n = std::max<long long>(2 * r.alloc, 4096);
-        while (n < used) n *= 2;
-        if ((st = map_regrow(m, r.pool, sizeof(int), (size_t)r.used, (size_t)n))) return st;
-        r.alloc = n;
-    }
-    r.used = used;
-    if ((st = m->stage_i.ensure(sizeof(int) * std::max<size_t>(data.size(), 1)))) return st;
-    if ((st = m->stage_items.ensure(sizeof(MapRowItem) * items.size()))) return st;
-    if (!data.empty())
-        ORBFE_HIP(hipMemcpyAsync(m->stage_i.p, data.data(), sizeof(int) * data.size(),
-                                 hipMemcpyHostToDevice, m->stream));
-    ORBFE_HIP(hipMemcpyAsync(m->stage_items.p, items.data(), sizeof(MapRowItem) * items.size(),
-                             hipMemcpyHostToDevice, m->stream));
-    const int n_items = (int)items.size();
-    hipLaunchKernelGGL(map_rows_kernel, dim3((n_items + 3) / 4), dim3(256), 0, m->stream, n_items,
-                       m->stage_items.as<MapRowItem>(), m->stage_i.as<int>(), r.pool.as<int>(),
-                       r.off.as<long long>(), r.len.as<int>());
-    ORBFE_HIP(hipGetLastError());
-    ORBFE_HIP(hipStreamSynchronize(m->stream));  // the staging vectors are this call's
-    return ORBFE_OK;
-}
-
-// dst[slots[i]] = vals[i] (or `value`) for n slots, all in range (checked by the caller).
-template <class T>
-int map_set(orbfe_map* m, int n, const int32_t* slots, const T* vals, T value, T* dst) {
-    if (!n) return ORBFE_OK;
-    int st;
-    if ((st = m->stage_i.ensure(sizeof(int) * (size_t)n))) return st;
-    ORBFE_HIP(hipMemcpyAsync(m->stage_i.p, slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, m->stream));
-    if (vals) {
-        if ((st = m->stage_v.ensure(sizeof(T) * (size_t)n))) return st;
-        ORBFE_HIP(hipMemcpyAsync(m->stage_v.p, vals, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, m->stream));
-    }
-    hipLaunchKernelGGL(map_set_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, m->stream, n,
-                       m->stage_i.as<int>(), vals ? m->stage_v.as<T>() : nullptr, value, dst);
-    ORBFE_HIP(hipGetLastError());
-    ORBFE_HIP(hipStreamSynchronize(m->stream));
-    return ORBFE_OK;
-}
-
-template <class F>
-int map_guarded(orbfe_map* m, F&& f) {
-    try {
-        DeviceGuard dg(m->device);
-        return f();
-    } catch (const std::bad_alloc&) {
-        return ORBFE_ERR_NOMEM;
-    } catch (...) {
-        return ORBFE_ERR_HIP;
-    }
-}
-
-int map_reset_ctl(orbfe_map* m) {
-    int h[kCtlWords] = {0};
-    h[kCtlRef] = -1;
-    ORBFE_HIP(hipMemcpyAsync(m->ctl.p, h, sizeof h, hipMemcpyHostToDevice, m->stream));
-    ORBFE_HIP(hipStreamSynchronize(m->stream));
-    return ORBFE_OK;
-}
 
 // The five launches of one query over the device array d_frame_mp; waits on the done word.
 int map_query(orbfe_map* m, uint64_t frame_id, int n, int32_t* d_frame_mp) {
@@ -727,88 +402,6 @@ int map_query(orbfe_map* m, uint64_t frame_id, int n, int32_t* d_frame_mp) {
 
 extern "C" {
 
-orbfe_map* orbfe_map_create(int device, int kf_hint, int mp_hint, int* status) {
-    int st = kf_hint < 0 || mp_hint < 0 ? ORBFE_ERR_ARG : check_device(device);
-    orbfe_map* m = nullptr;
-    if (st == ORBFE_OK) {
-        try {
-            DeviceGuard dg(device);
-            m = new orbfe_map();
-            m->device = device;
-            if (hipStreamCreateWithFlags(&m->own, hipStreamNonBlocking) != hipSuccess) st = ORBFE_ERR_HIP;
-            m->stream = m->own;
-            void* p = nullptr;
-            void* dp = nullptr;
-            if (st == ORBFE_OK && (hipHostMalloc(&p, kMapPinBytes, hipHostMallocDefault) != hipSuccess ||
-                                   hipHostGetDevicePointer(&dp, p, 0) != hipSuccess))
-                st = ORBFE_ERR_NOMEM;
-            m->pin = static_cast<int*>(p);
-            m->pin_dev = static_cast<int*>(dp);
-            if (st == ORBFE_OK) st = m->ctl.ensure(sizeof(int) * kCtlWords);
-            if (st == ORBFE_OK) st = m->touched.ensure(sizeof(int) * kMapMaxVoted);
-            if (st == ORBFE_OK) st = m->local_kf.ensure(sizeof(int) * kMapListCap);
-            if (st == ORBFE_OK) st = m->blk.ensure(sizeof(int) * (size_t)kMapListCap * kMapChunks);
-            if (st == ORBFE_OK) st = map_reset_ctl(m);
-            if (st == ORBFE_OK) st = map_grow_kf(m, std::max(kf_hint, 16));
-            if (st == ORBFE_OK) st = map_grow_mp(m, std::max(mp_hint, 1024));
-        } catch (const std::bad_alloc&) {
-            st = ORBFE_ERR_NOMEM;
-        } catch (...) {
-            st = ORBFE_ERR_HIP;
-        }
-    }
-    if (st != ORBFE_OK && m) {
-        delete m;
-        m = nullptr;
-    }
-    if (status) *status = st;
-    return m;
-}
-
-void orbfe_map_destroy(orbfe_map* m) {
-    if (!m) return;
-    DeviceGuard dg(m->device);
-    if (m->stream) hipStreamSynchronize(m->stream);
-    delete m;
-}
-
-int orbfe_map_set_stream(orbfe_map* m, void* hip_stream) {
-    if (!m) return ORBFE_ERR_ARG;
-    DeviceGuard dg(m->device);
-    hipStreamSynchronize(m->stream);
-    m->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : m->own;
-    return ORBFE_OK;
-}
-
-int orbfe_map_clear(orbfe_map* m) {
-    if (!m) return ORBFE_ERR_ARG;
-    return map_guarded(m, [&]() {
-        m->n_kf = m->n_mp = m->max_slots = 0;
-        m->by_key.clear();
-        m->h_key.clear();
-        m->h_obs.clear();
-        m->h_idx.clear();
-        m->n_unknown = 0;
-        m->h_local.clear();
-        m->h_ref = -1;
-        m->h_n_local_mp = 0;
-        m->kf_mp.reset();
-        m->kf_ch.reset();
-        m->mp_obs.reset();
-        m->mp_idx.reset();
-        map_covis_reset(m->covis);
-        map_cull_reset(m->cull);
-        return map_reset_ctl(m);
-    });
-}
-
-int orbfe_map_size(const orbfe_map* m, int32_t* n_keyframes, int32_t* n_points) {
-    if (!m) return ORBFE_ERR_ARG;
-    if (n_keyframes) *n_keyframes = m->n_kf;
-    if (n_points) *n_points = m->n_mp;
-    return ORBFE_OK;
-}
-
 int orbfe_map_add_keyframe(orbfe_map* m, uint64_t order_key, int n_slots, const int32_t* mp_slots,
                            int32_t* slot) {
     if (!m || !slot || n_slots < 0 || n_slots > kMapMaxSlots || m->by_key.count(order_key))
@@ -818,17 +411,14 @@ int orbfe_map_add_keyframe(orbfe_map* m, uint64_t order_key, int n_slots, const 
             if (mp_slots[i] != -1 && !m->mp_ok(mp_slots[i])) return ORBFE_ERR_ARG;
     return map_guarded(m, [&]() {
         int st;
-        if (m->n_kf == m->kf_alloc && (st = map_grow_kf(m, 2 * m->kf_alloc))) return st;
         const int s = m->n_kf;
-        hipLaunchKernelGGL(map_kf_init_kernel, dim3(1), dim3(64), 0, m->stream, s,
-                           (unsigned long long)order_key, m->kf_key.as<unsigned long long>(),
-                           m->kf_bad.as<uint8_t>(), m->kf_stamp.as<unsigned long long>(),
-                           m->kf_neigh.as<int>(), m->kf_ch.off.as<long long>(), m->kf_ch.len.as<int>(),
-                           m->kf_parent.as<int>(), m->kf_cnt.as<int>());
+        if ((st = store_cover(m, kGroupCoreKf, s + 1, 16))) return st;
+        hipLaunchKernelGGL(map_kf_key_kernel, dim3(1), dim3(64), 0, m->stream, s,
+                           (unsigned long long)order_key, m->at<unsigned long long>(kColKfKey));
         ORBFE_HIP(hipGetLastError());
         std::vector<int> none;
         if (!mp_slots) none.assign((size_t)n_slots, -1);
-        if ((st = map_put_rows(m, m->kf_mp, {{s, 0, n_slots, n_slots, mp_slots ? mp_slots : none.data()}})))
+        if ((st = map_put_kf_mp(m, {{s, 0, n_slots, n_slots, mp_slots ? mp_slots : none.data(), nullptr}})))
             return st;
         m->h_key.push_back(order_key);
         m->by_key[order_key] = s;
@@ -841,19 +431,19 @@ int orbfe_map_add_keyframe(orbfe_map* m, uint64_t order_key, int n_slots, const 
 
 int orbfe_map_set_keyframe_points(orbfe_map* m, int slot, int first, int n, const int32_t* mp_slots) {
     if (!m || !m->kf_ok(slot) || first < 0 || n < 0 || (n && !mp_slots) ||
-        (long long)first + n > m->kf_mp.h_n[slot])
+        (long long)first + n > m->kf_mp.len[slot])
         return ORBFE_ERR_ARG;
     for (int i = 0; i < n; ++i)
         if (mp_slots[i] != -1 && !m->mp_ok(mp_slots[i])) return ORBFE_ERR_ARG;
     if (!n) return ORBFE_OK;
-    return map_guarded(m, [&]() { return map_put_rows(m, m->kf_mp, {{slot, first, n, -1, mp_slots}}); });
+    return map_guarded(m, [&]() { return map_put_kf_mp(m, {{slot, first, n, -1, mp_slots, nullptr}}); });
 }
 
 int orbfe_map_set_keyframe_bad(orbfe_map* m, int slot, int bad) {
     if (!m || !m->kf_ok(slot)) return ORBFE_ERR_ARG;
     return map_guarded(m, [&]() {
         const int32_t s = slot;
-        return map_set<uint8_t>(m, 1, &s, nullptr, bad ? 1 : 0, m->kf_bad.as<uint8_t>());
+        return store_set<uint8_t>(m, m->at<uint8_t>(kColKfBad), 1, &s, nullptr, bad ? 1 : 0);
     });
 }
 
@@ -865,7 +455,7 @@ int orbfe_map_set_covisibility(orbfe_map* m, int slot, int n, const int32_t* nei
         if (l.v[j] != -1 && !m->kf_ok(l.v[j])) return ORBFE_ERR_ARG;
     }
     return map_guarded(m, [&]() {
-        hipLaunchKernelGGL(map_neigh_kernel, dim3(1), dim3(64), 0, m->stream, slot, l, m->kf_neigh.as<int>());
+        hipLaunchKernelGGL(map_neigh_kernel, dim3(1), dim3(64), 0, m->stream, slot, l, m->at<int>(kColKfNeigh));
         ORBFE_HIP(hipGetLastError());
         return (int)ORBFE_OK;
     });
@@ -880,7 +470,7 @@ int orbfe_map_set_children(orbfe_map* m, int slot, int n, const int32_t* child_s
         std::vector<int> c(child_slots, child_slots + n);
         std::sort(c.begin(), c.end(), [&](int x, int y) { return m->h_key[x] < m->h_key[y]; });
         c.erase(std::unique(c.begin(), c.end()), c.end());
-        return map_put_rows(m, m->kf_ch, {{slot, 0, (int)c.size(), (int)c.size(), c.data()}});
+        return map_put_kf_ch(m, {{slot, 0, (int)c.size(), (int)c.size(), c.data(), nullptr}});
     });
 }
 
@@ -888,7 +478,7 @@ int orbfe_map_set_parent(orbfe_map* m, int slot, int parent) {
     if (!m || !m->kf_ok(slot) || (parent != -1 && !m->kf_ok(parent))) return ORBFE_ERR_ARG;
     return map_guarded(m, [&]() {
         const int32_t s = slot;
-        return map_set<int>(m, 1, &s, nullptr, parent, m->kf_parent.as<int>());
+        return store_set<int>(m, m->at<int>(kColKfParent), 1, &s, nullptr, parent);
     });
 }
 
@@ -896,34 +486,13 @@ int orbfe_map_add_points(orbfe_map* m, int n, int32_t* first_slot) {
     if (!m || n < 0 || !first_slot || (long long)m->n_mp + n > 0x7fffffff) return ORBFE_ERR_ARG;
     return map_guarded(m, [&]() {
         int st;
-        if (m->n_mp + n > m->mp_alloc) {
-            int a = std::max(2 * m->mp_alloc, 1024);
-            while (a < m->n_mp + n) a *= 2;
-            if ((st = map_grow_mp(m, a))) return st;
-        }
-        if (n) {  // a new MapPoint: not bad, stamp 0 (MapPoint.cc:36, :55), no observations
-            const size_t o = (size_t)m->n_mp;
-            ORBFE_HIP(hipMemsetAsync(m->mp_bad.as<uint8_t>() + o, 0, (size_t)n, m->stream));
-            ORBFE_HIP(hipMemsetAsync(m->mp_stamp.as<unsigned long long>() + o, 0, 8 * (size_t)n, m->stream));
-            ORBFE_HIP(hipMemsetAsync(m->mp_obs.len.as<int>() + o, 0, sizeof(int) * (size_t)n, m->stream));
-            ORBFE_HIP(hipMemsetAsync(m->mp_idx.len.as<int>() + o, 0, sizeof(int) * (size_t)n, m->stream));
-            ORBFE_HIP(hipStreamSynchronize(m->stream));
-        }
+        // a new MapPoint is at the columns' defaults (kMapColumns)
+        if ((st = store_cover(m, kGroupCoreMp, m->n_mp + n, 1024))) return st;
         *first_slot = m->n_mp;
         m->n_mp += n;
         m->h_obs.resize((size_t)m->n_mp);
         m->h_idx.resize((size_t)m->n_mp);
-        for (MapRagged* r : {&m->mp_obs, &m->mp_idx})
-            if (r->h_cap.size() < (size_t)m->n_mp) {
-                r->h_off.resize((size_t)m->n_mp, 0);
-                r->h_n.resize((size_t)m->n_mp, 0);
-                r->h_cap.resize((size_t)m->n_mp, 0);
-            }
-        for (int i = *first_slot; i < m->n_mp; ++i) {
-            m->h_obs[i].clear();
-            m->h_idx[i].clear();
-            m->mp_obs.h_n[i] = m->mp_idx.h_n[i] = 0;
-        }
+        m->mp_obs.cover((size_t)m->n_mp);
         return (int)ORBFE_OK;
     });
 }
@@ -933,7 +502,7 @@ int orbfe_map_set_points_bad(orbfe_map* m, int n, const int32_t* mp_slots, int b
     for (int i = 0; i < n; ++i)
         if (!m->mp_ok(mp_slots[i])) return ORBFE_ERR_ARG;
     return map_guarded(m, [&]() {
-        return map_set<uint8_t>(m, n, mp_slots, nullptr, bad ? 1 : 0, m->mp_bad.as<uint8_t>());
+        return store_set<uint8_t>(m, m->at<uint8_t>(kColMpBad), n, mp_slots, nullptr, bad ? 1 : 0);
     });
 }
 
@@ -944,7 +513,7 @@ static int map_change_observations(orbfe_map* m, int n, const int32_t* mp_slots,
     if (!m || n < 0 || (n && (!mp_slots || !kf_slots))) return ORBFE_ERR_ARG;
     for (int i = 0; i < n; ++i) {
         if (!m->mp_ok(mp_slots[i]) || !m->kf_ok(kf_slots[i])) return ORBFE_ERR_ARG;
-        if (idx && (idx[i] < 0 || idx[i] >= m->kf_mp.h_n[kf_slots[i]])) return ORBFE_ERR_ARG;
+        if (idx && (idx[i] < 0 || idx[i] >= m->kf_mp.len[kf_slots[i]])) return ORBFE_ERR_ARG;
     }
     return map_guarded(m, [&]() {
         std::vector<int> dirty, who, amount;
@@ -956,7 +525,7 @@ static int map_change_observations(orbfe_map* m, int n, const int32_t* mp_slots,
             if (add == has) continue;  // set semantics (MapPoint.cc:342-343, :357)
             const auto xi = x.begin() + (it - o.begin());
             const int ix = add ? (idx ? idx[i] : -1) : *xi;
-            const int by = ix >= 0 && map_cull_right(m, kf_slots[i], ix) ? 2 : 1;  // :346-349, :360-363
+            const int by = ix >= 0 && map_has_right(m, kf_slots[i], ix) ? 2 : 1;  // :346-349, :360-363
             if (ix < 0) m->n_unknown += add ? 1 : -1;
             if (add) {
                 o.insert(it, kf_slots[i]);
@@ -971,16 +540,15 @@ static int map_change_observations(orbfe_map* m, int n, const int32_t* mp_slots,
         }
         std::sort(dirty.begin(), dirty.end());
         dirty.erase(std::unique(dirty.begin(), dirty.end()), dirty.end());
-        std::vector<MapRowWrite> w, wx;
+        std::vector<MapRowWrite> w;
         for (int p : dirty) {
             const std::vector<int>& o = m->h_obs[p];
-            w.push_back({p, 0, (int)o.size(), (int)o.size(), o.data()});
-            wx.push_back({p, 0, (int)o.size(), (int)o.size(), m->h_idx[p].data()});
+            w.push_back({p, 0, (int)o.size(), (int)o.size(), o.data(), m->h_idx[p].data()});
         }
         int st;
-        if ((st = map_put_rows(m, m->mp_obs, w))) return st;
-        if ((st = map_put_rows(m, m->mp_idx, wx))) return st;
-        return map_cull_add_nobs(m, who, amount);
+        if ((st = map_put_mp_obs(m, w))) return st;
+        if ((st = cull_ready(m))) return st;
+        return store_add(m, m->at<int>(kColNobs), (int)who.size(), who.data(), amount.data());
     });
 }
 
@@ -1005,9 +573,8 @@ int orbfe_map_set_stamps(orbfe_map* m, int kind, int n, const int32_t* slots, co
     for (int i = 0; i < n; ++i)
         if (kind == ORBFE_MAP_KEYFRAMES ? !m->kf_ok(slots[i]) : !m->mp_ok(slots[i])) return ORBFE_ERR_ARG;
     return map_guarded(m, [&]() {
-        DevBuf& b = kind == ORBFE_MAP_KEYFRAMES ? m->kf_stamp : m->mp_stamp;
-        return map_set<unsigned long long>(m, n, slots, reinterpret_cast<const unsigned long long*>(stamps),
-                                           0ull, b.as<unsigned long long>());
+        return store_set<unsigned long long>(m, m->at<unsigned long long>(kind == ORBFE_MAP_KEYFRAMES ? kColKfStamp : kColMpStamp),
+                                             n, slots, reinterpret_cast<const unsigned long long*>(stamps));
     });
 }
 
@@ -1019,18 +586,8 @@ int orbfe_map_get_stamps(orbfe_map* m, int kind, int n, const int32_t* slots, ui
         if (kind == ORBFE_MAP_KEYFRAMES ? !m->kf_ok(slots[i]) : !m->mp_ok(slots[i])) return ORBFE_ERR_ARG;
     if (!n) return ORBFE_OK;
     return map_guarded(m, [&]() {
-        int st;
-        DevBuf& b = kind == ORBFE_MAP_KEYFRAMES ? m->kf_stamp : m->mp_stamp;
-        if ((st = m->stage_i.ensure(sizeof(int) * (size_t)n))) return st;
-        if ((st = m->stage_v.ensure(8 * (size_t)n))) return st;
-        ORBFE_HIP(hipMemcpyAsync(m->stage_i.p, slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, m->stream));
-        hipLaunchKernelGGL(map_get_kernel<unsigned long long>, dim3((n + 255) / 256), dim3(256), 0,
-                           m->stream, n, m->stage_i.as<int>(), b.as<unsigned long long>(),
-                           m->stage_v.as<unsigned long long>());
-        ORBFE_HIP(hipGetLastError());
-        ORBFE_HIP(hipMemcpyAsync(stamps, m->stage_v.p, 8 * (size_t)n, hipMemcpyDeviceToHost, m->stream));
-        ORBFE_HIP(hipStreamSynchronize(m->stream));
-        return (int)ORBFE_OK;
+        return store_get<unsigned long long>(m, m->at<unsigned long long>(kind == ORBFE_MAP_KEYFRAMES ? kColKfStamp : kColMpStamp),
+                                             n, slots, reinterpret_cast<unsigned long long*>(stamps));
     });
 }
 
@@ -1088,20 +645,21 @@ int orbfe_map_update_local(orbfe_map* m, uint64_t frame_id, int n, int32_t* fram
     if (kf_cap < 0 || (kf_cap && !local_kf) || !n_local_kf || !ref_kf || !n_local_mp) return ORBFE_ERR_ARG;
     return map_guarded(m, [&]() {
         int st;
-        if ((st = m->frame.ensure(sizeof(int) * std::max<size_t>((size_t)n, 1)))) return st;
+        int* d_frame;  // the holders: the query borrows no staging
+        if ((st = store_borrow(m, kStageSlots, (size_t)n, d_frame))) return st;
         if (n)
-            ORBFE_HIP(hipMemcpyAsync(m->frame.p, frame_mp, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, m->stream));
-        st = orbfe_map_update_local_device(m, frame_id, n, m->frame.as<int32_t>(), local_kf, kf_cap,
+            ORBFE_HIP(hipMemcpyAsync(d_frame, frame_mp, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+        st = orbfe_map_update_local_device(m, frame_id, n, d_frame, local_kf, kf_cap,
                                            n_local_kf, ref_kf, n_local_mp);
         if (st != ORBFE_OK && st != ORBFE_ERR_CAPACITY) return st;
         if (n) {  // the NULLed bad points (:1508), also next to ORBFE_ERR_CAPACITY
-            ORBFE_HIP(hipMemcpyAsync(frame_mp, m->frame.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+            ORBFE_HIP(hipMemcpyAsync(frame_mp, d_frame, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
             ORBFE_HIP(hipStreamSynchronize(m->stream));
         }
         if (st != ORBFE_OK) return st;
         if (*n_local_mp > mp_cap) return (int)ORBFE_ERR_CAPACITY;
         if (*n_local_mp) {
-            ORBFE_HIP(hipMemcpyAsync(local_mp, m->local_mp.p, sizeof(int) * (size_t)*n_local_mp,
+            ORBFE_HIP(hipMemcpyAsync(local_mp, m->at<int>(kColLocalMp), sizeof(int) * (size_t)*n_local_mp,
                                      hipMemcpyDeviceToHost, m->stream));
             ORBFE_HIP(hipStreamSynchronize(m->stream));
         }
@@ -1111,7 +669,7 @@ int orbfe_map_update_local(orbfe_map* m, uint64_t frame_id, int n, int32_t* fram
 
 int orbfe_map_local_points_device(const orbfe_map* m, const int32_t** d_list, int32_t* n) {
     if (!m || !d_list || !n) return ORBFE_ERR_ARG;
-    *d_list = m->local_mp.as<int32_t>();
+    *d_list = m->at<int32_t>(kColLocalMp);
     *n = m->h_n_local_mp;
     return ORBFE_OK;
 }
@@ -1122,7 +680,7 @@ int orbfe_map_get_local_points(orbfe_map* m, int32_t* mp_slots, int cap, int32_t
     if (*n > cap) return ORBFE_ERR_CAPACITY;
     if (!*n) return ORBFE_OK;
     return map_guarded(m, [&]() {
-        ORBFE_HIP(hipMemcpyAsync(mp_slots, m->local_mp.p, sizeof(int) * (size_t)*n, hipMemcpyDeviceToHost, m->stream));
+        ORBFE_HIP(hipMemcpyAsync(mp_slots, m->at<int>(kColLocalMp), sizeof(int) * (size_t)*n, hipMemcpyDeviceToHost, m->stream));
         ORBFE_HIP(hipStreamSynchronize(m->stream));
         return (int)ORBFE_OK;
     });
@@ -1139,7 +697,7 @@ int orbfe_map_gather_points_device(orbfe_map* m, int n, const int32_t* d_list,
         ((uintptr_t)src->desc & 15) || ((uintptr_t)dst->desc & 15))
         return ORBFE_ERR_ARG;
     return map_guarded(m, [&]() {
-        MapGatherArgs a{n, m->n_mp, d_list, m->mp_bad.as<uint8_t>(), *src, *dst};
+        MapGatherArgs a{n, m->n_mp, d_list, m->at<uint8_t>(kColMpBad), *src, *dst};
         const long long threads = 4ll * n;
         hipLaunchKernelGGL(map_gather_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
                            m->stream, a);
