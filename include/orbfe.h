@@ -1271,7 +1271,8 @@ int orbfe_map_add_observations_idx(orbfe_map* m, int n, const int32_t* mp_slots,
                                    const int32_t* kf_slots, const int32_t* idx);
 /* MapPoint::EraseObservation(pKF) (:352-378): an absent pair is a no-op; else nObs goes down by 2
  * or 1 by the right flag at the stored index, the pair is erased and, if nObs <= 2, the point's
- * SetBadFlag runs (*went_bad = 1; may be NULL).  mpRefKF is not mirrored. */
+ * SetBadFlag runs (*went_bad = 1; may be NULL).  mpRefKF follows (:367-368; see the
+ * refresh section below). */
 int orbfe_map_erase_observation(orbfe_map* m, int mp_slot, int kf_slot, int32_t* went_bad);
 /* MapPoint::SetBadFlag (:392-409) of n points: the bad flag set, the observation row cleared (nObs
  * untouched) and EraseMapPointMatch(idx) on every former observer: entry idx of that keyframe's
@@ -1322,7 +1323,7 @@ int orbfe_map_get_bad_flags(orbfe_map* m, int kind, int n, const int32_t* slots,
  * LocalMapping::KeyFrameCulling (LocalMapping.cc:632-698) --------------------------------------
  * Per keyframe, more plain state: mbNotErase and mbToBeErased (KeyFrame.cc:1152-1186), both 0 for
  * a new keyframe.  mTcp, Map::EraseKeyFrame and KeyFrameDatabase::erase stay with the caller
- * (orbfe_kfdb_erase); mpRefKF of a point is not mirrored. */
+ * (orbfe_kfdb_erase); mpRefKF of a point follows each EraseObservation (the refresh section below). */
 
 #define ORBFE_MAP_BAD_NOTHING   0   /* *what of a SetBadFlag: mnId == 0, nothing changed          */
 #define ORBFE_MAP_BAD_DEFERRED  1   /* mbNotErase: mbToBeErased set, nothing else                 */
@@ -1380,6 +1381,101 @@ int orbfe_map_cull_keyframes(orbfe_map* m, int current_slot, int n, const int32_
                              int first_kf_slot, int monocular, int32_t* result, int result_cap,
                              int32_t* n_listed, int32_t* bad_points, int bad_cap, int32_t* n_bad,
                              int32_t* pairs, int pair_cap, int32_t* n_pairs);
+
+/* ---- MapPoint refresh: UpdateNormalAndDepth (MapPoint.cc:571-619), ComputeDistinctiveDescriptors
+ * (:483-548) and the map-point loop of LocalMapping::ProcessNewKeyFrame (LocalMapping.cc:140-161) --
+ * More plain state of an orbfe_map, each item with a setter and a getter, reset by
+ * orbfe_map_clear, carried over by growth, and made by the first call that needs it.  Per map:
+ * mvScaleFactors.  Per keyframe: GetCameraCenter() as three floats, (0, 0, 0) until set.  Per
+ * keyframe keypoint: its row of mDescriptors, 32 bytes, with a per-keyframe "set" flag.  Per point:
+ * mpRefKF as a keyframe slot or -1 (the default).
+ * mpRefKF follows every erase as MapPoint.cc:367-368 has it: when the observation of keyframe k is
+ * erased and the point's reference is k, the reference becomes mObservations.begin()->first, the
+ * remaining observer with the lowest order key, before the `nObs <= 2` decision (a point that goes
+ * bad on that erase has the new reference; SetBadFlag leaves it).  Where nothing remains the
+ * reference dereferences begin() of an empty map; the mirror stores -1.  This holds for
+ * orbfe_map_erase_observation, orbfe_map_erase_observations and the erases of a keyframe's
+ * SetBadFlag, from the first call that touches mpRefKF on.  From then on the two host erase calls
+ * read the references of the listed points back first (one more host wait per call) and write
+ * the changed ones after the rows (one more launch and wait, only when one changed). */
+
+#define ORBFE_MAP_REFRESH_NORMAL_DEPTH 1      /* bits of `what` and of result[]                    */
+#define ORBFE_MAP_REFRESH_DESCRIPTOR   2
+#define ORBFE_MAP_REFRESH_UNSUPPORTED  4      /* result[] only: the entry's normal and distances   */
+                                              /* were left alone (see ORBFE_ERR_UNSUPPORTED below) */
+#define ORBFE_MAP_MAX_REFRESH_OBS      1024   /* observers of one refreshed point                  */
+
+/* mvScaleFactors: 1 <= nlevels <= 128.  The getter: *nlevels = 0 while never set; > cap:
+ * ORBFE_ERR_CAPACITY. */
+int orbfe_map_set_scale_factors(orbfe_map* m, int nlevels, const float* scale);
+int orbfe_map_get_scale_factors(const orbfe_map* m, float* scale, int cap, int32_t* nlevels);
+/* GetCameraCenter() of n keyframes: ow holds 3 n floats. */
+int orbfe_map_set_keyframe_centers(orbfe_map* m, int n, const int32_t* kf_slots, const float* ow);
+int orbfe_map_get_keyframe_centers(orbfe_map* m, int n, const int32_t* kf_slots, float* ow);
+/* mDescriptors of a keyframe, n x 32 bytes; n must equal its slot count.  The device form copies
+ * from a device pointer (e.g. a row of the batch extraction's slab) on the handle's stream.  The
+ * getter: *is_set (may be NULL) = whether a set call has run; rows never set read zero; *n > cap:
+ * ORBFE_ERR_CAPACITY. */
+int orbfe_map_set_keyframe_descriptors(orbfe_map* m, int slot, int n, const uint8_t* desc);
+int orbfe_map_set_keyframe_descriptors_device(orbfe_map* m, int slot, int n, const uint8_t* d_desc);
+int orbfe_map_get_keyframe_descriptors(orbfe_map* m, int slot, int cap, uint8_t* desc, int32_t* n,
+                                       int32_t* is_set);
+/* mpRefKF of n points (distinct slots for the setter): a keyframe slot or -1. */
+int orbfe_map_set_point_ref_keyframes(orbfe_map* m, int n, const int32_t* mp_slots,
+                                      const int32_t* kf_slots);
+int orbfe_map_get_point_ref_keyframes(orbfe_map* m, int n, const int32_t* mp_slots, int32_t* kf_slots);
+
+/* UpdateNormalAndDepth (what & 1) and ComputeDistinctiveDescriptors (what & 2) of the n listed
+ * points.  `arrays` is the map-wide device struct orbfe_map_gather_points_device takes as src: xyz
+ * is read; normal, min_dist, max_dist and desc are written in place at the point's slot; the other
+ * members are ignored and may be NULL.  Entries of -1 and bad points are skipped (mbBad returns
+ * first in both functions); a point listed twice gets the same bytes twice.  result (may be NULL):
+ * per entry the bits of what was written, and ORBFE_MAP_REFRESH_UNSUPPORTED.
+ * Both functions walk the observations in pointer order (ascending order key, H26); that order
+ * picks the first descriptor on a median tie and is the order of the normal's float sum.
+ * The descriptor: observers whose keyframe is bad are left out (:506); none left: desc stays; the
+ * rest as orbfe_distinctive_descriptors, observer j's descriptor being row idx_j of its keyframe.
+ * The normal and the distances, literally: every observer counts, bad keyframes too;
+ *   d = Pos - Ow_i (float); a = (float)(1.0 / sqrt(sum (double)d_k d_k)); acc_k = acc_k + d_k a
+ * (product rounded before the add), sequentially in pointer order; pRefKF == NULL leaves all three
+ * outputs alone (:600), the normal too; else, pRefKF not tested for isBad,
+ *   dist = (float)sqrt(..) of Pos - Ow_ref; level = pRefKF's octave at observations[pRefKF]
+ * (operator[] on the copy: index 0 when pRefKF is not an observer; n is not affected);
+ *   max = dist scale[level]; min = max / scale[nlevels - 1]; normal_k = acc_k (float)(1.0 / n).
+ * ORBFE_ERR_ARG with nothing written: a list entry outside [-1, points); a live listed point with
+ * an observation of index -1; what & 1 without a scale table; what & 2 where a non-bad observer's
+ * keyframe has no descriptors set.  ORBFE_ERR_CAPACITY with nothing written: a live listed point
+ * with more than 1,024 observers (the reference puts float Distances[N][N] on the stack).
+ * ORBFE_ERR_UNSUPPORTED: a point whose reference octave is >= nlevels, or whose reference keyframe
+ * has no keypoint at the index read (the reference reads out of range): that point's normal and
+ * distances stay and its result carries ORBFE_MAP_REFRESH_UNSUPPORTED; everything else is written.
+ * Two launches of a wave per entry: a check launch that writes nothing but the error word, an
+ * apply launch that returns at once when that word holds a refusal.  The host waits once, on the
+ * done word; the host form's masks come back through pinned memory.  The device forms read the
+ * list, and write d_result, in device memory. */
+int orbfe_map_refresh_points(orbfe_map* m, int what, int n, const int32_t* mp_slots,
+                             const orbfe_map_point_arrays* arrays, uint8_t* result);
+int orbfe_map_refresh_points_device(orbfe_map* m, int what, int n, const int32_t* d_list,
+                                    const orbfe_map_point_arrays* arrays, uint8_t* d_result);
+/* The same over the keyframe's mvpMapPoints where it lies (the loop of LocalMapping.cc:518-530);
+ * nothing is uploaded.  *n_refreshed (may be NULL): the entries that hold a point that is not bad. */
+int orbfe_map_refresh_keyframe_points(orbfe_map* m, int kf_slot, int what,
+                                      const orbfe_map_point_arrays* arrays, int32_t* n_refreshed);
+/* The map-point loop of ProcessNewKeyFrame over index i of the keyframe's mvpMapPoints: NULL and
+ * bad entries are skipped; a point the keyframe does not observe yet gets AddObservation(kf, i)
+ * (nObs rises by 2 or 1 by the right flag) and both refreshes; any other is appended to `recent`
+ * (mlpRecentAddedMapPoints), in index order.  A point held at two indices is added at the lower
+ * one and listed in recent at the higher one.  recent_cap too small: ORBFE_ERR_CAPACITY with the
+ * true count and nothing changed.  ComputeBoW, UpdateConnections and Map::AddKeyFrame stay the
+ * separate calls they are.  What the refresh would refuse (see orbfe_map_refresh_points; also a
+ * keyframe whose descriptors were never set, bad or not, while it has a point to add) is found
+ * first: ORBFE_ERR_ARG or ORBFE_ERR_CAPACITY with nothing changed.  Four steps: one classifying
+ * launch (a thread per slot; one wait on the done word), one check launch over what is new (one
+ * wait), orbfe_map_add_observations_idx of it (two launches, two waits), then
+ * orbfe_map_refresh_points of the same (two launches, one wait), which can only return
+ * ORBFE_OK or ORBFE_ERR_UNSUPPORTED by then. */
+int orbfe_map_process_new_keyframe(orbfe_map* m, int kf_slot, const orbfe_map_point_arrays* arrays,
+                                   int32_t* recent, int recent_cap, int32_t* n_recent);
 
 /* ---- map-archive records of the extractor outputs (device side) ---------------------------
  * The bodies the reference's Boost map archive stores for the extractor's outputs, written

@@ -1090,6 +1090,79 @@ public:
     uint64_t MapPointStamp(uint64_t mpId) { return stamp(ORBFE_MAP_POINTS, mp(mpId)); }
     orbfe_map* handle() const { return m_; }
 
+    // ---- MapPoint refresh (MapPoint.cc:483-548, 571-619; LocalMapping.cc:140-161).  `arrays` are
+    // the caller's map-wide device arrays, indexed by MapPointSlot(mnId): xyz is read; normal,
+    // min_dist, max_dist and desc are written.
+    int32_t MapPointSlot(uint64_t mpId) const { return mp(mpId); }
+    // mvScaleFactors of the map's keyframes
+    void SetScaleFactors(const std::vector<float>& mvScaleFactors) {
+        check("orbfe_map_set_scale_factors",
+              orbfe_map_set_scale_factors(m_, (int)mvScaleFactors.size(), mvScaleFactors.data()));
+    }
+    // pKF->GetCameraCenter(), after every SetPose
+    void SetCameraCenter(uint64_t kfId, const float Ow[3]) {
+        const int32_t s = kf(kfId);
+        check("orbfe_map_set_keyframe_centers", orbfe_map_set_keyframe_centers(m_, 1, &s, Ow));
+    }
+    // pKF->mDescriptors: n rows of 32 bytes, n = the keyframe's keypoints; on the host or on the device
+    void SetDescriptors(uint64_t kfId, const uint8_t* mDescriptors, size_t n) {
+        check("orbfe_map_set_keyframe_descriptors",
+              orbfe_map_set_keyframe_descriptors(m_, kf(kfId), (int)n, mDescriptors));
+    }
+    void SetDescriptorsDevice(uint64_t kfId, const uint8_t* d_desc, size_t n) {
+        check("orbfe_map_set_keyframe_descriptors_device",
+              orbfe_map_set_keyframe_descriptors_device(m_, kf(kfId), (int)n, d_desc));
+    }
+    // mpRefKF (kNone: NULL); the handle keeps it through every EraseObservation from here on
+    void SetReferenceKeyFrame(uint64_t mpId, uint64_t kfId) {
+        const int32_t p = mp(mpId), k = kfId == kNone ? -1 : kf(kfId);
+        check("orbfe_map_set_point_ref_keyframes", orbfe_map_set_point_ref_keyframes(m_, 1, &p, &k));
+    }
+    uint64_t GetReferenceKeyFrame(uint64_t mpId) {
+        const int32_t p = mp(mpId);
+        int32_t k = -1;
+        check("orbfe_map_get_point_ref_keyframes", orbfe_map_get_point_ref_keyframes(m_, 1, &p, &k));
+        return k < 0 ? kNone : kf_id_[k];
+    }
+    // Both functions (by the bits of `what`) of the listed points -> per point the bits of what was
+    // written; ORBFE_MAP_REFRESH_UNSUPPORTED marks a point whose normal and distances were left
+    // alone because the reference reads out of range there (everything else was written).
+    std::vector<uint8_t> RefreshPoints(const std::vector<uint64_t>& mpIds, int what,
+                                       const orbfe_map_point_arrays& arrays) {
+        std::vector<int32_t> s(mpIds.size());
+        for (size_t i = 0; i < s.size(); ++i) s[i] = mp(mpIds[i], true);
+        std::vector<uint8_t> res(mpIds.size(), 0);
+        const int st = orbfe_map_refresh_points(m_, what, (int)s.size(), s.data(), &arrays, res.data());
+        if (st != ORBFE_OK && st != ORBFE_ERR_UNSUPPORTED) throw Error("orbfe_map_refresh_points", st);
+        return res;
+    }
+    // pMP->UpdateNormalAndDepth() / pMP->ComputeDistinctiveDescriptors(); the second alone is the
+    // last line of MapPoint::Replace (MapPoint.cc:453)
+    uint8_t UpdateNormalAndDepth(uint64_t mpId, const orbfe_map_point_arrays& arrays) {
+        return RefreshPoints({mpId}, ORBFE_MAP_REFRESH_NORMAL_DEPTH, arrays)[0];
+    }
+    uint8_t ComputeDistinctiveDescriptors(uint64_t mpId, const orbfe_map_point_arrays& arrays) {
+        return RefreshPoints({mpId}, ORBFE_MAP_REFRESH_DESCRIPTOR, arrays)[0];
+    }
+    // The loop at LocalMapping.cc:518-530 over pKF's mvpMapPoints where they lie -> the entries refreshed
+    int RefreshKeyFramePoints(uint64_t kfId, const orbfe_map_point_arrays& arrays,
+                              int what = ORBFE_MAP_REFRESH_NORMAL_DEPTH | ORBFE_MAP_REFRESH_DESCRIPTOR) {
+        int32_t n = 0;
+        const int st = orbfe_map_refresh_keyframe_points(m_, kf(kfId), what, &arrays, &n);
+        if (st != ORBFE_OK && st != ORBFE_ERR_UNSUPPORTED) throw Error("orbfe_map_refresh_keyframe_points", st);
+        return n;
+    }
+    // The map-point loop of LocalMapping::ProcessNewKeyFrame -> what it appends to mlpRecentAddedMapPoints
+    std::vector<uint64_t> ProcessNewKeyFrame(uint64_t kfId, const orbfe_map_point_arrays& arrays) {
+        std::vector<int32_t> rec(ORBFE_MAP_MAX_KF_SLOTS);
+        int32_t n = 0;
+        const int st = orbfe_map_process_new_keyframe(m_, kf(kfId), &arrays, rec.data(), (int)rec.size(), &n);
+        if (st != ORBFE_OK && st != ORBFE_ERR_UNSUPPORTED) throw Error("orbfe_map_process_new_keyframe", st);
+        std::vector<uint64_t> out;
+        for (int i = 0; i < n; ++i) out.push_back(mp_id_[rec[i]]);
+        return out;
+    }
+
 private:
     int32_t kf(uint64_t id) const {
         const auto it = kf_slot_.find(id);

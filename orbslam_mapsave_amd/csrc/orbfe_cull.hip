@@ -169,6 +169,34 @@ __device__ __forceinline__ int cull_ld(const int* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// mObservations.begin()->first once position p has left the row at oo: the remaining observer with
+// the lowest order key (rows are stored by slot), or -1 where the reference dereferences begin()
+// of an empty map.  The whole wave calls it; every lane returns the answer.
+__device__ __forceinline__ int cull_first_observer(const MapDev& d, long long oo, int no, int p, int lane) {
+    unsigned long long best = ~0ull;
+    int who = -1;
+    for (int j = lane; j < no; j += 64) {
+        if (j == p) continue;
+        const int kfj = d.mp_obs[oo + j];
+        if (kfj < 0 || kfj >= d.n_kf) continue;
+        const unsigned long long key = d.kf_key[kfj];
+        if (who < 0 || key < best) {
+            best = key;
+            who = kfj;
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const unsigned long long ob = __shfl_xor(best, s, 64);
+        const int ow = __shfl_xor(who, s, 64);
+        if (ow >= 0 && (who < 0 || ob < best)) {
+            best = ob;
+            who = ow;
+        }
+    }
+    return who;
+}
+
 // EraseObservation(this) of every entry of the keyframe's mvpMapPoints (:1191-1193), one wave per
 // slot, in three launches: marking (a point held at two indices is erased at the lower one, the
 // other finds nothing), checking (what each erase will do; a point that will go bad with an
@@ -231,6 +259,12 @@ __global__ __launch_bounds__(kCullBlock) void cull_kf_obs_kernel(CullKfObsArgs a
         }
         if (lane == 0) a.flag[i] = bad ? 2 : 1;
         return;
+    }
+    // mpRefKF follows the erase ahead of the nObs decision (MapPoint.cc:367-368); SetBadFlag below
+    // leaves it alone.  Every lane has read the column before lane 0 writes it.
+    if (cu.ref_kf && cu.ref_kf[mp] == a.kf) {
+        const int next = cull_first_observer(d, oo, no, p, lane);
+        if (lane == 0) cu.ref_kf[mp] = next;
     }
     if (fl == 2) {  // MapPoint::SetBadFlag of what is left (:392-409)
         for (int j = lane; j < no; j += 64) {
@@ -516,6 +550,7 @@ struct CullKfResult {
 int cull_kf_bad(orbfe_map* m, int slot, CullKfResult& out) {
     int st;
     if ((st = cull_ready(m))) return st;
+    if (ref_made(m) && (st = ref_ready_mp(m))) return st;  // mpRefKF follows the erases
     if ((st = store_side_pools(m))) return st;
     if ((st = cov_ready(m))) return st;
     const int ns = m->kf_mp.len[slot];

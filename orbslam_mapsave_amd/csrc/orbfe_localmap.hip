@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/orbfe.h"
@@ -516,6 +517,16 @@ static int map_change_observations(orbfe_map* m, int n, const int32_t* mp_slots,
         if (idx && (idx[i] < 0 || idx[i] >= m->kf_mp.len[kf_slots[i]])) return ORBFE_ERR_ARG;
     }
     return map_guarded(m, [&]() {
+        int st;
+        // mpRefKF of the points an erase may touch, once the column exists (MapPoint.cc:367-368)
+        std::unordered_map<int, int> ref;
+        std::vector<int> ref_changed;
+        if (!add && n && ref_made(m)) {
+            if ((st = ref_ready_mp(m))) return st;
+            std::vector<int> r((size_t)n);
+            if ((st = store_get<int>(m, m->at<int>(kColRefKf), n, mp_slots, r.data()))) return st;
+            for (int i = 0; i < n; ++i) ref[mp_slots[i]] = r[i];
+        }
         std::vector<int> dirty, who, amount;
         for (int i = 0; i < n; ++i) {
             std::vector<int>& o = m->h_obs[mp_slots[i]];
@@ -533,6 +544,15 @@ static int map_change_observations(orbfe_map* m, int n, const int32_t* mp_slots,
             } else {
                 o.erase(it);
                 x.erase(xi);
+                const auto r = ref.find(mp_slots[i]);
+                if (r != ref.end() && r->second == kf_slots[i]) {
+                    // mObservations.begin()->first: the lowest order key that remains, or -1
+                    int next = -1;
+                    for (int k : o)
+                        if (next < 0 || m->h_key[k] < m->h_key[next]) next = k;
+                    r->second = next;
+                    ref_changed.push_back(mp_slots[i]);
+                }
             }
             dirty.push_back(mp_slots[i]);
             who.push_back(mp_slots[i]);
@@ -545,8 +565,15 @@ static int map_change_observations(orbfe_map* m, int n, const int32_t* mp_slots,
             const std::vector<int>& o = m->h_obs[p];
             w.push_back({p, 0, (int)o.size(), (int)o.size(), o.data(), m->h_idx[p].data()});
         }
-        int st;
         if ((st = map_put_mp_obs(m, w))) return st;
+        if (!ref_changed.empty()) {
+            std::sort(ref_changed.begin(), ref_changed.end());
+            ref_changed.erase(std::unique(ref_changed.begin(), ref_changed.end()), ref_changed.end());
+            std::vector<int> v;
+            for (int p : ref_changed) v.push_back(ref[p]);
+            if ((st = store_set<int>(m, m->at<int>(kColRefKf), (int)v.size(), ref_changed.data(), v.data())))
+                return st;
+        }
         if ((st = cull_ready(m))) return st;
         return store_add(m, m->at<int>(kColNobs), (int)who.size(), who.data(), amount.data());
     });

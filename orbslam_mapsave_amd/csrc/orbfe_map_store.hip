@@ -1,8 +1,8 @@
 // orbfe_map_store.hip — the store under the device map: the orbfe_map handle, the columns of its
 // keyframes and points, its ragged row tables and their side pools, staging, the control and the
 // pinned block, and the scatter / gather / add helpers of the mutators ("The map's
-// store").  orbfe_localmap.hip, orbfe_covis.hip and orbfe_cull.hip hold their kernels, argument
-// structs and entry points on top of it; the arithmetic is in orbfe_map_plan.hpp.
+// store").  orbfe_localmap.hip, orbfe_covis.hip, orbfe_cull.hip and orbfe_refresh.hip hold their
+// kernels, argument structs and entry points on top of it; the arithmetic is in orbfe_map_plan.hpp.
 //
 // Columns.  kMapColumns gives every per-keyframe and per-point array its group, element size,
 // default and whether its contents survive growth.  A buffer is filled with its default when it
@@ -22,6 +22,9 @@
 //                and one length column serve both.
 //   feat, depth  per keypoint beside kf_mp (whose rows never move: only orbfe_map_add_keyframe
 //                sets a length), made by the first call that reads or writes them.
+//   kdesc        the keypoints' descriptor rows, 32 bytes each, beside kf_mp as well; made by the
+//                first call of orbfe_refresh.hip that needs it (store_desc_pool), so a handle that
+//                never refreshes a point holds none.
 //
 // What may move when: a column group in store_grow, a pool in store_put_rows / cov_reserve /
 // store_side_pools, a staging buffer in store_borrow, the pinned block in store_pin_reserve; all
@@ -61,7 +64,7 @@ enum { kCtlTouched, kCtlErr, kCtlNKf, kCtlRef, kCtlNMp, kCtlRun, kCtlStatus, kCt
 enum { kResNKf, kResRef, kResNMp, kResStatus, kResDone, kResKept, kResCulled, kResCullStatus, kResValue,
        kResTail = 1024 };
 
-enum { kGroupCoreKf, kGroupCoreMp, kGroupCovis, kGroupCullMp, kGroupCullKf, kMapGroups };
+enum { kGroupCoreKf, kGroupCoreMp, kGroupCovis, kGroupCullMp, kGroupCullKf, kGroupRefMp, kGroupRefKf, kMapGroups };
 enum {
     kColKfKey, kColKfBad, kColKfStamp, kColKfNeigh, kColKfParent, kColKfCnt, kColKfMpOff, kColKfMpLen,
     kColKfChOff, kColKfChLen,
@@ -69,6 +72,8 @@ enum {
     kColCovOff, kColCovCap, kColCovNw, kColCovNo, kColCovFirst, kColCovRes, kColCovPos,
     kColNobs, kColFound, kColVisible, kColFirstKf, kColMark,
     kColThDepth, kColCand,
+    kColRefKf,
+    kColCenter, kColDescSet,
     kMapCols
 };
 
@@ -119,11 +124,18 @@ constexpr MapColumn kMapColumns[kMapCols] = {
     {kGroupCullMp, 4, {false, 0x7f}, false},                // mark: all kMapNoPos between calls
     {kGroupCullKf, 4, {false, 0x00}, true},                 // th_depth: 0.f
     {kGroupCullKf, 4, {false, 0x00}, false},                // cand: all 0 between calls
+    // what MapPoint::UpdateNormalAndDepth and ComputeDistinctiveDescriptors read (orbfe_refresh.hip):
+    // mpRefKF as a keyframe slot, GetCameraCenter(), whether the keyframe's descriptors were set
+    {kGroupRefMp, 4, {false, 0xff}, true},                  // ref_kf: -1
+    {kGroupRefKf, 12, {false, 0x00}, true},                 // center: (0, 0, 0)
+    {kGroupRefKf, 1, {false, 0x00}, true},                  // desc_set
 };
 // what no orbfe_map_set_keyframe_features wrote: octave 0 and no right coordinate; depth -1.f
 constexpr MapFill kFillZero = {false, 0x00};
 constexpr MapFill kFillFeat = {false, 0x00};
 constexpr MapFill kFillDepth = {true, 0xbf800000u};
+constexpr int kMapDescBytes = 32;                         // one row of mDescriptors
+constexpr int kMapMaxLevels = 128;                        // mvScaleFactors of a map
 
 // ---- the device views, one per group: built by orbfe_map::dev(), cov_dev() and cull_dev()
 
@@ -178,6 +190,7 @@ struct CullDev {
     const float* depth;
     const float* th_depth; // [n_kf]
     int* cand;             // [n_kf] all 0 between calls
+    int* ref_kf;           // [n_mp] mpRefKF, or NULL while nobody has made the column
 };
 
 __global__ __launch_bounds__(256) void store_fill_kernel(long long n, unsigned* dst, unsigned v) {
@@ -276,6 +289,10 @@ struct orbfe_map {
     MapPool kf_mp_pool, kf_ch_pool, mp_obs_pool, cov_pool;
     MapPool mp_idx_pool;            // side pool of mp_obs
     MapPool feat_pool, depth_pool;  // side pools of kf_mp
+    MapPool kdesc_pool;             // side pool of kf_mp: kMapDescBytes per keypoint
+    DevBuf scale;                   // mvScaleFactors: kMapMaxLevels floats, made by its setter
+    std::vector<float> h_scale;     // the same; empty: never set
+    std::vector<uint8_t> h_desc_set;  // per keyframe: orbfe_map_set_keyframe_descriptors has run
     DevBuf touched, ctl, local_kf, blk;  // the query's fixed scratch
     DevBuf stage[kStageRoles];
     // scratch that lives across a call's nested mutators: the counters of an UpdateConnections
@@ -353,6 +370,7 @@ CullDev cull_dev(const orbfe_map* m) {
     c.depth = m->depth_pool.buf.as<float>();
     c.th_depth = m->at<float>(kColThDepth);
     c.cand = m->at<int>(kColCand);
+    c.ref_kf = m->group[kGroupRefMp].alloc ? m->at<int>(kColRefKf) : nullptr;
     return c;
 }
 
@@ -462,6 +480,9 @@ int store_reset(orbfe_map* m) {
         return st;
     if ((st = store_fill(m, m->depth_pool.buf.p, sizeof(float),
                          side_pool_plan(m->kf_mp, m->depth_pool.alloc).keep, kFillDepth)))
+        return st;
+    if ((st = store_fill(m, m->kdesc_pool.buf.p, kMapDescBytes, side_pool_plan(m->kf_mp, m->kdesc_pool.alloc).keep,
+                         kFillZero)))
         return st;
     m->kf_mp.reset();
     m->kf_ch.reset();
@@ -653,6 +674,31 @@ int cull_ready(orbfe_map* m) {
     return ORBFE_OK;
 }
 
+// The refresh groups (mpRefKF; camera centres and descriptor flags) cover every point and keyframe
+// of the map, at the core groups' capacities.  ref_made(): whether any call has made mpRefKF.
+bool ref_made(const orbfe_map* m) { return m->group[kGroupRefMp].alloc > 0; }
+int ref_ready_mp(orbfe_map* m) {
+    int st;
+    if (m->n_mp > m->group[kGroupRefMp].alloc && (st = store_grow(m, kGroupRefMp, m->group[kGroupCoreMp].alloc)))
+        return st;
+    m->group[kGroupRefMp].cover(m->n_mp);
+    return ORBFE_OK;
+}
+int ref_ready_kf(orbfe_map* m) {
+    int st;
+    if (m->n_kf > m->group[kGroupRefKf].alloc && (st = store_grow(m, kGroupRefKf, m->group[kGroupCoreKf].alloc)))
+        return st;
+    m->group[kGroupRefKf].cover(m->n_kf);
+    m->h_desc_set.resize((size_t)m->n_kf, 0);
+    return ORBFE_OK;
+}
+
+// The descriptor pool holds what kf_mp's pool holds; rows nobody set read zero.
+int store_desc_pool(orbfe_map* m) {
+    const SidePoolPlan p = side_pool_plan(m->kf_mp, m->kdesc_pool.alloc);
+    return store_grow_pool(m, m->kdesc_pool, kMapDescBytes, p.keep, p.alloc, kFillZero);
+}
+
 int map_reset_ctl(orbfe_map* m) {
     int h[kCtlWords] = {0};
     h[kCtlRef] = -1;
@@ -732,6 +778,8 @@ int orbfe_map_clear(orbfe_map* m) {
         m->h_th_depth.clear();
         m->h_not_erase.clear();
         m->h_to_erase.clear();
+        m->h_scale.clear();
+        m->h_desc_set.clear();
         return map_reset_ctl(m);
     });
 }

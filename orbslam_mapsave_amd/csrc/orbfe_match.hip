@@ -999,6 +999,36 @@ __global__ __launch_bounds__(256) void sbp_kf_cand_kernel(SbpKfArgs a) {
 // smallest median: min over (median << 16 | i).
 constexpr int kDdBlock = 256;
 constexpr int kDdStage = 64;  // descriptors per wave staged in LDS
+
+// The median and winner rule over N descriptors, by one whole wave: row(j, d0, d1) yields
+// descriptor j wherever it lies (LDS, a contiguous block, a keyframe's pool through an index
+// list).  Returns the winner's index in every lane.  Shared with refresh_kernel
+// (orbfe_refresh.hip).
+template <class Row>
+__device__ __forceinline__ int distinctive_best(int N, int lane, Row row) {
+    const int k = (int)(0.5 * (double)(N - 1));  // vDists[0.5*(N-1)]
+    uint32_t key = 0xffffffffu;
+    for (int i = lane; i < N; i += 64) {
+        uint4 a0, a1;
+        row(i, a0, a1);
+        int lo = 0, hi = 256;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            int c = 0;
+            for (int j = 0; j < N; ++j) {
+                uint4 b0, b1;
+                row(j, b0, b1);
+                c += hamming256(a0, a1, b0, b1) <= mid;
+            }
+            if (c > k) hi = mid; else lo = mid + 1;
+        }
+        key = min(key, ((uint32_t)lo << 16) | (uint32_t)i);
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) key = min(key, (uint32_t)__shfl_xor((int)key, s, 64));
+    return (int)(key & 0xffff);
+}
+
 __global__ __launch_bounds__(kDdBlock) void distinctive_kernel(int n_mp, const int* off,
                                                                const uint4* desc, int* best,
                                                                uint4* desc_out) {
@@ -1019,22 +1049,10 @@ __global__ __launch_bounds__(kDdBlock) void distinctive_kernel(int n_mp, const i
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     }
     const uint4* src = staged ? s_d[wid] : d;
-    const int k = (int)(0.5 * (double)(N - 1));  // vDists[0.5*(N-1)]
-    uint32_t key = 0xffffffffu;
-    for (int i = lane; i < N; i += 64) {
-        const uint4 a0 = src[2 * i], a1 = src[2 * i + 1];
-        int lo = 0, hi = 256;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            int c = 0;
-            for (int j = 0; j < N; ++j) c += hamming256(a0, a1, src[2 * j], src[2 * j + 1]) <= mid;
-            if (c > k) hi = mid; else lo = mid + 1;
-        }
-        key = min(key, ((uint32_t)lo << 16) | (uint32_t)i);
-    }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) key = min(key, (uint32_t)__shfl_xor((int)key, s, 64));
-    const int bi = (int)(key & 0xffff);
+    const int bi = distinctive_best(N, lane, [src](int j, uint4& d0, uint4& d1) {
+        d0 = src[2 * j];
+        d1 = src[2 * j + 1];
+    });
     if (lane == 0) best[mp] = bi;
     if (desc_out && lane < 2) desc_out[2 * (size_t)mp + lane] = d[2 * bi + lane];
 }

@@ -88,6 +88,13 @@ EXPORTED = [
     "orbfe_map_get_observations", "orbfe_map_get_bad_flags",
     "orbfe_map_set_not_erase", "orbfe_map_get_erase_flags", "orbfe_map_set_keyframe_bad_flag",
     "orbfe_map_set_erase", "orbfe_map_cull_keyframes",
+    "orbfe_map_set_scale_factors", "orbfe_map_get_scale_factors",
+    "orbfe_map_set_keyframe_centers", "orbfe_map_get_keyframe_centers",
+    "orbfe_map_set_keyframe_descriptors", "orbfe_map_set_keyframe_descriptors_device",
+    "orbfe_map_get_keyframe_descriptors", "orbfe_map_set_point_ref_keyframes",
+    "orbfe_map_get_point_ref_keyframes", "orbfe_map_refresh_points",
+    "orbfe_map_refresh_points_device", "orbfe_map_refresh_keyframe_points",
+    "orbfe_map_process_new_keyframe",
     "orbfe_archive_mat_bytes",
     "orbfe_archive_write_keypoints_device", "orbfe_archive_read_keypoints_device",
     "orbfe_archive_write_descriptors_device", "orbfe_archive_read_descriptors_device",
@@ -222,6 +229,21 @@ def lib() -> C.CDLL:
             L.orbfe_map_set_keyframe_bad_flag.argtypes = [vp, i, i, vp, vp, i, vp, vp, i, vp]
             L.orbfe_map_set_erase.argtypes = [vp, i, i, i, vp, vp, i, vp, vp, i, vp]
             L.orbfe_map_cull_keyframes.argtypes = [vp, i, i, vp, i, i, vp, i, vp, vp, i, vp, vp, i, vp]
+        if hasattr(L, "orbfe_map_refresh_points"):
+            vp, i = C.c_void_p, C.c_int
+            L.orbfe_map_set_scale_factors.argtypes = [vp, i, vp]
+            L.orbfe_map_get_scale_factors.argtypes = [vp, vp, i, vp]
+            L.orbfe_map_set_keyframe_centers.argtypes = [vp, i, vp, vp]
+            L.orbfe_map_get_keyframe_centers.argtypes = [vp, i, vp, vp]
+            L.orbfe_map_set_keyframe_descriptors.argtypes = [vp, i, i, vp]
+            L.orbfe_map_set_keyframe_descriptors_device.argtypes = [vp, i, i, vp]
+            L.orbfe_map_get_keyframe_descriptors.argtypes = [vp, i, i, vp, vp, vp]
+            L.orbfe_map_set_point_ref_keyframes.argtypes = [vp, i, vp, vp]
+            L.orbfe_map_get_point_ref_keyframes.argtypes = [vp, i, vp, vp]
+            L.orbfe_map_refresh_points.argtypes = [vp, i, i, vp, vp, vp]
+            L.orbfe_map_refresh_points_device.argtypes = [vp, i, i, vp, vp, vp]
+            L.orbfe_map_refresh_keyframe_points.argtypes = [vp, i, i, vp, vp]
+            L.orbfe_map_process_new_keyframe.argtypes = [vp, i, vp, vp, i, vp]
         if hasattr(L, "orbfe_archive_mat_bytes"):
             L.orbfe_archive_mat_bytes.restype = C.c_int64
             sz, vp, i = C.c_size_t, C.c_void_p, C.c_int
@@ -958,6 +980,8 @@ MAP_FOUND, MAP_VISIBLE = 0, 1          # ORBFE_MAP_FOUND / ORBFE_MAP_VISIBLE
 MAP_BAD_NOTHING, MAP_BAD_DEFERRED, MAP_BAD_DONE = 0, 1, 2      # ORBFE_MAP_BAD_*
 MAP_CULL_KEPT, MAP_CULL_CULLED, MAP_CULL_DEFERRED = 0, 1, 2    # ORBFE_MAP_CULL_*
 MAP_MAX_CULL_LIST = 4096
+MAP_REFRESH_NORMAL_DEPTH, MAP_REFRESH_DESCRIPTOR, MAP_REFRESH_UNSUPPORTED = 1, 2, 4  # ORBFE_MAP_REFRESH_*
+MAP_MAX_REFRESH_OBS = 1024
 
 
 class LocalMap:
@@ -1441,6 +1465,117 @@ class LocalMap:
         _check("orbfe_map_tracked_map_points", lib().orbfe_map_tracked_map_points(
             self._h, kf, min_obs, C.byref(n)))
         return n.value
+
+    # ---- MapPoint refresh (MapPoint.cc:483-548, 571-619; LocalMapping.cc:140-161)
+    def SetScaleFactors(self, scale) -> None:
+        """mvScaleFactors of the map's keyframes."""
+        s = np.ascontiguousarray(scale, np.float32).reshape(-1)
+        _check("orbfe_map_set_scale_factors", lib().orbfe_map_set_scale_factors(self._h, len(s), ptr(s)))
+
+    def GetScaleFactors(self) -> np.ndarray:
+        s, n = np.zeros(128, np.float32), C.c_int32(0)
+        _check("orbfe_map_get_scale_factors", lib().orbfe_map_get_scale_factors(
+            self._h, ptr(s), len(s), C.byref(n)))
+        return s[:n.value].copy()
+
+    def SetCameraCenter(self, kf_slots, ow) -> None:
+        """GetCameraCenter() of one keyframe (three floats) or of a sequence (n x 3)."""
+        k = self._i32([kf_slots] if np.isscalar(kf_slots) else kf_slots)
+        o = np.ascontiguousarray(ow, np.float32).reshape(-1)
+        if len(o) != 3 * len(k):
+            raise ValueError("three floats per keyframe")
+        _check("orbfe_map_set_keyframe_centers", lib().orbfe_map_set_keyframe_centers(
+            self._h, len(k), ptr(k), ptr(o)))
+
+    def GetCameraCenter(self, kf_slots) -> np.ndarray:
+        k = self._i32([kf_slots] if np.isscalar(kf_slots) else kf_slots)
+        o = np.zeros((len(k), 3), np.float32)
+        _check("orbfe_map_get_keyframe_centers", lib().orbfe_map_get_keyframe_centers(
+            self._h, len(k), ptr(k), ptr(o)))
+        return o[0] if np.isscalar(kf_slots) else o
+
+    def SetDescriptors(self, kf: int, desc=None, d_desc: int | None = None, n: int | None = None) -> None:
+        """mDescriptors of a keyframe: an (n_slots, 32) uint8 array, or ``d_desc`` a device pointer
+        to ``n`` rows (copied on the handle's stream)."""
+        if d_desc is not None:
+            _check("orbfe_map_set_keyframe_descriptors_device",
+                   lib().orbfe_map_set_keyframe_descriptors_device(self._h, kf, int(n), C.c_void_p(d_desc)))
+            return
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        _check("orbfe_map_set_keyframe_descriptors", lib().orbfe_map_set_keyframe_descriptors(
+            self._h, kf, len(d), ptr(d)))
+
+    def GetDescriptors(self, kf: int):
+        """-> (descriptors (n_slots, 32), whether they were ever set)."""
+        d = np.zeros((MAP_MAX_KF_SLOTS, 32), np.uint8)
+        n, s = C.c_int32(0), C.c_int32(0)
+        _check("orbfe_map_get_keyframe_descriptors", lib().orbfe_map_get_keyframe_descriptors(
+            self._h, kf, len(d), ptr(d), C.byref(n), C.byref(s)))
+        return d[:n.value].copy(), bool(s.value)
+
+    def SetReferenceKeyFrame(self, mp_slots, kf_slots) -> None:
+        """mpRefKF of the listed points: keyframe slots or -1."""
+        p = self._i32([mp_slots] if np.isscalar(mp_slots) else mp_slots)
+        k = self._i32([kf_slots] if np.isscalar(kf_slots) else kf_slots)
+        if len(p) != len(k):
+            raise ValueError("one keyframe per point")
+        _check("orbfe_map_set_point_ref_keyframes", lib().orbfe_map_set_point_ref_keyframes(
+            self._h, len(p), ptr(p), ptr(k)))
+
+    def GetReferenceKeyFrame(self, mp_slots):
+        p = self._i32([mp_slots] if np.isscalar(mp_slots) else mp_slots)
+        k = np.full(len(p), -1, np.int32)
+        _check("orbfe_map_get_point_ref_keyframes", lib().orbfe_map_get_point_ref_keyframes(
+            self._h, len(p), ptr(p), ptr(k)))
+        return int(k[0]) if np.isscalar(mp_slots) else k
+
+    def RefreshPoints(self, what: int, mp_slots, arrays: MapPointArrays, d_list: int | None = None,
+                      n: int | None = None, d_result: int | None = None):
+        """UpdateNormalAndDepth (``what & 1``) and ComputeDistinctiveDescriptors (``what & 2``) of
+        the listed points, written into the map-wide device ``arrays``.  Host list -> the masks of
+        what was written per entry; with ``d_list`` (a device pointer to ``n`` slots) the masks go
+        to ``d_result`` if given.  A refusal raises; ORBFE_ERR_UNSUPPORTED raises with ``e.result``
+        holding the masks of the host form (everything else was written)."""
+        if d_list is not None:
+            _check("orbfe_map_refresh_points_device", lib().orbfe_map_refresh_points_device(
+                self._h, what, int(n), C.c_void_p(d_list), C.byref(arrays), C.c_void_p(d_result or 0)))
+            return None
+        p = self._i32(mp_slots)
+        res = np.zeros(len(p), np.uint8)
+        st = lib().orbfe_map_refresh_points(self._h, what, len(p), ptr(p) if len(p) else None,
+                                            C.byref(arrays), ptr(res) if len(p) else None)
+        if st != ORBFE_OK:
+            e = OrbfeError("orbfe_map_refresh_points", st)
+            e.result = res
+            raise e
+        return res
+
+    def UpdateNormalAndDepth(self, mp_slots, arrays: MapPointArrays):
+        return self.RefreshPoints(MAP_REFRESH_NORMAL_DEPTH, [mp_slots] if np.isscalar(mp_slots) else mp_slots, arrays)
+
+    def ComputeDistinctiveDescriptors(self, mp_slots, arrays: MapPointArrays):
+        return self.RefreshPoints(MAP_REFRESH_DESCRIPTOR, [mp_slots] if np.isscalar(mp_slots) else mp_slots, arrays)
+
+    def RefreshKeyFramePoints(self, kf: int, arrays: MapPointArrays,
+                              what: int = MAP_REFRESH_NORMAL_DEPTH | MAP_REFRESH_DESCRIPTOR) -> int:
+        """Both functions over the keyframe's mvpMapPoints where it lies (LocalMapping.cc:518-530)
+        -> the number of entries refreshed."""
+        n = C.c_int32(0)
+        _check("orbfe_map_refresh_keyframe_points", lib().orbfe_map_refresh_keyframe_points(
+            self._h, kf, what, C.byref(arrays), C.byref(n)))
+        return n.value
+
+    def ProcessNewKeyFrame(self, kf: int, arrays: MapPointArrays, recent_cap: int = MAP_MAX_KF_SLOTS):
+        """The map-point loop of LocalMapping::ProcessNewKeyFrame (:140-161) -> the points to append
+        to mlpRecentAddedMapPoints, in index order."""
+        rec = np.zeros(max(recent_cap, 1), np.int32)
+        n = C.c_int32(0)
+        st = lib().orbfe_map_process_new_keyframe(self._h, kf, C.byref(arrays), ptr(rec), recent_cap, C.byref(n))
+        if st != ORBFE_OK:
+            e = OrbfeError("orbfe_map_process_new_keyframe", st)
+            e.count = n.value
+            raise e
+        return rec[:n.value].copy()
 
 
 class ORBmatcher:
